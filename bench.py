@@ -13,6 +13,15 @@ torch is used only as the CPU control plane for N > 1 (gloo: the RCCL unique
 id broadcast, barriers and the max over ranks); no torch GPU state exists.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c3|c3g|c4|c5]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line
+(value, ms_per_step, the hot kernel's roofline from the timed steps' own
+counters).  --dump-outputs DIR also writes the image of the last timed step
+(what a caller of the path reads back, mrt_renderer_read_image) as
+DIR/image.npy.  --full adds everything that takes runs of its own: the
+sustained window after the timed steps, the CPU oracle baseline with the image
+parity legs (fast and precise build), the host noise-table timing and c2i's
+bitwise check against the batched render.
 N > 1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) each
 process is one rank; without it, bench.py starts the N ranks itself (children
 with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, before any HIP call),
@@ -89,7 +98,14 @@ def parse():
     p.add_argument("--max-path-length", type=int, default=0,
                    help="override the config's MAX_PATH_LENGTH (e.g. 5 = primary ray + 4 bounces)")
     p.add_argument("--precise", action="store_true", help="time the parity build instead of the fast build")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run what the headline value does not need: the --sustain "
+                        "window, the CPU oracle baseline + image parity legs, the host noise-table timing and "
+                        "c2i's bitwise image check (each still has its own switch below)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the image of the last timed step (rank 0's, as mrt_renderer_read_image returns it) "
+                        "to DIR/image.npy (float32; above 64 MB a fixed seeded sample of its pixels)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU oracle baseline / parity legs")
     p.add_argument("--bvh", default="sah", choices=["sah", "lbvh", "ploc"],
                    help="BVH builder: host binned SAH (default), device LBVH or device PLOC")
     p.add_argument("--cpu-frames", type=int, default=0,
@@ -114,8 +130,8 @@ def parse():
                    help="rccl: libmrt's RCCL collective (one process per GPU); host: packed tiles through host "
                         "memory and a gloo gather (rehearsal of the N>1 path with several ranks on one GPU)")
     p.add_argument("--sustain", type=float, default=10.0,
-                   help="N=1 batched configs: after the timed steps, keep stepping for this many seconds and "
-                        "report the sustained rate beside the line (0 = off; not the headline value)")
+                   help="with --full, N=1 batched configs: after the timed steps, keep stepping for this many seconds "
+                        "and report the sustained rate beside the line (0 = off; not the headline value)")
     p.add_argument("--no-image-check", action="store_true",
                    help="c2i: skip the bitwise check of the timed image against draw_n (profiling passes)")
     p.add_argument("--sweep-gpus", default="",
@@ -431,6 +447,26 @@ def roofline(args, pmc_path, whole_frame, timed, launch_s, step_s, launches_per_
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: the timed path's result, the [H, W, 4] float32 image a
+    caller reads back after the last timed step, as <out_dir>/image.npy.  An
+    image above 64 MB (C5's 4K frame) is written as a fixed sample of its
+    pixels, [n, 4] in ascending pixel order (row-major index y * W + x drawn
+    with seed 0: the same pixels in every run of the same size)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(img, np.float32)
+    if img.nbytes > DUMP_MAX_BYTES:
+        px = img.reshape(-1, img.shape[-1])
+        n = DUMP_MAX_BYTES // (px.shape[1] * 4)
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+        img = np.ascontiguousarray(px[idx])
+    np.save(os.path.join(out_dir, "image.npy"), img)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.sweep_gpus):
@@ -536,8 +572,10 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     st = r.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r.read_image())
     sustained = None
-    if world == 1 and args.sustain > 0 and not per_frame:
+    if args.full and world == 1 and args.sustain > 0 and not per_frame:
         # a longer window of the same steps (~seconds, visible to an outside
         # utilisation sampler); the headline value stays the K timed steps
         n_s, t_s = 0, time.perf_counter()
@@ -629,18 +667,20 @@ def main():
     # window ahead of the timed region (mrt_renderer_prepare, host threads +
     # one upload).  Both per frame: a progressive render past the window pays
     # the latter inside draw.
-    mrt.noise_table(mrt.DEFAULT_SEED, 0)   # first call imports numpy
-    t_n = time.perf_counter()
-    for f in range(32):
-        mrt.noise_table(mrt.DEFAULT_SEED, f)
-    noise_1t_ms = (time.perf_counter() - t_n) * 1e3 / 32
-    noise = {"noise_ms_per_frame": round(noise_1t_ms, 4),
-             "noise_ms_per_frame_note": "one table generated on one host thread (mrt_noise_table), the "
-                                        "reference's per-frame CPU cost model; not in the timed steps",
+    noise = {"noise_ms_per_frame": None,
              "prepare_ms_per_frame": round(prep["noise_ms"] / max(1, prep["noise_tables"]), 4),
              "prepare_tables": int(prep["noise_tables"]),
              "prepare_note": "mrt_renderer_prepare: the window's tables on the library's host threads + one "
                              "upload, per table"}
+    if args.full:
+        mrt.noise_table(mrt.DEFAULT_SEED, 0)   # first call imports numpy
+        t_n = time.perf_counter()
+        for f in range(32):
+            mrt.noise_table(mrt.DEFAULT_SEED, f)
+        noise_1t_ms = (time.perf_counter() - t_n) * 1e3 / 32
+        noise.update({"noise_ms_per_frame": round(noise_1t_ms, 4),
+                      "noise_ms_per_frame_note": "one table generated on one host thread (mrt_noise_table), the "
+                                                 "reference's per-frame CPU cost model; not in the timed steps"})
     if per_frame:
         noise.update({"timed_tables": int(st["noise_tables"] - base["noise_tables"]),
                       "timed_gen_ms": round(st["noise_ms"] - base["noise_ms"], 3),
@@ -691,7 +731,7 @@ def main():
             "note": "draws_overlapped: calls enqueued while the previous draw still ran on the GPU; "
                     "inflight_waits: calls that waited for the draw 3 back (MaxBuffersInFlight, "
                     "renderer/Renderer.mm:16,593-600)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.shard_of:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.shard_of:
         base_cpu, ref_img, mask, frames = cpu_baseline(cfg, args.cpu_frames or spp)
         result["cpu_baseline"] = base_cpu
         # image match vs the reference restatement (north_star): the timed
@@ -718,7 +758,7 @@ def main():
         result["parity"] = par[0]
         if len(par) > 1:
             result["parity_precise"] = par[1]
-    if per_frame and rank == 0 and world == 1 and not args.no_image_check:
+    if args.full and per_frame and rank == 0 and world == 1 and not args.no_image_check:
         # the timed progressive image == the same frames drawn in 64-frame
         # batches (draw_n), bitwise
         total = int(st["frame_index"])

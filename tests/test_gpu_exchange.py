@@ -173,6 +173,39 @@ def test_bench_self_launches_ranks(gpu):
     assert d["n_gpus"] == 2 and d["image_check"] == "bitwise equal to the 1-GPU render"
 
 
+def test_bench_plain_run_dumps_its_image(gpu, mrt_mod, tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline keys and none of
+    the legs that take runs of their own; --dump-outputs writes the last timed
+    step's image ([H, W, 4] float32), which is the library's own render of the
+    config (C1: reset + 1 frame) bit for bit, and the same from run to run."""
+    imgs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c1", "--steps", "3",
+               "--warmup", "1", "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "Mpaths/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        # value = paths per step / ms_per_step, up to the line's rounding (ms to 3 decimals, value to 3)
+        ms = d["ms_per_step"]
+        assert 256 * 256 / (ms + 0.0006) / 1e3 - 0.001 <= d["value"] <= 256 * 256 / max(1e-4, ms - 0.0006) / 1e3 + 0.001
+        assert d["cpu_baseline"] is None and "sustained" not in d and "parity" not in d
+        assert sorted(os.listdir(out)) == ["image.npy"]
+        imgs.append(np.load(out / "image.npy"))
+        assert imgs[-1].dtype == np.float32 and imgs[-1].shape == (256, 256, 4)
+    assert imgs[0].tobytes() == imgs[1].tobytes()
+    r = mrt_mod.Renderer(mrt_mod.Scene("cornellbox"), 256, 256, 1)
+    r.draw(1)
+    ref = r.read_image()
+    r.close()
+    assert np.isfinite(ref[..., :3]).all() and ref[..., :3].max() > 0
+    assert imgs[0].tobytes() == ref.tobytes()
+
+
 def test_overlapped_exchange_then_resize_reset_and_comm_close(gpu, mrt_mod):
     """A deferred (overlapped) gather is dropped, not unpacked, by resize (the
     buffers were packed for the old size) and by reset, and a flush after the

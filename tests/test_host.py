@@ -350,6 +350,31 @@ def test_bench_child_argv():
     assert argv[2:] == ["--config", "c5", "--steps", "2", "--gpus", "4"]
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the image goes out whole as float32; above the
+    size cap it is a fixed sample of its pixels (same pixels every time, in
+    ascending pixel order) that fits the cap."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    img = np.arange(37 * 53 * 4, dtype=np.float32).reshape(37, 53, 4)
+    bench.dump_outputs(str(tmp_path / "a" / "b"), img)
+    got = np.load(tmp_path / "a" / "b" / "image.npy")
+    assert got.dtype == np.float32 and got.tobytes() == img.tobytes()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1000 * 16)
+    outs = []
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / f"s{k}"), img)
+        outs.append(np.load(tmp_path / f"s{k}" / "image.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (1000, 4) and outs[0].nbytes <= 1000 * 16
+    assert outs[0].tobytes() == outs[1].tobytes()
+    px = outs[0][:, 0].astype(np.int64) // 4            # pixel index of each sampled row
+    assert (np.diff(px) > 0).all() and (outs[0] == img.reshape(-1, 4)[px]).all()
+
+
 def test_stray_diagnostic_env_ignored_without_mrt_diag(mrt_mod, monkeypatch):
     """The library reads its diagnostic MRT_* overrides only under MRT_DIAG=1
     (csrc/diag_env.h): a host that integrates libmrt with stray variables set

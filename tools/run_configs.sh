@@ -1,6 +1,6 @@
 #!/bin/bash
-# Every BASELINE configuration's bench line (GPU box, repo root): default bench
-# (CPU oracle baseline + image parity, fast and precise) for c1..c4 and c2l5
+# Every BASELINE configuration's bench line (from the repository root): bench.py --full
+# (sustained window, CPU oracle baseline + image parity, fast and precise) for c1..c4 and c2l5
 # (C2 at MAX_PATH_LENGTH 5: the primary ray + 4 bounces), and one GPU's 1/8
 # tile share for c2 and c5 (the 8-GPU configuration's per-GPU work).  Timed
 # regions of >= ~1 s (a short one carries the pipeline's fill and drain:
@@ -8,7 +8,7 @@
 # usage: tools/run_configs.sh <outdir>
 OUT=${1:-gpurun_out/configs}
 mkdir -p $OUT
-run() { local name=$1 secs=$2; shift 2; echo "== $name"; timeout -k 10 $secs python3 bench.py "$@" > $OUT/cfg_$name.json 2> $OUT/cfg_$name.log; local rc=$?; tail -c 300 $OUT/cfg_$name.json; echo; echo "== $name rc=$rc"; [ $rc -eq 0 ] || exit $rc; }
+run() { local name=$1 secs=$2; shift 2; echo "== $name"; timeout -k 10 $secs python3 bench.py --full "$@" > $OUT/cfg_$name.json 2> $OUT/cfg_$name.log; local rc=$?; tail -c 300 $OUT/cfg_$name.json; echo; echo "== $name rc=$rc"; [ $rc -eq 0 ] || exit $rc; }
 run c1 300 --config c1 --steps 50 --warmup 5
 run c2 400 --config c2 --steps 100 --warmup 5
 run c2l5 400 --config c2l5 --steps 100 --warmup 5
