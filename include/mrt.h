@@ -198,6 +198,45 @@ int mrt_resolve_shadow(const mrt_scene* scene, uint32_t count, const void* inter
 int mrt_accumulate(const mrt_scene* scene, uint32_t width, uint32_t height, uint32_t frame_index,
                    const void* rays, float* image_rgba, uint32_t flags, void* stream);
 
+/* ---- camera ---------------------------------------------------------------
+ * The reference's rayGenerator has one fixed camera; this is the same
+ * construction with a pose, a field of view and a thin lens.  With (u, v) the
+ * reference's jittered image-plane coordinates of a pixel (u in [-1, 1], v in
+ * [-H/W, H/W]) and s = tan_half_fov:
+ *   pinhole:   c = (u s, v s, -1), w = normalize(c), o = origin
+ *   thin lens: (xi1, xi2) = (z, w) of the frame's raygen noise table at cell
+ *              ((x + 32) % 64, (y + 32) % 64) (not the cell of the pixel's own
+ *              jitter and bounce-0 samples),
+ *              l = lens_radius sqrt(xi1) (cos 2 pi xi2, sin 2 pi xi2),
+ *              w = normalize(c focus_distance - (l.x, l.y, 0)),
+ *              o = origin + right l.x + up l.y
+ *   d = right w.x + up w.y + forward (-w.z)
+ * A camera bitwise equal to mrt_camera_default takes the reference's own code
+ * path (bit-identical images). */
+typedef struct mrt_camera {
+  float origin[3];
+  float right[3], up[3], forward[3];  /* orthonormal, right-handed: right x up = -forward */
+  float tan_half_fov;                 /* half-width of the image plane at distance 1 (reference: 1) */
+  float lens_radius;                  /* 0 = pinhole */
+  float focus_distance;               /* depth (along forward) of the plane in focus; used when lens_radius > 0 */
+} mrt_camera;
+
+/* The reference's camera, exactly: origin (0, 1, 2.35), looking down -z, tan 1. */
+int mrt_camera_default(mrt_camera* out);
+/* Host only.  A pinhole camera at `eye` looking at `target`; fov_x_degrees is
+ * the full horizontal field of view, in (0, 180).  MRT_ERR_INVALID for
+ * eye == target, for `up` parallel to the view direction (or zero) and for a
+ * non-finite argument.  Set lens_radius / focus_distance on the result. */
+int mrt_camera_look_at(const float eye[3], const float target[3], const float up[3],
+                       float fov_x_degrees, mrt_camera* out);
+/* Host only.  MRT_ERR_INVALID (with a message) for a non-finite field, a basis
+ * that is not orthonormal to 1e-4 or not right-handed, tan_half_fov <= 0,
+ * lens_radius < 0, or lens_radius > 0 with focus_distance <= 0. */
+int mrt_camera_check(const mrt_camera* cam);
+/* rayGenerator of `cam` (mrt_raygen is this with mrt_camera_default). */
+int mrt_raygen_camera(const mrt_scene* scene, const mrt_camera* cam, uint32_t width, uint32_t height,
+                      const float* noise, void* rays, uint32_t flags, void* stream);
+
 /* ---- renderer (B-1) ------------------------------------------------------ */
 typedef struct mrt_renderer_desc {
   const mrt_scene* scene;          /* not owned; must outlive the renderer */
@@ -259,6 +298,21 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height);
  * by an exchange or mrt_renderer_tiles_write, and an external image, are
  * cleared here); the cumulative counters of mrt_stats are kept. */
 int mrt_renderer_reset(mrt_renderer* r);
+/* mrt_renderer_reset plus a new camera (checked with mrt_camera_check): after
+ * set_camera(C); draw(n) the image is bitwise that of a fresh renderer with
+ * camera C after draw(n).  A draw uses the camera in force when it was
+ * enqueued, on every render stream: draws already enqueued keep theirs.  The
+ * call does not wait for the GPU: the camera and its candidate lists (rebuilt
+ * on the host for a pinhole camera, under the conditions of the default
+ * camera's; none with a thin lens) go to a device buffer of their own,
+ * uploaded asynchronously and recycled once the draws that read it have
+ * finished (five such buffers, allocated at create / resize for the frame's
+ * size, so this call allocates nothing).  A camera that fails the check or
+ * cannot be installed leaves the renderer as it was, not reset.  Only a host that replaces the camera more than four times while
+ * the first of those cameras' draws is still executing waits for that draw.
+ * The camera persists across mrt_renderer_resize and mrt_renderer_reset. */
+int mrt_renderer_set_camera(mrt_renderer* r, const mrt_camera* cam);
+int mrt_renderer_get_camera(const mrt_renderer* r, mrt_camera* out);
 /* Generate the noise tables for frames [frame_index, frame_index+n) ahead
  * of time and enqueue their upload (the reference regenerates one slot per
  * frame on the CPU, Renderer.mm:486-496).  Blocks on host generation only.

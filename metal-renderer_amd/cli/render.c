@@ -26,6 +26,11 @@
  *                   [--w W] [--h H] [--spp N] [--L L] [--seed S] [--out x.pfm|x.exr]
  *                   [--precise] [--static-noise] [--no-accumulate] [--debug-material]
  *                   [--gpus N] [--device D] [--exchange rccl|host]
+ *                   [--eye x,y,z] [--target x,y,z] [--up x,y,z] [--fov DEGREES]
+ *                   [--aperture LENS_RADIUS] [--focus DISTANCE]
+ * The camera options go through mrt_camera_look_at / mrt_renderer_set_camera
+ * (fov: full horizontal angle; --aperture > 0: a thin lens, focused at --focus
+ * or else on the target); without any of them the reference's camera renders.
  */
 #define _GNU_SOURCE
 #include <errno.h>
@@ -50,7 +55,16 @@ typedef struct {
   uint32_t procedural, width, height, spp, max_path_length, gpus, flags;
   int device;
   uint64_t seed;
+  /* camera (mrt_camera_look_at): set_camera is called when any of these is given */
+  int camera_set, pose_set, focus_set;   /* pose_set: --eye, --target, --up or --fov */
+  float eye[3], target[3], up[3], fov, aperture, focus;
 } options;
+
+/* "x,y,z" -> three floats */
+static int parse_vec3(const char* s, float* out) {
+  char tail = 0;
+  return sscanf(s, "%f,%f,%f%c", &out[0], &out[1], &out[2], &tail) == 3 ? 0 : -1;
+}
 
 static int die(const char* what) {
   fprintf(stderr, "mrt_render: %s: %s\n", what, mrt_last_error());
@@ -62,7 +76,9 @@ static void usage(void) {
           "usage: mrt_render --scene NAME|PATH.obj [--mtl PATH] [--procedural N] [--w W] [--h H]\n"
           "                  [--spp N] [--L L] [--seed S] [--out x.pfm|x.exr] [--precise]\n"
           "                  [--static-noise] [--no-accumulate] [--debug-material]\n"
-          "                  [--gpus N] [--device D] [--exchange rccl|host]\n");
+          "                  [--gpus N] [--device D] [--exchange rccl|host]\n"
+          "                  [--eye x,y,z] [--target x,y,z] [--up x,y,z] [--fov DEGREES]\n"
+          "                  [--aperture LENS_RADIUS] [--focus DISTANCE]\n");
 }
 
 /* --scene cornellbox -> <dir of this executable>/../scenes/cornellbox.obj */
@@ -84,7 +100,9 @@ static int resolve_scene(const char* name, char* path, size_t n) {
 
 static int parse(int argc, char** argv, options* o) {
   *o = (options){.scene = "cornellbox", .out = "render.pfm", .exchange = "rccl", .width = 800, .height = 600,
-                 .spp = 16, .max_path_length = 8, .gpus = 1, .seed = 0x6D6574616C2D7274ull};
+                 .spp = 16, .max_path_length = 8, .gpus = 1, .seed = 0x6D6574616C2D7274ull,
+                 /* the reference's view: from (0, 1, 2.35) down -z, 90 degrees */
+                 .eye = {0.0f, 1.0f, 2.35f}, .target = {0.0f, 1.0f, 1.35f}, .up = {0.0f, 1.0f, 0.0f}, .fov = 90.0f};
   for (int i = 1; i < argc; ++i) {
     const char* a = argv[i];
     const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -101,6 +119,12 @@ static int parse(int argc, char** argv, options* o) {
     else if (VAL("--seed")) o->seed = strtoull(v, NULL, 0);
     else if (VAL("--gpus")) o->gpus = (uint32_t)strtoul(v, NULL, 0);
     else if (VAL("--device")) o->device = atoi(v);
+    else if (VAL("--eye")) { if (parse_vec3(v, o->eye)) { usage(); return -1; } o->camera_set = o->pose_set = 1; }
+    else if (VAL("--target")) { if (parse_vec3(v, o->target)) { usage(); return -1; } o->camera_set = o->pose_set = 1; }
+    else if (VAL("--up")) { if (parse_vec3(v, o->up)) { usage(); return -1; } o->camera_set = o->pose_set = 1; }
+    else if (VAL("--fov")) { o->fov = strtof(v, NULL); o->camera_set = o->pose_set = 1; }
+    else if (VAL("--aperture")) { o->aperture = strtof(v, NULL); o->camera_set = 1; }
+    else if (VAL("--focus")) { o->focus = strtof(v, NULL); o->camera_set = o->focus_set = 1; }
     else if (strcmp(a, "--precise") == 0) o->flags |= MRT_FLAG_PRECISE;
     else if (strcmp(a, "--static-noise") == 0) o->flags |= MRT_FLAG_STATIC_NOISE;
     else if (strcmp(a, "--no-accumulate") == 0) o->flags |= MRT_FLAG_NO_ACCUMULATE;
@@ -193,6 +217,23 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
   rd.flags = o->flags;
   mrt_renderer* r = NULL;
   if (mrt_renderer_create(&rd, &r)) return die("mrt_renderer_create");
+  if (o->camera_set) {   /* every rank sets the same camera */
+    mrt_camera cam;
+    if (!o->pose_set) {   /* only a lens: the reference's pose, bit for bit */
+      if (mrt_camera_default(&cam)) return die("mrt_camera_default");
+    } else if (mrt_camera_look_at(o->eye, o->target, o->up, o->fov, &cam)) {
+      return die("mrt_camera_look_at");
+    }
+    cam.lens_radius = o->aperture;
+    if (o->focus_set) {
+      cam.focus_distance = o->focus;
+    } else if (o->aperture > 0.0f) {   /* focused on the target */
+      float d = 0.0f;
+      for (int k = 0; k < 3; ++k) d += (o->target[k] - o->eye[k]) * cam.forward[k];
+      cam.focus_distance = d;
+    }
+    if (mrt_renderer_set_camera(r, &cam)) return die("mrt_renderer_set_camera");
+  }
   struct timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
   if (mrt_renderer_draw_n(r, o->spp)) return die("mrt_renderer_draw_n");

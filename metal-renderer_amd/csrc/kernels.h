@@ -142,6 +142,10 @@ struct BounceArgs {
   // exact division by the launch's runtime divisors without per-lane
   // reciprocals (magic_div): tiles_x, num_slots, batch
   MagicDiv div_tiles, div_slots, div_batch;
+  // null = the reference's camera, and then the kernels' instantiation
+  // without a camera block is launched (kernels.hip camera_ray<CAM>);
+  // `primary` was built for this camera.  Last, so that no other argument moves.
+  const CameraBlock* camera;
 };
 
 // running-mean accumulation of one frame over the owned tiles
@@ -167,7 +171,9 @@ constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_sha
 
 #define MRT_DECLARE_LAUNCHERS(NS)                                                                         \
   namespace NS {                                                                                          \
-  hipError_t launch_raygen(uint32_t W, uint32_t H, const float* noise, RefRay* rays, hipStream_t s);      \
+  /* cam: host pointer, null = the reference's camera */                                               \
+  hipError_t launch_raygen(uint32_t W, uint32_t H, const float* noise, RefRay* rays,                      \
+                           const CameraBlock* cam, hipStream_t s);                                        \
   /* spill: >= (max_stack - 32) * kIntersectSpillGrid * 256 uint32 when sc.max_stack > kMaxStack */       \
   hipError_t launch_intersect(const DeviceScene& sc, const void* rays, uint32_t stride, uint32_t count,   \
                               RefIntersection* out, uint32_t* spill, hipStream_t s);                      \

@@ -1188,17 +1188,59 @@ struct ShadowRay {
   bool graze;   // cosine to the light below the occluder tree's guard (shadow_root)
 };
 
-// rayGenerator — renderer/Shaders.metal:75-103 (camera fixed at t = 0)
+// rayGenerator — renderer/Shaders.metal:75-103 (camera fixed at t = 0),
+// generalised to a movable camera (kernels.h CameraBlock; DESIGN.md "Camera").
+// cam == nullptr (wave-uniform: a kernel argument) is the reference's camera
+// and keeps its expression, so its bits do not depend on x * 1 + y * 0
+// identities.  Otherwise, with (u, v) as in the reference and s = tan(half fov):
+//   pinhole:   c = (u s, v s, -1), w = normalize(c), o = origin
+//   thin lens: (xi1, xi2) = (z, w) of the frame's raygen table at cell
+//              ((x + 32) % 64, (y + 32) % 64) — not the cell of the pixel's
+//              own jitter and bounce-0 shading sample (shade_noise_cell) —
+//              l = lens sqrt(xi1) (cos 2 pi xi2, sin 2 pi xi2),
+//              w = normalize(c focus - (l, 0)), o = origin + right l.x + up l.y
+//   d = (right w.x + up w.y) + forward (-w.z)
+// The block is read with scalar loads (uniform address) inside this function only.
+// CAM: the kernel instantiation for a moved camera.  The persistent kernels
+// are compiled twice — with CAM = false camera_ray is the reference's
+// expression alone, so the default camera's kernels are the code they were
+// before the camera could move (compiled in one kernel, the moved branch cost
+// the default camera 26 % on C2, measured: DESIGN.md 2.1f "Two instantiations").
+template <bool CAM>
 __device__ __forceinline__ void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, const float4& ns,
-                                           V3& o, V3& d) {
+                                           const float4* table, const CameraBlock* __restrict__ cam, V3& o, V3& d) {
   const float aspect = m_div(float(H), float(W));
   const float wm1 = float(W - 1), hm1 = float(H - 1);
   const float dudvx = m_div(ns.x * 2.0f - 1.0f, wm1);
   const float dudvy = m_div(ns.y * 2.0f - 1.0f, hm1);
   const float ncx = m_div(float(2 * x), wm1) - 1.0f;
   const float ncy = m_div(float(2 * y), hm1) - 1.0f;
-  d = normalize(mk(dudvx + ncx, dudvy + ncy * aspect, -1.0f));
-  o = mk(kCameraX, kCameraY, kCameraZ);   // up - view * 2.35
+  if (!CAM || cam == nullptr) {
+    d = normalize(mk(dudvx + ncx, dudvy + ncy * aspect, -1.0f));
+    o = mk(kCameraX, kCameraY, kCameraZ);   // up - view * 2.35
+    return;
+  }
+  // The block's address goes through an opaque move, so its (loop-invariant)
+  // loads stay here instead of being hoisted out of the persistent kernels'
+  // loops, where 15 more live SGPRs would spill.
+  asm volatile("" : "+s"(cam));
+  const float s = cam->tan_half_fov;
+  const V3 right = mk(cam->right[0], cam->right[1], cam->right[2]), up = mk(cam->up[0], cam->up[1], cam->up[2]);
+  const V3 fwd = mk(cam->forward[0], cam->forward[1], cam->forward[2]);
+  const V3 c = mk((dudvx + ncx) * s, (dudvy + ncy * aspect) * s, -1.0f);
+  o = mk(cam->origin[0], cam->origin[1], cam->origin[2]);
+  V3 w;
+  if (cam->lens_radius > 0.0f) {
+    const float4 ls = table[((x + kNoiseDim / 2) % kNoiseDim) + ((y + kNoiseDim / 2) % kNoiseDim) * kNoiseDim];
+    const float rad = cam->lens_radius * m_sqrt(ls.z), phi = ls.w * 6.28318530718f;
+    const float lx = rad * m_cos(phi), ly = rad * m_sin(phi);
+    const V3 p = mul(c, cam->focus_distance);
+    w = normalize(mk(p.x - lx, p.y - ly, p.z));
+    o = add(add(o, mul(right, lx)), mul(up, ly));
+  } else {
+    w = normalize(c);
+  }
+  d = add(add(mul(right, w.x), mul(up, w.y)), mul(fwd, -w.z));
 }
 
 // Owned slots: slot s of a frame = owned tile k = s >> 12 (global tile
@@ -1485,7 +1527,7 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t* v, uint32_t n
 // Used by bounce_kernel (one launch per bounce) and, with WAVEQ (the wave's
 // own queue: survivors at out_base + their rank among the wave's survivors,
 // no cursors, no class split), by stream_kernel.
-template <int STACK, int MODE, bool WAVEQ = false>
+template <int STACK, int MODE, bool WAVEQ = false, bool CAM = false>
 __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const LdsCtx& cx, const BounceArgs& a,
                                                uint32_t bounce, bool active, uint32_t idx, uint32_t slot,
                                                const RayQueue& in_q, const RayQueue& out_q, uint32_t* cursor,
@@ -1511,7 +1553,7 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
         tag = idx;
         pblk = (x / kPrimaryBlock) + (y / kPrimaryBlock) * a.primary_bx;
         const float4 ns = noise_table(a, fj, 0u)[(x % kNoiseDim) + (y % kNoiseDim) * kNoiseDim];
-        camera_ray(x, y, a.width, a.height, ns, s.o, s.d);
+        camera_ray<CAM>(x, y, a.width, a.height, ns, noise_table(a, fj, 0u), a.camera, s.o, s.d);
       }
     } else {
       // planes 2-3 (throughput, pdf, radiance, ior) are loaded after the
@@ -1657,7 +1699,7 @@ __device__ __forceinline__ void span_end(const BounceArgs& a) {
   if (a.span && (threadIdx.x & 63u) == 0) atomicMax(a.span + 1, (unsigned long long)wall_clock64());
 }
 
-template <int STACK, int MODE>
+template <int STACK, int MODE, bool CAM = false>
 __global__ __launch_bounds__(kBlock, MRT_BOUNCE_WAVES) void bounce_kernel(DeviceScene sc, BounceArgs a) {
   __shared__ uint32_t s_wave[kBlock / 64];
   __shared__ uint32_t s_cursor[2], s_res, s_closed;
@@ -1762,7 +1804,7 @@ __global__ __launch_bounds__(kBlock, MRT_BOUNCE_WAVES) void bounce_kernel(Device
                          : (lo - g_in) * in_chunk + in_chunk - (seg[lo + 1] - seg[lo]) + (idx - seg[lo]);
       }
       STAMP_BEGIN();
-      wrote += bounce_wave<STACK, MODE>(sc, cx, a, a.bounce, active, idx, slot, a.in_q, a.out_q, s_cursor,
+      wrote += bounce_wave<STACK, MODE, false, CAM>(sc, cx, a, a.bounce, active, idx, slot, a.in_q, a.out_q, s_cursor,
                                                out_base, cap, STAMP_REF());
     }
     STAMP_WORK();
@@ -1802,7 +1844,7 @@ __global__ __launch_bounds__(kBlock, MRT_BOUNCE_WAVES) void bounce_kernel(Device
 // the camera rays are gone a wave runs its partial levels, deepest first.
 // No wave ever waits for another, so any grid and any residency is safe.
 // ---------------------------------------------------------------------------
-template <int STACK, int MODE>
+template <int STACK, int MODE, bool CAM = false>
 // Waves per SIMD the stream kernel's registers allow: 6 (80 VGPRs, 6 values
 // spilled to scratch, reloaded outside the traversal loops: tools/
 // scratch_sites.py) under the max-ILP scheduler of its unit (Makefile):
@@ -1907,7 +1949,7 @@ __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(Device
     if (!camera) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     LS_ADD(camera ? 26 : 27, 1);
-    const uint32_t wrote = bounce_wave<STACK, MODE, true>(sc, cx, a, camera ? 0u : lvl, active, idx, slot,
+    const uint32_t wrote = bounce_wave<STACK, MODE, true, CAM>(sc, cx, a, camera ? 0u : lvl, active, idx, slot,
                                                                  a.in_q, a.in_q, nullptr, out, 0u, st);
     if (lvl + 1u < L && lane == 0) {
       cnt[lvl + 1u] += wrote;
@@ -2058,7 +2100,7 @@ __device__ __forceinline__ bool trace_lane(const BounceArgs& a, uint32_t tagv) {
 #define MRT_TRACE(tagv, ...) do {} while (0)
 #endif
 
-template <int STACK, int MODE>
+template <int STACK, int MODE, bool CAM = false>
 __global__ __launch_bounds__(kBlock, MRT_PATH_WAVES) void path_kernel(DeviceScene sc, BounceArgs a) {
   __shared__ uint32_t s_closed;
   __shared__ uint32_t s_count[64];   // rays alive at the start of bounce b + 1 (stats)
@@ -2138,7 +2180,7 @@ __global__ __launch_bounds__(kBlock, MRT_PATH_WAVES) void path_kernel(DeviceScen
         slot_pixel_a(sl, a, x, y);
         if ((x < a.width) && (y < a.height)) {
           const float4 ns = noise_table(a, fj, 0u)[(x % kNoiseDim) + (y % kNoiseDim) * kNoiseDim];
-          camera_ray(x, y, a.width, a.height, ns, ro, rd);
+          camera_ray<CAM>(x, y, a.width, a.height, ns, noise_table(a, fj, 0u), a.camera, ro, rd);
           ps[0 * kBlock] = fbits(1.0f); ps[1 * kBlock] = fbits(1.0f); ps[2 * kBlock] = fbits(1.0f);
           ps[3 * kBlock] = 0u; ps[4 * kBlock] = 0u; ps[5 * kBlock] = 0u;
           ps[6 * kBlock] = fbits(1.0f); ps[7 * kBlock] = fbits(1.00029f);
@@ -2358,12 +2400,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_vgpr(32))) void a
 // ---------------------------------------------------------------------------
 // Stage kernels over the reference AoS records (B-2 ABI, parity replay)
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void raygen_kernel(uint32_t W, uint32_t H, const float4* noise, RefRay* rays) {
+// (the stage kernel takes the camera by value — no device block to keep alive;
+// moved = 0: the reference's camera)
+__global__ __launch_bounds__(kBlock) void raygen_kernel(uint32_t W, uint32_t H, const float4* noise, RefRay* rays,
+                                                        CameraBlock cam, uint32_t moved) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= W * H) return;
   const uint32_t x = i % W, y = i / W;
   V3 o, d;
-  camera_ray(x, y, W, H, noise[(x % kNoiseDim) + (y % kNoiseDim) * kNoiseDim], o, d);
+  camera_ray<true>(x, y, W, H, noise[(x % kNoiseDim) + (y % kNoiseDim) * kNoiseDim], noise, moved ? &cam : nullptr, o, d);
   RefRay& r = rays[i];
   r.origin[0] = o.x; r.origin[1] = o.y; r.origin[2] = o.z;
   r.direction[0] = d.x; r.direction[1] = d.y; r.direction[2] = d.z;
@@ -2561,7 +2606,9 @@ template <int STACK, int MODE>
 hipError_t launch_path_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
   const int stack = STACK < 0 ? -STACK : STACK;
   const DeviceScene f = fit_path_lds_nodes(sc, MODE, stack);
-  path_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), path_lds_bytes(f, MODE, stack), s>>>(f, a);
+  // (a moved camera: the CAM instantiation, same launch bounds and LDS)
+  if (a.camera) path_kernel<STACK, MODE, true><<<dim3(grid), dim3(kBlock), path_lds_bytes(f, MODE, stack), s>>>(f, a);
+  else path_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), path_lds_bytes(f, MODE, stack), s>>>(f, a);
   return hipGetLastError();
 }
 
@@ -2599,7 +2646,8 @@ template <int STACK, int MODE>
 hipError_t launch_bounce_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
   const DeviceScene f = fit_lds_nodes(sc, MODE, STACK < 0 ? -STACK : STACK, grid);
   const size_t lds = bounce_lds_bytes(f, MODE, STACK < 0 ? -STACK : STACK, grid);
-  bounce_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
+  if (a.camera) bounce_kernel<STACK, MODE, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
+  else bounce_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
   return hipGetLastError();
 }
 
@@ -2638,7 +2686,10 @@ hipError_t dispatch(const DeviceScene& sc, const BounceArgs* a, uint32_t stack_e
 // wave-local streaming wavefront: whole-scene-in-LDS scenes, the stack in LDS
 template <int STACK>
 hipError_t launch_stream_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
-  stream_kernel<STACK, kAllLds><<<dim3(grid), dim3(kBlock), bounce_lds_bytes(sc, kAllLds, STACK, 0), s>>>(sc, a);
+  if (a.camera)
+    stream_kernel<STACK, kAllLds, true><<<dim3(grid), dim3(kBlock), bounce_lds_bytes(sc, kAllLds, STACK, 0), s>>>(sc, a);
+  else
+    stream_kernel<STACK, kAllLds><<<dim3(grid), dim3(kBlock), bounce_lds_bytes(sc, kAllLds, STACK, 0), s>>>(sc, a);
   return hipGetLastError();
 }
 // the stream kernel's own persistent grid: every block slot its LDS (scene
@@ -2677,9 +2728,10 @@ bool stream_ok(const DeviceScene& sc, uint32_t stack_entries) {
 // max-ILP machine scheduler (-amdgpu-sched-strategy=max-ilp: C2 +0.45 %,
 // alternating in one call, while the path kernel loses 0.5 % under it).
 #if MRT_EMIT_MAIN
-hipError_t launch_raygen(uint32_t W, uint32_t H, const float* noise, RefRay* rays, hipStream_t s) {
+hipError_t launch_raygen(uint32_t W, uint32_t H, const float* noise, RefRay* rays, const CameraBlock* cam,
+                         hipStream_t s) {
   raygen_kernel<<<dim3(blocks_for(W * H)), dim3(kBlock), 0, s>>>(W, H,
-                     reinterpret_cast<const float4*>(noise), rays);
+                     reinterpret_cast<const float4*>(noise), rays, cam ? *cam : CameraBlock{}, cam ? 1u : 0u);
   return hipGetLastError();
 }
 

@@ -26,6 +26,17 @@ constexpr float kPi = 3.1415926f;                    // PI (truncated, as in the
 // rayGenerator's fixed camera origin up - view * 2.35 (renderer/Shaders.metal:75-103),
 // shared by the kernels' camera_ray and the candidate-list builder (primary.cpp)
 constexpr float kCameraX = 0.0f, kCameraY = 1.0f, kCameraZ = 2.35f;
+// A movable camera (include/mrt.h mrt_camera, the same 15 floats + padding):
+// on the device it is read only by the kernels' camera_ray, through scalar
+// loads.  Launches and the candidate-list builder take a pointer to it;
+// null = the reference's fixed camera above, which keeps its own code path.
+struct CameraBlock {
+  float origin[3];
+  float right[3], up[3], forward[3];   // orthonormal, right x up = -forward
+  float tan_half_fov, lens_radius, focus_distance;
+  float pad_;
+};
+static_assert(sizeof(CameraBlock) == 64, "CameraBlock");
 constexpr unsigned kNoiseDim = 64;                   // NOISE_DIMENSIONS
 constexpr unsigned kNoiseFloats = kNoiseDim * kNoiseDim * 4;
 constexpr unsigned kTile = 64;                       // shard tile edge (== NOISE_DIMENSIONS)

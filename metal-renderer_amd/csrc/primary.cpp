@@ -57,13 +57,36 @@ bool overlaps(const double (*p)[2], const Rect& r, double m) {
 }  // namespace
 
 bool build_primary_lists(const float* tris, uint32_t num_tris, uint32_t W, uint32_t H, uint32_t cap,
-                         PrimaryLists& out) {
+                         const CameraBlock* cam, PrimaryLists& out) {
   out = PrimaryLists{};
+  if (cam && cam->lens_radius > 0.0f) return false;   // a thin lens has no single origin to project from
   if (W < 2 || H < 2 || num_tris == 0 || cap == 0 || cap >= kPrimaryFallback) return false;
   const uint32_t BX = (W + kPrimaryBlock - 1) / kPrimaryBlock, BY = (H + kPrimaryBlock - 1) / kPrimaryBlock;
   const uint64_t nblocks = (uint64_t)BX * BY;
   const double W1 = W - 1.0, H1 = H - 1.0, aspect = (double)H / (double)W;
-  const D3 O = {(double)kCameraX, (double)kCameraY, (double)kCameraZ};   // camera_ray's origin (mrt_layout.h)
+  // camera_ray's origin and basis (mrt_layout.h): the reference's camera, or
+  // the movable one.  Triangles go to camera space in double — lateral
+  // coordinates and depth by the inverse of the basis (below) — and their
+  // projections are divided by s = tan(half fov), which puts them in the
+  // (u, v) units of the block rectangles below.  With the reference's basis
+  // ((1,0,0), (0,1,0), (0,0,-1), s = 1) every product below is exact, so its
+  // lists are the same words as before the camera could move.
+  const D3 O = cam ? D3{cam->origin[0], cam->origin[1], cam->origin[2]}
+                   : D3{(double)kCameraX, (double)kCameraY, (double)kCameraZ};
+  const D3 AX = cam ? D3{cam->right[0], cam->right[1], cam->right[2]} : D3{1.0, 0.0, 0.0};
+  const D3 AY = cam ? D3{cam->up[0], cam->up[1], cam->up[2]} : D3{0.0, 1.0, 0.0};
+  const D3 AZ = cam ? D3{cam->forward[0], cam->forward[1], cam->forward[2]} : D3{0.0, 0.0, -1.0};
+  const double S = cam ? (double)cam->tan_half_fov : 1.0;
+  // camera_ray sends w to right w.x + up w.y + forward (-w.z); camera space is
+  // the inverse of that map, taken from the basis as it is (rows = cross
+  // products / determinant), not its transpose: mrt_camera_check admits a
+  // basis off orthonormal by up to 1e-4, which through the transpose would
+  // move projections by ~1e-4 (1 + |p|^2), the size of kMargin.
+  const D3 CX = cross(AY, AZ), CY = cross(AZ, AX), CZ = cross(AX, AY);
+  const double det = dot(AX, CX);   // -1 for an orthonormal right-handed basis
+  if (!(std::fabs(det) > 0.5)) return false;
+  const D3 IX = {CX.x / det, CX.y / det, CX.z / det}, IY = {CY.x / det, CY.y / det, CY.z / det},
+           IZ = {CZ.x / det, CZ.y / det, CZ.z / det};
   // rectangle of block (bx, by): pixel centres x0..x1, y0..y1 plus the jitter
   auto rect = [&](uint32_t bx, uint32_t by) {
     const double px0 = bx * kPrimaryBlock, px1 = std::min<double>(px0 + kPrimaryBlock - 1, W - 1.0);
@@ -84,7 +107,8 @@ bool build_primary_lists(const float* tris, uint32_t num_tris, uint32_t W, uint3
     D3 rel[3];
     double smin = INFINITY, smax = -INFINITY, R = 0.0;
     for (int i = 0; i < 3; ++i) {
-      rel[i] = sub(v[i], O);
+      const D3 w = sub(v[i], O);
+      rel[i] = {dot(w, IX), dot(w, IY), -dot(w, IZ)};   // camera space: the view is down -z
       const double s = -rel[i].z;   // depth in front of the camera
       smin = std::min(smin, s);
       smax = std::max(smax, s);
@@ -114,6 +138,16 @@ bool build_primary_lists(const float* tris, uint32_t num_tris, uint32_t W, uint3
       const double emax = std::max(l1, l2);
       const double db = 16.0 * kEps * R * (R * emax + l1 * l2) / (nl * hgt);
       m += 2.0 * db * emax * (1.0 + pmax) / smin;
+      // The margin so far is in units of the plane at depth 1; the rectangles
+      // are in (u, v) = that plane / s.  (kMargin also covers camera_ray's own
+      // roundoff: the float rotation of the direction into the camera's basis
+      // adds a few unit roundoffs, ~1e-7 (1 + |p|^2) on the plane, far below
+      // kMargin; for s > 1 the margin is kept, not shrunk.)
+      m /= std::min(S, 1.0);
+      for (int i = 0; i < 3; ++i) {
+        p[i][0] /= S;
+        p[i][1] /= S;
+      }
       if (!(m < 0.25)) all = true;
     }
     if (all) {

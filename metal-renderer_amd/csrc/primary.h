@@ -1,8 +1,9 @@
 // primary.h — camera-ray candidate lists (host build).
 //
 // The reference's camera is fixed (rayGenerator, renderer/Shaders.metal:75-103:
-// origin (0, 1, 2.35), image plane z = -1 in front of it), and bounce 0 sends
-// one ray per pixel through it.  Every camera ray of an 8x8 pixel block —
+// origin (0, 1, 2.35), image plane z = -1 in front of it); a pinhole camera
+// set with mrt_renderer_set_camera is the same construction in its own basis.
+// Bounce 0 sends one ray per pixel through it.  Every camera ray of an 8x8 pixel block —
 // one 64-lane wave of bounce 0 (kernels.hip slot_pixel) — points into a small
 // rectangle of the image plane, so the only triangles such a ray can hit are
 // those whose perspective projection overlaps that rectangle.  For each block
@@ -33,7 +34,10 @@ struct PrimaryLists {
 // tris: 12 floats per leaf-ordered triangle {v0, bits(prim), e1, 0, e2, 0};
 // lists longer than `cap` fall back to the traversal.  Returns false (and an
 // empty result) when the scene is too dense for lists to pay off.
+// cam: the camera the rays leave (mrt_layout.h CameraBlock; null = the
+// reference's).  A thin lens (lens_radius > 0) gets no lists: they assume
+// that every camera ray starts at one point.
 bool build_primary_lists(const float* tris, uint32_t num_tris, uint32_t width, uint32_t height, uint32_t cap,
-                         PrimaryLists& out);
+                         const CameraBlock* cam, PrimaryLists& out);
 
 }  // namespace mrt

@@ -157,6 +157,34 @@ struct FrameSlot {
   bool acc_recorded = false;
 };
 
+// One camera's device data: the CameraBlock the kernels' camera_ray reads and,
+// behind it, the camera-ray candidate lists built for that camera.  A draw
+// launches with pointers into the generation in force when it is enqueued;
+// mrt_renderer_set_camera fills another generation (pinned staging, one
+// asynchronous copy on the next batch's render stream) instead of touching
+// one that launches in flight may read, and a replaced generation is recycled
+// once `retired` — recorded on the main stream, behind the accumulates that
+// follow every render launch of the earlier draws — has completed.
+struct CameraGen {
+  DevBuf dev;                     // [CameraBlock, 64 B][candidate-list words]
+  void* host = nullptr;           // pinned staging of the same bytes
+  size_t host_bytes = 0;
+  hipEvent_t ready = nullptr;     // the upload, on the render stream that carried it
+  hipEvent_t retired = nullptr;
+  bool busy = false;              // replaced, `retired` not yet seen complete
+  bool async = false;             // uploaded asynchronously (`ready` is recorded)
+  uint32_t waited_streams = 0;    // render streams (slots) ordered behind `ready`
+  bool moved = false;             // not the reference's camera: launches get the block's address
+  bool has_lists = false;
+  uint32_t primary_bx = 0;
+  ~CameraGen() {
+    if (ready) (void)hipEventDestroy(ready);
+    if (retired) (void)hipEventDestroy(retired);
+    if (host) (void)hipHostFree(host);
+  }
+};
+constexpr size_t kCameraGens = 5;   // the one in force + four replaced ones whose draws may still execute
+
 // Failure state of one RCCL communicator, shared by the communicator and the
 // renderers that enqueued collectives on it (a renderer may outlive it: a
 // deferred unpack after mrt_comm_destroy).  A collective that reports an
@@ -258,10 +286,14 @@ struct mrt_renderer {
   // A/B).  The path kernel refills lanes one by one, so its lists would be
   // per-lane dependent global loads at refill: C3 -4.8 %, not used there.
   // MRT_PRIMARY=0: off; MRT_PRIMARY_CAP: longest list (12)
+  // The lists belong to a camera: they live in the camera's generation
+  // (CameraGen), rebuilt by mrt_renderer_set_camera; none with a thin lens.
   bool primary_allowed = true;
   uint32_t primary_cap = 12;
-  DevBuf primary;
-  uint32_t primary_bx = 0;
+  mrt_camera camera{};          // the camera in force (mrt_camera_default until set_camera)
+  bool camera_moved = false;    // `camera` is not bitwise the default: the kernels read its block
+  std::vector<std::unique_ptr<CameraGen>> cams;
+  CameraGen* cam_cur = nullptr;
   Exchange x;
   DevBuf reference, display;   // comparison image (mrt_renderer_load_reference) and blit output
   struct DisplaySlot {          // mrt_renderer_display_enqueue / _map: pinned copies of the blit
@@ -343,6 +375,110 @@ int acquire_noise(mrt_renderer* r, int64_t f0, uint32_t n, std::vector<mrt::Nois
   return MRT_OK;
 }
 
+mrt::CameraBlock camera_block(const mrt_camera& c) {
+  mrt::CameraBlock b{};
+  static_assert(sizeof(mrt_camera) == 60 && sizeof(mrt_camera) <= sizeof(mrt::CameraBlock), "mrt_camera");
+  std::memcpy(&b, &c, sizeof(mrt_camera));   // the same fields in the same order
+  return b;
+}
+
+// Put r->camera in force: build its candidate lists (wavefront kernels only,
+// primary_allowed, the cap, a pinhole camera) and upload them with the camera
+// block into a generation no launch in flight reads.  idle: nothing of this
+// renderer is executing (create / resize): a synchronous copy, and every
+// other generation is free.  Otherwise the copy is asynchronous on the next
+// batch's render stream and the host waits for nothing — unless all
+// kCameraGens generations are still read by executing draws.
+int install_camera(mrt_renderer* r, bool idle) {
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  const mrt::CameraBlock cb = camera_block(r->camera);
+  const mrt::CameraBlock* cbp = r->camera_moved ? &cb : nullptr;
+  mrt::PrimaryLists pl;
+  const mrt::BvhResult& b = r->scene->bvh;
+  const bool lists_possible = r->primary_allowed && !r->path_mode;
+  const bool lists = lists_possible && mrt::build_primary_lists(b.tris.data(), (uint32_t)(b.tris.size() / 12), W, H,
+                                                                r->primary_cap, cbp, pl);
+  // capacity: the block and the longest buffer build_primary_lists can return
+  // for this frame size, so a generation never grows between resizes
+  const size_t nblocks = (size_t)((W + mrt::kPrimaryBlock - 1) / mrt::kPrimaryBlock) *
+                         ((H + mrt::kPrimaryBlock - 1) / mrt::kPrimaryBlock);
+  const size_t cap_bytes = sizeof(mrt::CameraBlock) + (lists_possible ? nblocks * (1 + (size_t)r->primary_cap) * 4 : 0);
+  const size_t bytes = sizeof(mrt::CameraBlock) + (lists ? pl.words.size() * 4 : 0);
+  if (bytes > cap_bytes) return fail(MRT_ERR_STATE, "camera: candidate lists exceed their bound");
+  auto size_gen = [&](CameraGen* c) -> int {
+    if (c->dev.bytes < cap_bytes) HIP_TRY(c->dev.alloc(cap_bytes));
+    if (c->host_bytes < cap_bytes) {
+      if (c->host) HIP_TRY(hipHostFree(c->host));
+      c->host = nullptr;
+      c->host_bytes = 0;
+      HIP_TRY(hipHostMalloc(&c->host, cap_bytes, hipHostMallocDefault));
+      c->host_bytes = cap_bytes;
+    }
+    return MRT_OK;
+  };
+  CameraGen* g = nullptr;
+  while (idle && r->cams.size() < kCameraGens) {   // all generations exist from create on
+    r->cams.emplace_back(new CameraGen());
+    CameraGen* c = r->cams.back().get();
+    HIP_TRY(hipEventCreateWithFlags(&c->ready, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->retired, hipEventDisableTiming));
+  }
+  for (auto& c : r->cams) {
+    if (idle) {
+      // The caller synchronised the main stream, which follows every render
+      // launch — but not an upload that no draw followed (set_camera, then
+      // resize): wait for it before its staging is written again.  Every
+      // generation is sized for the new frame here, where allocation's
+      // implicit synchronisation costs nothing, so a later set_camera never
+      // allocates.
+      if (c->async) HIP_TRY(hipEventSynchronize(c->ready));
+      c->async = false;
+      c->busy = false;
+      const int rc = size_gen(c.get());
+      if (rc) return rc;
+    } else {
+      if (c.get() == r->cam_cur) continue;
+      if (c->busy && hipEventQuery(c->retired) == hipSuccess) c->busy = false;
+    }
+    if (!c->busy && !g) g = c.get();
+  }
+  if (!g) {   // every generation is read by draws still executing: wait for one
+    for (auto& c : r->cams)
+      if (c.get() != r->cam_cur) { g = c.get(); break; }
+    HIP_TRY(hipEventSynchronize(g->retired));
+    g->busy = false;
+  }
+  if (g->dev.bytes < cap_bytes || g->host_bytes < cap_bytes)   // sized in the idle path for this frame size
+    return fail(MRT_ERR_STATE, "camera: generation smaller than the frame's bound");
+  std::memcpy(g->host, &cb, sizeof(cb));
+  if (lists) std::memcpy(static_cast<char*>(g->host) + sizeof(cb), pl.words.data(), pl.words.size() * 4);
+  if (idle) {
+    HIP_TRY(hipMemcpy(g->dev.p, g->host, bytes, hipMemcpyHostToDevice));
+    g->async = false;
+    g->waited_streams = ~0u;
+  } else {
+    const uint32_t slot = r->slot_next;
+    HIP_TRY(hipMemcpyAsync(g->dev.p, g->host, bytes, hipMemcpyHostToDevice, r->slots[slot].stream));
+    HIP_TRY(hipEventRecord(g->ready, r->slots[slot].stream));
+    g->async = true;
+    g->waited_streams = 1u << slot;
+    if (CameraGen* old = r->cam_cur) {
+      // (a generation replaced before any draw used it: its upload, on a
+      // render stream, must also be over before it is recycled)
+      if (old->async) HIP_TRY(hipStreamWaitEvent(r->stream, old->ready, 0));
+      HIP_TRY(hipEventRecord(old->retired, r->stream));
+      old->busy = true;
+    }
+  }
+  g->moved = r->camera_moved;
+  g->has_lists = lists;
+  g->primary_bx = lists ? pl.blocks_x : 0;
+  r->cam_cur = g;
+  r->stats.primary_blocks = lists ? pl.listed_blocks : 0;
+  r->stats.primary_mean = lists ? (float)pl.mean_count : 0.0f;
+  return MRT_OK;
+}
+
 int alloc_frame_buffers(mrt_renderer* r) {
   const uint32_t W = r->desc.width, H = r->desc.height;
   const uint32_t S = std::max<uint32_t>(1, r->desc.shard_count);
@@ -402,17 +538,8 @@ int alloc_frame_buffers(mrt_renderer* r) {
   r->stats.kernel = r->path_mode ? 1u : (r->stream_mode ? 2u : 0u);
   r->stats.inflight = r->inflight;
   {
-    mrt::PrimaryLists pl;
-    const mrt::BvhResult& b = r->scene->bvh;
-    HIP_TRY(r->primary.alloc(0));
-    r->primary_bx = 0;
-    if (r->primary_allowed && !r->path_mode &&
-        mrt::build_primary_lists(b.tris.data(), (uint32_t)(b.tris.size() / 12), W, H, r->primary_cap, pl)) {
-      HIP_TRY(upload(r->primary, pl.words.data(), pl.words.size() * 4));
-      r->primary_bx = pl.blocks_x;
-      r->stats.primary_blocks = pl.listed_blocks;
-      r->stats.primary_mean = (float)pl.mean_count;
-    }
+    const int rc = install_camera(r, true);
+    if (rc) return rc;
   }
   // the render streams do not wait on the main stream: its memsets above
   // (segments, image) complete before any batch is queued
@@ -1469,7 +1596,96 @@ int mrt_accel_destroy(mrt_accel* accel) {
 int mrt_raygen(const mrt_scene* scene, uint32_t W, uint32_t H, const float* noise, void* rays, uint32_t flags,
                void* stream) {
   if (!scene || !noise || !rays || W < 2 || H < 2) return fail(MRT_ERR_INVALID, "mrt_raygen: bad argument");
-  STAGE_CALL(launch_raygen(W, H, noise, (mrt::RefRay*)rays, (hipStream_t)stream));
+  STAGE_CALL(launch_raygen(W, H, noise, (mrt::RefRay*)rays, nullptr, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+// ---- camera (include/mrt.h) -------------------------------------------------
+int mrt_camera_default(mrt_camera* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_camera_default: null camera");
+  // rayGenerator's camera (mrt_layout.h kCameraX/Y/Z), looking down -z
+  *out = mrt_camera{{mrt::kCameraX, mrt::kCameraY, mrt::kCameraZ}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f},
+                    {0.0f, 0.0f, -1.0f}, 1.0f, 0.0f, 0.0f};
+  return MRT_OK;
+}
+
+int mrt_camera_check(const mrt_camera* cam) {
+  if (!cam) return fail(MRT_ERR_INVALID, "camera: null");
+  const float* f = cam->origin;   // 15 consecutive floats
+  for (int i = 0; i < 15; ++i)
+    if (!std::isfinite(f[i])) return fail(MRT_ERR_INVALID, "camera: a field is not finite");
+  auto dotd = [](const float* a, const float* b) {
+    return (double)a[0] * b[0] + (double)a[1] * b[1] + (double)a[2] * b[2];
+  };
+  const float* ax[3] = {cam->right, cam->up, cam->forward};
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j)
+      if (std::fabs(dotd(ax[i], ax[j]) - (i == j ? 1.0 : 0.0)) > 1e-4)
+        return fail(MRT_ERR_INVALID, "camera: right, up, forward are not orthonormal to 1e-4");
+  const double cx[3] = {(double)cam->right[1] * cam->up[2] - (double)cam->right[2] * cam->up[1],
+                        (double)cam->right[2] * cam->up[0] - (double)cam->right[0] * cam->up[2],
+                        (double)cam->right[0] * cam->up[1] - (double)cam->right[1] * cam->up[0]};
+  if (!(cx[0] * cam->forward[0] + cx[1] * cam->forward[1] + cx[2] * cam->forward[2] < 0.0))
+    return fail(MRT_ERR_INVALID, "camera: the basis is not right-handed (right x up must be -forward)");
+  if (!(cam->tan_half_fov > 0.0f)) return fail(MRT_ERR_INVALID, "camera: tan_half_fov must be positive");
+  if (cam->lens_radius < 0.0f) return fail(MRT_ERR_INVALID, "camera: lens_radius must not be negative");
+  if (cam->lens_radius > 0.0f && !(cam->focus_distance > 0.0f))
+    return fail(MRT_ERR_INVALID, "camera: a lens needs a positive focus_distance");
+  return MRT_OK;
+}
+
+int mrt_camera_look_at(const float eye[3], const float target[3], const float up[3], float fov_x_degrees,
+                       mrt_camera* out) {
+  if (!eye || !target || !up || !out) return fail(MRT_ERR_INVALID, "mrt_camera_look_at: null argument");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(eye[i]) || !std::isfinite(target[i]) || !std::isfinite(up[i]))
+      return fail(MRT_ERR_INVALID, "mrt_camera_look_at: an argument is not finite");
+  if (!(fov_x_degrees > 0.0f && fov_x_degrees < 180.0f))
+    return fail(MRT_ERR_INVALID, "mrt_camera_look_at: fov_x_degrees must lie in (0, 180)");
+  double f[3] = {(double)target[0] - eye[0], (double)target[1] - eye[1], (double)target[2] - eye[2]};
+  const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+  if (!(fl > 0.0)) return fail(MRT_ERR_INVALID, "mrt_camera_look_at: eye and target coincide");
+  for (double& v : f) v /= fl;
+  const double ul = std::sqrt((double)up[0] * up[0] + (double)up[1] * up[1] + (double)up[2] * up[2]);
+  double r[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+  const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  if (!(ul > 0.0) || !(rl > 1e-6 * ul))
+    return fail(MRT_ERR_INVALID, "mrt_camera_look_at: up is zero or parallel to the view direction");
+  for (double& v : r) v /= rl;
+  const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
+  mrt_camera c{};
+  for (int i = 0; i < 3; ++i) {
+    c.origin[i] = eye[i];
+    c.right[i] = (float)r[i];
+    c.up[i] = (float)u[i];
+    c.forward[i] = (float)f[i];
+  }
+  c.tan_half_fov = (float)std::tan((double)fov_x_degrees * (3.14159265358979323846 / 360.0));
+  c.lens_radius = 0.0f;
+  c.focus_distance = 0.0f;
+  const int rc = mrt_camera_check(&c);   // (e.g. a field of view whose tangent overflows a float)
+  if (rc) return rc;
+  *out = c;
+  return MRT_OK;
+}
+
+namespace {
+bool camera_is_default(const mrt_camera& c) {
+  mrt_camera d;
+  (void)mrt_camera_default(&d);
+  return std::memcmp(&c, &d, sizeof(mrt_camera)) == 0;
+}
+}  // namespace
+
+int mrt_raygen_camera(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, const float* noise,
+                      void* rays, uint32_t flags, void* stream) {
+  if (!scene || !cam || !noise || !rays || W < 2 || H < 2)
+    return fail(MRT_ERR_INVALID, "mrt_raygen_camera: bad argument");
+  const int rc = mrt_camera_check(cam);
+  if (rc) return rc;
+  const mrt::CameraBlock cb = camera_block(*cam);
+  STAGE_CALL(launch_raygen(W, H, noise, (mrt::RefRay*)rays, camera_is_default(*cam) ? nullptr : &cb,
+                           (hipStream_t)stream));
   return MRT_OK;
 }
 
@@ -1630,6 +1846,7 @@ int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out) {
   // a stream created before the render streams pushed a render stream onto a
   // queue another stream's work serialises with (C2 -10 %, C4 -7 %, measured r6)
   HIP_TRY(r->noise->init());
+  (void)mrt_camera_default(&r->camera);
   int rc = alloc_frame_buffers(r.get());
   if (rc) return rc;
   *out = r.release();
@@ -1665,6 +1882,31 @@ int mrt_renderer_reset(mrt_renderer* r) {
   }
   r->frame_index = 0;
   r->stats.frame_index = 0;   // cumulative counters (paths, A, kernel time) persist
+  return MRT_OK;
+}
+
+int mrt_renderer_set_camera(mrt_renderer* r, const mrt_camera* cam) {
+  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
+  int rc = mrt_camera_check(cam);
+  if (rc) return rc;
+  // lists and upload first: a camera that cannot be installed leaves the
+  // renderer as it was — the previous camera in force, nothing reset
+  const mrt_camera old = r->camera;
+  const bool old_moved = r->camera_moved;
+  r->camera = *cam;
+  r->camera_moved = !camera_is_default(*cam);
+  rc = install_camera(r, false);
+  if (rc) {
+    r->camera = old;
+    r->camera_moved = old_moved;
+    return rc;
+  }
+  return mrt_renderer_reset(r);
+}
+
+int mrt_renderer_get_camera(const mrt_renderer* r, mrt_camera* out) {
+  if (!r || !out) return fail(MRT_ERR_INVALID, "mrt_renderer_get_camera: null argument");
+  *out = r->camera;
   return MRT_OK;
 }
 
@@ -1771,6 +2013,12 @@ int mrt_renderer_draw_n(mrt_renderer* r, uint32_t n) {
       HIP_TRY(hipStreamWaitEvent(fs.stream, nc->ready, 0));
       nc->waited_streams |= 1u << slot;
     }
+    // the camera generation's upload, likewise (set_camera with draws in flight)
+    CameraGen* cg = r->cam_cur;
+    if (!(cg->waited_streams & (1u << slot))) {
+      HIP_TRY(hipStreamWaitEvent(fs.stream, cg->ready, 0));
+      cg->waited_streams |= 1u << slot;
+    }
     uint32_t* seg = fs.segments.as<uint32_t>();
     uint32_t* meta = seg + 4 * (size_t)r->grid;
     for (uint32_t b = 0; b < launches_per_batch; ++b) {
@@ -1812,8 +2060,10 @@ int mrt_renderer_draw_n(mrt_renderer* r, uint32_t n) {
       a.radiance = radiance;
       a.stack_spill = fs.spill.as<uint32_t>();
       a.bounce_counts = cnt + (size_t)k * L;
-      a.primary = r->primary.as<uint32_t>();
-      a.primary_bx = r->primary_bx;
+      a.camera = cg->moved ? cg->dev.as<mrt::CameraBlock>() : nullptr;
+      a.primary = cg->has_lists ? reinterpret_cast<const uint32_t*>(cg->dev.as<char>() + sizeof(mrt::CameraBlock))
+                                : nullptr;
+      a.primary_bx = cg->primary_bx;
       a.span = r->wall_khz > 0.0
                    ? reinterpret_cast<unsigned long long*>(static_cast<char*>(d.counters.p) + span_off) + 2 * k
                    : nullptr;

@@ -141,6 +141,42 @@ class Stats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Camera(ctypes.Structure):
+    """mrt_camera (include/mrt.h): pose, field of view and thin lens.  Build one
+    with Camera.default() (the reference's fixed camera) or Camera.look_at()."""
+    _fields_ = [
+        ("origin", ctypes.c_float * 3),
+        ("right", ctypes.c_float * 3), ("up", ctypes.c_float * 3), ("forward", ctypes.c_float * 3),
+        ("tan_half_fov", ctypes.c_float), ("lens_radius", ctypes.c_float), ("focus_distance", ctypes.c_float),
+    ]
+
+    @classmethod
+    def default(cls) -> "Camera":
+        c = cls()
+        _check(lib().mrt_camera_default(ctypes.byref(c)), "mrt_camera_default")
+        return c
+
+    @classmethod
+    def look_at(cls, eye, target, up, fov_x_degrees: float, lens_radius: float = 0.0,
+                focus_distance: float = 0.0) -> "Camera":
+        """A camera at `eye` looking at `target`; fov_x_degrees is the full
+        horizontal field of view.  lens_radius > 0 makes it a thin lens focused
+        at depth focus_distance along the view direction."""
+        c = cls()
+        v3 = ctypes.c_float * 3
+        _check(lib().mrt_camera_look_at(v3(*eye), v3(*target), v3(*up), fov_x_degrees, ctypes.byref(c)),
+               "mrt_camera_look_at")
+        c.lens_radius, c.focus_distance = lens_radius, focus_distance
+        c.check()
+        return c
+
+    def check(self) -> None:
+        _check(lib().mrt_camera_check(ctypes.byref(self)), "mrt_camera_check")
+
+    def as_dict(self) -> dict:
+        return {k: _plain(getattr(self, k)) for k, _ in self._fields_}
+
+
 EXPORTED = [
     "mrt_scene_create", "mrt_scene_info_get", "mrt_scene_export", "mrt_scene_destroy", "mrt_scene_check_bvh",
     "mrt_raygen", "mrt_intersect", "mrt_shade", "mrt_resolve_shadow", "mrt_accumulate",
@@ -158,6 +194,8 @@ EXPORTED = [
     "mrt_renderer_display_enqueue", "mrt_renderer_display_map",
     "mrt_debug_lanes", "mrt_debug_exchange_unpack", "mrt_debug_box_margin",
     "mrt_debug_magic_div", "mrt_comm_set_timeout", "mrt_comm_check", "mrt_debug_comm_fail",
+    "mrt_camera_default", "mrt_camera_look_at", "mrt_camera_check", "mrt_raygen_camera",
+    "mrt_renderer_set_camera", "mrt_renderer_get_camera",
 ]
 
 _lib = None
@@ -240,6 +278,13 @@ def lib() -> ctypes.CDLL:
         "mrt_renderer_display": [vp, u32, ctypes.c_float, vp, ctypes.c_size_t],
         "mrt_renderer_display_enqueue": [vp, u32, ctypes.c_float, u32],
         "mrt_renderer_display_map": [vp, u32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)],
+        "mrt_camera_default": [ctypes.POINTER(Camera)],
+        "mrt_camera_look_at": [ctypes.c_float * 3, ctypes.c_float * 3, ctypes.c_float * 3, ctypes.c_float,
+                               ctypes.POINTER(Camera)],
+        "mrt_camera_check": [ctypes.POINTER(Camera)],
+        "mrt_raygen_camera": [vp, ctypes.POINTER(Camera), u32, u32, vp, vp, u32, vp],
+        "mrt_renderer_set_camera": [vp, ctypes.POINTER(Camera)],
+        "mrt_renderer_get_camera": [vp, ctypes.POINTER(Camera)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -409,6 +454,17 @@ class Renderer:
     def reset(self) -> None:
         _check(lib().mrt_renderer_reset(self._h), "mrt_renderer_reset")
 
+    def set_camera(self, camera: Camera) -> None:
+        """reset() plus a new camera; draws already enqueued keep theirs, and
+        the call does not wait for the GPU (mrt_renderer_set_camera)."""
+        _check(lib().mrt_renderer_set_camera(self._h, ctypes.byref(camera)), "mrt_renderer_set_camera")
+
+    @property
+    def camera(self) -> Camera:
+        c = Camera()
+        _check(lib().mrt_renderer_get_camera(self._h, ctypes.byref(c)), "mrt_renderer_get_camera")
+        return c
+
     def prepare(self, frames: int) -> None:
         _check(lib().mrt_renderer_prepare(self._h, frames), "mrt_renderer_prepare")
 
@@ -541,8 +597,13 @@ def _flags(precise):
 
 
 def raygen(scene: Scene, width: int, height: int, noise_ptr: int, rays_ptr: int, precise=True, stream=None,
-           sync=True):
-    _check(lib().mrt_raygen(scene.handle, width, height, noise_ptr, rays_ptr, _flags(precise), stream), "mrt_raygen")
+           sync=True, camera: Camera | None = None):
+    if camera is None:
+        _check(lib().mrt_raygen(scene.handle, width, height, noise_ptr, rays_ptr, _flags(precise), stream),
+               "mrt_raygen")
+    else:
+        _check(lib().mrt_raygen_camera(scene.handle, ctypes.byref(camera), width, height, noise_ptr, rays_ptr,
+                                       _flags(precise), stream), "mrt_raygen_camera")
     if sync:
         synchronize(stream)
 

@@ -13,6 +13,10 @@
 // perturbed by a random -1 / 0 / +1 ulp per use, the documented accuracy of
 // v_rcp_f32 / v_rsq_f32 — so the lists are checked against the answers the
 // benchmarked build can give, not only the IEEE ones.
+// Arguments 8-20 (all 13 or none): a moved pinhole camera — origin, right,
+// up, forward, tan_half_fov of mrt_camera (include/mrt.h).  The lists are then
+// built for that camera and the rays formed with camera_ray's arithmetic for a
+// camera block (scale by tan_half_fov, normalise, rotate into the basis).
 // build: g++ -O2 -std=c++17 -ffp-contract=off -I../metal-renderer_amd/csrc primary_check.cpp
 //        ../metal-renderer_amd/csrc/{scene,bvh,primary}.cpp
 #include <cmath>
@@ -71,9 +75,50 @@ bool tri_bary(V o, V d, V v0, V e1, V e2, float& t) {
   return (det != 0.0f) & (b1 >= 0.0f) & (b1 <= 1.0f) & (b2 >= 0.0f) & (b1 + b2 <= 1.0f);
 }
 
+const CameraBlock* g_cam = nullptr;   // a moved pinhole camera (arguments 8-20); null = the reference's
+
+// kernels.hip camera_ray with a camera block (pinhole): c = (u s, v s, -1),
+// w = normalize(c), d = (right w.x + up w.y) + forward (-w.z)
+template <bool F>
+void moved_camera_ray(const CameraBlock& c, float u, float v, V& o, V& d) {
+  o = {c.origin[0], c.origin[1], c.origin[2]};
+  const V q = {u * c.tan_half_fov, v * c.tan_half_fov, -1.0f};
+  V w;
+  if (F) {
+    const float r = approx(1.0f / std::sqrt(dot<F>(q, q)));
+    w = {q.x * r, q.y * r, q.z * r};
+    d = {std::fma(c.forward[0], -w.z, std::fma(c.up[0], w.y, c.right[0] * w.x)),
+         std::fma(c.forward[1], -w.z, std::fma(c.up[1], w.y, c.right[1] * w.x)),
+         std::fma(c.forward[2], -w.z, std::fma(c.up[2], w.y, c.right[2] * w.x))};
+    return;
+  }
+  const float l = std::sqrt(dot<F>(q, q));
+  w = {q.x * (1.0f / l), q.y * (1.0f / l), q.z * (1.0f / l)};
+  d = {(c.right[0] * w.x + c.up[0] * w.y) + c.forward[0] * -w.z,
+       (c.right[1] * w.x + c.up[1] * w.y) + c.forward[1] * -w.z,
+       (c.right[2] * w.x + c.up[2] * w.y) + c.forward[2] * -w.z};
+}
+
 template <bool F>
 void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, float nsx, float nsy, V& o, V& d) {
   const float wm1 = float(W - 1), hm1 = float(H - 1);
+  if (g_cam) {
+    float u, v;
+    if (F) {
+      const float rw = approx(1.0f / float(W)), rw1 = approx(1.0f / wm1), rh1 = approx(1.0f / hm1);
+      const float aspect = float(H) * rw;
+      const float dudvx = (nsx * 2.0f - 1.0f) * rw1, dudvy = (nsy * 2.0f - 1.0f) * rh1;
+      u = dudvx + std::fma(float(2 * x), rw1, -1.0f);
+      v = std::fma(std::fma(float(2 * y), rh1, -1.0f), aspect, dudvy);
+    } else {
+      const float aspect = float(H) / float(W);
+      const float dudvx = (nsx * 2.0f - 1.0f) / wm1, dudvy = (nsy * 2.0f - 1.0f) / hm1;
+      u = dudvx + (float(2 * x) / wm1 - 1.0f);
+      v = dudvy + (float(2 * y) / hm1 - 1.0f) * aspect;
+    }
+    moved_camera_ray<F>(*g_cam, u, v, o, d);
+    return;
+  }
   o = {kCameraX, kCameraY, kCameraZ};   // mrt_layout.h, shared with kernels.hip camera_ray
   if (F) {   // m_div(a, b) = a * rcp(b), contracted where the compiler can
     const float rw = approx(1.0f / float(W)), rw1 = approx(1.0f / wm1), rh1 = approx(1.0f / hm1);
@@ -148,7 +193,7 @@ uint64_t check(const BvhResult& b, const PrimaryLists& pl, uint32_t T, uint32_t 
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::fprintf(stderr, "usage: primary_check scene.obj W H [jitters] [procedural_tris] [cap] [fast]\n");
+    std::fprintf(stderr, "usage: primary_check scene.obj W H [jitters] [procedural_tris] [cap] [fast] [camera: 13 floats]\n");
     return 2;
   }
   const uint32_t W = (uint32_t)std::atoi(argv[2]), H = (uint32_t)std::atoi(argv[3]);
@@ -156,6 +201,16 @@ int main(int argc, char** argv) {
   const uint32_t proc = argc > 5 ? (uint32_t)std::atoi(argv[5]) : 0;
   const uint32_t cap = argc > 6 ? (uint32_t)std::atoi(argv[6]) : 12;
   g_fast = argc > 7 && std::atoi(argv[7]) != 0;
+  CameraBlock cam{};
+  if (argc > 8) {   // a moved pinhole camera: the 13 floats of mrt_camera up to tan_half_fov
+    if (argc != 21) {
+      std::fprintf(stderr, "camera: origin(3) right(3) up(3) forward(3) tan_half_fov expected after [fast]\n");
+      return 2;
+    }
+    float* f = cam.origin;
+    for (int i = 0; i < 13; ++i) f[i] = std::strtof(argv[8 + i], nullptr);
+    g_cam = &cam;
+  }
   HostScene sc;
   std::string err;
   if (!import_obj(argv[1], "", sc, err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 2; }
@@ -168,7 +223,7 @@ int main(int argc, char** argv) {
                  err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 2; }
   const uint32_t T = (uint32_t)(b.tris.size() / 12);
   PrimaryLists pl;
-  const bool built = build_primary_lists(b.tris.data(), T, W, H, cap, pl);
+  const bool built = build_primary_lists(b.tris.data(), T, W, H, cap, g_cam, pl);
   if (!built) {
     std::printf("violations 0 blocks %u listed 0 mean 0 (lists not built)\n", (W + 7) / 8 * ((H + 7) / 8));
     return 0;
