@@ -141,6 +141,7 @@ def _render_gpu(mrt_mod, sc, W, H, L, frames, precise, shard=(0, 1), seed=SEED):
     ("white-box", 80, 60, 8, 2),
     ("CornellBox-Water-plastic", 48, 36, 8, 2),
     ("CornellBox-Water-mirror", 40, 30, 3, 2),
+    ("CornellBox-Water", 48, 36, 8, 2),
 ])
 def test_render_parity_precise(gpu, mrt_mod, oracle_mod, scene, W, H, L, frames):
     sc, osc = _scene(mrt_mod, scene), _oscene(oracle_mod, mrt_mod, scene)

@@ -18,7 +18,9 @@ import os
 import numpy as np
 import pytest
 
+import roomgen
 from helpers import SEED
+from test_convex_occluders import _recip
 
 
 def _supporting_planes(V, I, light_pts):
@@ -50,7 +52,9 @@ def _fma(a, b, c):
 
 
 def _tri_t(o, d, v0, e1, e2, fma):
-    """kernels.hip tri_bary in float32: (t, inside)."""
+    """kernels.hip tri_bary in float32: (t, inside).  fma: False (IEEE), True
+    (FMA contraction) or "rcp" (FMA contraction and the fast build's approximate
+    reciprocal, test_convex_occluders._recip)."""
     f32 = np.float32
 
     def cross(a, b):
@@ -70,7 +74,7 @@ def _tri_t(o, d, v0, e1, e2, fma):
     p = cross(d, e2)
     det = dot(e1, p)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        inv = f32(1.0) / det
+        inv = _recip(np.asarray(det, f32), fma)
         s = o - v0
         b1 = dot(s, p) * inv
         q = cross(s, e1)
@@ -115,9 +119,12 @@ def test_occluder_planes_of_the_shipped_scenes(mrt_mod):
     assert w.info["occluder_planes"] == 0
 
 
-@pytest.mark.parametrize("fma", [False, True])
-def test_culled_triangles_never_occlude(mrt_mod, fma):
-    s = mrt_mod.Scene("cornellbox", device=-1)
+def _check_culled(mrt_mod, obj, fma):
+    """From origins inside every culled plane by the margin — half of them at
+    1-2 margins from a culled plane, an eighth within 30 margins of the culled
+    plane the light is nearest to (the Cornell box's ceiling) — no culled
+    triangle reports a hit in [0, t_light] on the way to a light sample."""
+    s = mrt_mod.Scene(obj, device=-1)
     e = s.export()
     V = e["vertices"]["v"]
     I = e["indices"]
@@ -126,6 +133,7 @@ def test_culled_triangles_never_occlude(mrt_mod, fma):
     planes, culled = _supporting_planes(V, I, light_pts)
     assert culled.sum() == s.info["occluder_culled"] and len(planes) == s.info["occluder_planes"]
     margin = np.float32(s.info["occluder_margin"])
+    s.close()
 
     rng = np.random.default_rng(SEED)
     n = 120_000
@@ -137,9 +145,13 @@ def test_culled_triangles_never_occlude(mrt_mod, fma):
     dist = margin * rng.uniform(1.0, 2.0, k)
     foot = o[:k] - ((o[:k].astype(np.float64) * pl[:, :3]).sum(1) - pl[:, 3])[:, None] * pl[:, :3]
     o[:k] = (foot - dist[:, None] * pl[:, :3]).astype(np.float32)
-    # origins near the ceiling (shadow rays grazing the plane the light hangs under)
+    # origins near the plane the light is nearest to (shadow rays grazing the
+    # plane the light hangs under: the ceiling, or the back wall for a wall light)
     g = n // 8
-    o[k:k + g, 1] = np.float32(2.0) - margin * rng.uniform(1.0, 30.0, g).astype(np.float32)
+    near = planes[np.argmin([(p[3] - light_pts @ p[:3]).min() for p in planes])]
+    dist = margin * rng.uniform(1.0, 30.0, g).astype(np.float32)
+    og = o[k:k + g].astype(np.float64)
+    o[k:k + g] = (og - ((og @ near[:3] - near[3]) + dist)[:, None] * near[:3]).astype(np.float32)
     # the kernel's selection: inside every culled plane by the margin (float32)
     inside = np.ones(n, bool)
     for p in planes.astype(np.float32):
@@ -167,6 +179,23 @@ def test_culled_triangles_never_occlude(mrt_mod, fma):
         tt, hit = _tri_t(o, d, v0[None], (Pv[t, 1] - v0)[None], (Pv[t, 2] - v0)[None], fma)
         bad = hit & (tt >= 0) & (tt <= tT)
         assert not bad.any(), (t, o[bad][:3], d[bad][:3], tt[bad][:3], tT[bad][:3])
+    return int(culled.sum())
+
+
+@pytest.mark.parametrize("fma", [False, True, "rcp"])
+def test_culled_triangles_never_occlude(mrt_mod, fma):
+    assert _check_culled(mrt_mod, "cornellbox", fma) == 14
+
+
+@pytest.mark.parametrize("fma", [False, True, "rcp"])
+@pytest.mark.parametrize("name", sorted(roomgen.CASES))
+def test_culled_triangles_never_occlude_in_generated_rooms(mrt_mod, tmp_path, name, fma):
+    """The same on every generated room (tests/roomgen.py): block bottoms on
+    the floor's plane, a block's side on the left wall's plane (wall), two
+    lights, and a light 0.01 in front of the back wall (walllight: the
+    grazing origins are then placed along the back wall)."""
+    rm = roomgen.room(name, roomgen.seeds(name)[0], tmp_path)
+    assert _check_culled(mrt_mod, rm.path, fma) >= 10
 
 
 def _sliver_room(path):

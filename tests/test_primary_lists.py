@@ -9,6 +9,9 @@ import subprocess
 
 import pytest
 
+import roomgen
+from camera_cases import camera_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "metal-renderer_amd", "csrc")
 SCENES = os.path.join(ROOT, "metal-renderer_amd", "scenes")
@@ -45,6 +48,23 @@ def test_lists_are_conservative(checker, scene, W, H, jitters, cap, fast):
     assert words[0] == "violations" and words[1] == "0", out.stdout
     listed = int(words[words.index("listed") + 1])
     assert listed > 0, out.stdout
+
+
+@pytest.mark.parametrize("fast", [0, 1])
+@pytest.mark.parametrize("moved", [False, True], ids=["default-camera", "camera-inside"])
+@pytest.mark.parametrize("name", ["plain-3", "skew", "stacked", "crossing"])
+def test_lists_are_conservative_in_generated_rooms(checker, mrt_mod, tmp_path, name, moved, fast):
+    """The same on generated rooms (tests/roomgen.py) at 97 x 61, 8 jitters,
+    cap 12: the reference camera, and a pinhole camera inside the room whose
+    camera plane cuts triangles."""
+    rm = roomgen.room(name, roomgen.seeds(name)[0], tmp_path)
+    cam = camera_args(mrt_mod.Camera.look_at((0.0, 1.5, 0.3), (0.0, 0.3, -0.5), (0.0, 1.0, 0.0), 100.0)) if moved else []
+    out = subprocess.run([checker, rm.path, "97", "61", "8", "0", "12", str(fast)] + cam, capture_output=True, text=True)
+    print(rm.id, out.stdout.strip())
+    assert out.returncode == 0, out.stdout + out.stderr
+    words = out.stdout.split()
+    assert words[0] == "violations" and words[1] == "0", out.stdout
+    assert int(words[words.index("listed") + 1]) > 0, out.stdout
 
 
 def test_lists_skip_dense_scenes(checker):
