@@ -237,6 +237,60 @@ int mrt_camera_check(const mrt_camera* cam);
 int mrt_raygen_camera(const mrt_scene* scene, const mrt_camera* cam, uint32_t width, uint32_t height,
                       const float* noise, void* rays, uint32_t flags, void* stream);
 
+/* ---- denoised output -------------------------------------------------------
+ * First-hit guide buffers and an edge-avoiding A-Trous filter driven by them
+ * (Dammertz, Sewtz, Hanika, Lensch, HPG 2010; DESIGN.md "Denoised output").
+ * Not in the reference, which only ever shows the accumulation image.
+ *
+ * mrt_guides: one guide ray per pixel over the whole W x H frame (index
+ * y * W + x, row 0 at the bottom) — the pixel's camera ray at the pixel centre
+ * (the jitter sample (0.5, 0.5)) through a pinhole: a camera with
+ * lens_radius > 0 is used as if its lens were absent; NULL = mrt_camera_default.
+ * Traced with tmin 0 and no tmax.  Two float4 planes (device, W*H*4 floats each):
+ *   guide_n[p] = (shading normal, bits(word)), guide_p[p] = (hit position, t)
+ * with position, normal and material index as mrt_shade computes them; word is
+ * the material index, bit 31 set when the hit is a light triangle; a miss
+ * writes (0, 0, 0, bits(0xFFFFFFFF)) and (0, 0, 0, -1).  A pixel is FILTERABLE
+ * iff word < 0x80000000.  flags: MRT_FLAG_PRECISE.
+ * On a scene whose tree needs more than 64 traversal-stack entries (see
+ * mrt_scene_info.bvh_max_stack) mrt_guides and mrt_intersect keep the deeper
+ * entries in one buffer of the scene: such calls on one scene must not run
+ * concurrently on different streams.  A renderer's own guide pass
+ * (mrt_renderer_denoise) uses a buffer of the renderer's. */
+int mrt_guides(const mrt_scene* scene, const mrt_camera* cam /* NULL = default */, uint32_t width, uint32_t height,
+               float* guide_n, float* guide_p /* W*H*4 floats each, device */, uint32_t flags, void* stream);
+
+/* The filter.  k = (1/16, 1/4, 3/8, 1/4, 1/16), c^0 = the image's rgb; for
+ * iteration i = 0 .. iterations-1 the step is s = 2^i.  A pixel p that is not
+ * filterable keeps its value.  Otherwise, over (dx, dy) in {-2..2}^2 with
+ * q = p + s (dx, dy), a tap counts only if q is inside the image, q is
+ * filterable, word_q == word_p and every component of c^i_q is finite; its
+ * weight is the product of
+ *   k[dx+2] k[dy+2],
+ *   D^(2^e) with D = max(0, n_p.n_q) and e = normal_log2_power,
+ *   exp(-|n_p.(x_q - x_p)| / (sigma_plane t_p)),
+ *   exp(-|c^i_q - c^i_p|^2 / sigma_color^2)   (1 if sigma_color == 0 or c^i_p is not finite)
+ * and c^(i+1)_p = sum w c^i_q / sum w (c^i_p if the sum is 0: a non-finite
+ * centre without a usable neighbour; one with usable neighbours is repaired,
+ * and never spreads).  Alpha is copied; iterations = 0 copies the image. */
+typedef struct mrt_denoise_params {
+  uint32_t iterations;         /* 0..8 */
+  float sigma_color;           /* >= 0; 0 = no colour term */
+  float sigma_plane;           /* > 0 */
+  uint32_t normal_log2_power;  /* e, 0..8 */
+} mrt_denoise_params;
+/* Host only.  iterations = 3 (frames <= 2), 2 (frames <= 16), else 1;
+ * sigma_color = 2 / sqrt(max(frames, 1)); sigma_plane = 0.01; normal_log2_power = 6. */
+int mrt_denoise_params_default(uint64_t frames, mrt_denoise_params* out);
+/* Host only.  MRT_ERR_INVALID (with a message) for a field outside the ranges
+ * above, a non-finite one included. */
+int mrt_denoise_params_check(const mrt_denoise_params* p);
+/* Device pointers, W*H*4 floats each.  The iterations ping-pong between `out`
+ * and `scratch` so that the last one writes `out`; `image` is only read.  Any
+ * aliasing among image, out and scratch, and params == NULL, is MRT_ERR_INVALID. */
+int mrt_denoise(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
+                uint32_t width, uint32_t height, const mrt_denoise_params* params, void* stream);
+
 /* ---- renderer (B-1) ------------------------------------------------------ */
 typedef struct mrt_renderer_desc {
   const mrt_scene* scene;          /* not owned; must outlive the renderer */
@@ -337,6 +391,25 @@ int mrt_renderer_read_image(mrt_renderer* r, float* rgba, size_t count);
 int mrt_renderer_set_max_frames(mrt_renderer* r, uint32_t max_frames);
 /* Save the image top-down as .pfm (float RGB) or .exr (float RGBA, uncompressed). */
 int mrt_renderer_save_image(mrt_renderer* r, const char* path);
+/* Denoise the accumulation image into a buffer the renderer owns; the image
+ * itself is never written.  Enqueued on the renderer's stream after the draws
+ * queued so far, without a host wait (draw; denoise; display_enqueue(slot |
+ * MRT_DISPLAY_DENOISED); map).  params NULL = mrt_denoise_params_default for
+ * the frames accumulated.  The guide planes are computed on the same stream
+ * at the first denoise after create, resize or set_camera, with the camera in
+ * force and the renderer's precise or fast build, and kept until the next
+ * such call.  The buffers (guides 32 B, denoised 16 B, scratch 16 B per pixel)
+ * are allocated at the first denoise and re-made by resize: a renderer that
+ * never denoises allocates nothing.  MRT_ERR_STATE when no frame has been
+ * accumulated since create, resize, reset or set_camera.  A sharded renderer
+ * filters whatever its image holds, which is the whole frame only on rank 0
+ * after an exchange. */
+int mrt_renderer_denoise(mrt_renderer* r, const mrt_denoise_params* params);
+/* The denoised buffer, as read_image / save_image give the image (read
+ * synchronises).  MRT_ERR_STATE when no denoise has run at the renderer's
+ * current size. */
+int mrt_renderer_read_denoised(mrt_renderer* r, float* rgba, size_t count);
+int mrt_renderer_save_denoised(mrt_renderer* r, const char* path);   /* .pfm / .exr */
 int mrt_renderer_stats(const mrt_renderer* r, mrt_stats* stats);
 int mrt_renderer_destroy(mrt_renderer* r);
 
@@ -359,6 +432,8 @@ int mrt_shard_mask(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_
  * RGBA32F in and out; `reference` may be NULL when no compare mode is set. */
 #define MRT_DISPLAY_TONEMAP 1u
 #define MRT_DISPLAY_SRGB 2u
+#define MRT_DISPLAY_DENOISED 4u   /* mrt_renderer_display / _display_enqueue: blit the denoised buffer instead of the
+                                     image (MRT_ERR_STATE without a denoise at the current size); mrt_display ignores it */
 #define MRT_DISPLAY_COMPARE(mode) ((uint32_t)(mode) << 8)   /* 1 abs, 2 ref-to-color, 3 color-to-ref, 4 luminance */
 int mrt_display(const float* image, const float* reference, float* out, uint32_t width, uint32_t height,
                 uint32_t flags, float compare_scale, void* stream);
@@ -510,6 +585,17 @@ int mrt_debug_box_margin(const mrt_scene* scene, const void* rays, uint32_t stri
  * division by a launch divisor (kernels.h magic_div: the multiplier the
  * renderer passes, applied as the kernels' mulhi + shift), n[i] < 2^31. */
 int mrt_debug_magic_div(uint32_t d, const uint32_t* n, uint32_t count, uint32_t* q);
+/* Test / measurement entry: the implementation mrt_denoise uses for an
+ * iteration, process-wide — 0: the shipped choice per step; 1: every tap from
+ * global memory; 2: tile and halo staged in LDS at every step it supports
+ * (s <= 4; the direct one above).  The results agree to rounding. */
+int mrt_debug_denoise_path(uint32_t path);
+/* Measurement entry (tools/denoise_time.py): ONE iteration of mrt_denoise at
+ * step 2^step_log2 (<= 14) with implementation `path` (as above), image ->
+ * out; params->iterations is not used.  Touches no process-wide state. */
+int mrt_debug_denoise_step(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
+                           uint32_t width, uint32_t height, const mrt_denoise_params* params, uint32_t step_log2,
+                           uint32_t path, void* stream);
 /* Number of HIP devices visible (0 when none; never fails). */
 int mrt_device_count(void);
 

@@ -28,6 +28,11 @@
  *                   [--gpus N] [--device D] [--exchange rccl|host]
  *                   [--eye x,y,z] [--target x,y,z] [--up x,y,z] [--fov DEGREES]
  *                   [--aperture LENS_RADIUS] [--focus DISTANCE]
+ *                   [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]
+ * --denoise: after the last draw (and the exchange: only rank 0, which holds
+ * the whole image, denoises) mrt_renderer_denoise with the defaults for --spp
+ * frames, and --out receives the denoised image (mrt_renderer_save_denoised);
+ * the two other options override a default and imply --denoise.
  * The camera options go through mrt_camera_look_at / mrt_renderer_set_camera
  * (fov: full horizontal angle; --aperture > 0: a thin lens, focused at --focus
  * or else on the target); without any of them the reference's camera renders.
@@ -58,6 +63,10 @@ typedef struct {
   /* camera (mrt_camera_look_at): set_camera is called when any of these is given */
   int camera_set, pose_set, focus_set;   /* pose_set: --eye, --target, --up or --fov */
   float eye[3], target[3], up[3], fov, aperture, focus;
+  /* denoised output (mrt_renderer_denoise) */
+  int denoise, denoise_iterations_set, denoise_sigma_set;
+  uint32_t denoise_iterations;
+  float denoise_sigma_color;
 } options;
 
 /* "x,y,z" -> three floats */
@@ -78,7 +87,8 @@ static void usage(void) {
           "                  [--static-noise] [--no-accumulate] [--debug-material]\n"
           "                  [--gpus N] [--device D] [--exchange rccl|host]\n"
           "                  [--eye x,y,z] [--target x,y,z] [--up x,y,z] [--fov DEGREES]\n"
-          "                  [--aperture LENS_RADIUS] [--focus DISTANCE]\n");
+          "                  [--aperture LENS_RADIUS] [--focus DISTANCE]\n"
+          "                  [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]\n");
 }
 
 /* --scene cornellbox -> <dir of this executable>/../scenes/cornellbox.obj */
@@ -125,6 +135,9 @@ static int parse(int argc, char** argv, options* o) {
     else if (VAL("--fov")) { o->fov = strtof(v, NULL); o->camera_set = o->pose_set = 1; }
     else if (VAL("--aperture")) { o->aperture = strtof(v, NULL); o->camera_set = 1; }
     else if (VAL("--focus")) { o->focus = strtof(v, NULL); o->camera_set = o->focus_set = 1; }
+    else if (VAL("--denoise-iterations")) { o->denoise_iterations = (uint32_t)strtoul(v, NULL, 0); o->denoise = o->denoise_iterations_set = 1; }
+    else if (VAL("--denoise-sigma-color")) { o->denoise_sigma_color = strtof(v, NULL); o->denoise = o->denoise_sigma_set = 1; }
+    else if (strcmp(a, "--denoise") == 0) o->denoise = 1;
     else if (strcmp(a, "--precise") == 0) o->flags |= MRT_FLAG_PRECISE;
     else if (strcmp(a, "--static-noise") == 0) o->flags |= MRT_FLAG_STATIC_NOISE;
     else if (strcmp(a, "--no-accumulate") == 0) o->flags |= MRT_FLAG_NO_ACCUMULATE;
@@ -265,7 +278,16 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
   mrt_stats st;
   if (mrt_renderer_stats(r, &st)) return die("mrt_renderer_stats");
   if (rank == 0) {
-    if (mrt_renderer_save_image(r, o->out)) return die("mrt_renderer_save_image");
+    if (o->denoise) {
+      mrt_denoise_params dp;
+      if (mrt_denoise_params_default(st.frame_index, &dp)) return die("mrt_denoise_params_default");
+      if (o->denoise_iterations_set) dp.iterations = o->denoise_iterations;
+      if (o->denoise_sigma_set) dp.sigma_color = o->denoise_sigma_color;
+      if (mrt_renderer_denoise(r, &dp)) return die("mrt_renderer_denoise");
+      if (mrt_renderer_save_denoised(r, o->out)) return die("mrt_renderer_save_denoised");
+    } else if (mrt_renderer_save_image(r, o->out)) {
+      return die("mrt_renderer_save_image");
+    }
     const double s = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
     const double paths = (double)o->width * o->height * o->spp;
     printf("{\"out\": \"%s\", \"width\": %u, \"height\": %u, \"spp\": %u, \"max_path_length\": %u, \"gpus\": %u, "

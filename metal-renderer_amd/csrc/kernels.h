@@ -177,6 +177,10 @@ constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_sha
   /* spill: >= (max_stack - 32) * kIntersectSpillGrid * 256 uint32 when sc.max_stack > kMaxStack */       \
   hipError_t launch_intersect(const DeviceScene& sc, const void* rays, uint32_t stride, uint32_t count,   \
                               RefIntersection* out, uint32_t* spill, hipStream_t s);                      \
+  /* first-hit guide planes of the denoiser (W*H float4 each); cam: host pointer with lens_radius 0,     \
+     null = the reference's camera; spill as launch_intersect */                                          \
+  hipError_t launch_guides(const DeviceScene& sc, uint32_t W, uint32_t H, const CameraBlock* cam,         \
+                           float* guide_n, float* guide_p, uint32_t* spill, hipStream_t s);               \
   hipError_t launch_shade(const DeviceScene& sc, uint32_t W, uint32_t H, uint32_t frame_index,            \
                           uint32_t max_path_length, const float* noise, const RefIntersection* isect,     \
                           RefRay* rays, RefShadowRay* srays, uint32_t flags, hipStream_t s);              \

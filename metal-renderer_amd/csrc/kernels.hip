@@ -2439,6 +2439,43 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DeviceScene sc, const
   }
 }
 
+// First-hit guide buffers of the denoiser (denoise.hip), one pixel per lane
+// over the whole frame (index y * W + x, row 0 at the bottom, whatever the
+// sharding).  The guide ray is the pixel's camera ray at the pixel centre
+// (jitter sample (0.5, 0.5): both jitter terms are exactly 0) through a
+// pinhole (the host passes the camera block with lens_radius = 0), traced with
+// tmin 0 and no tmax.  gn[p] = (hn, bits(word)), gp[p] = (hv, t), with hv, hn
+// and the material index as shade_hit computes them; word = the material
+// index, bit 31 set on a light triangle; a miss writes (0, 0, 0, ~0u) and
+// (0, 0, 0, -1).  A pixel is filterable iff word < 0x80000000.
+template <int STACK>
+__global__ __launch_bounds__(kBlock) void guide_kernel(DeviceScene sc, uint32_t W, uint32_t H, CameraBlock cam,
+                                                       uint32_t moved, float4* gn, float4* gp, uint32_t* spill) {
+  const LdsCtx cx = stage_lds<kGlobal>(sc, 0, spill);
+  const uint32_t count = W * H;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) {
+    const uint32_t x = i % W, y = i / W;
+    V3 o, d;
+    camera_ray<true>(x, y, W, H, make_float4(0.5f, 0.5f, 0.5f, 0.5f), nullptr, moved ? &cam : nullptr, o, d);
+    const Hit h = trace_nearest<STACK, kGlobal>(sc, cx, o, d, 0.0f, __builtin_inff());
+    float4 n = make_float4(0.0f, 0.0f, 0.0f, bitsf(0xFFFFFFFFu)), p = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    if (h.found) {
+      const float wu = h.u, wv = h.v, ww = (1.0f - h.u) - h.v;   // shade_hit's interpolation
+      const float4 P0 = fetch_prim<kGlobal>(sc, cx, h.prim, 0), P1 = fetch_prim<kGlobal>(sc, cx, h.prim, 1);
+      const float4 P2 = fetch_prim<kGlobal>(sc, cx, h.prim, 2);
+      const float4 N0 = fetch_prim<kGlobal>(sc, cx, h.prim, 3), N1 = fetch_prim<kGlobal>(sc, cx, h.prim, 4);
+      const float4 N2 = fetch_prim<kGlobal>(sc, cx, h.prim, 5);
+      const V3 hv = add(add(mul(mk(P0), wu), mul(mk(P1), wv)), mul(mk(P2), ww));
+      const V3 hn = normalize(add(add(mul(mk(N0), wu), mul(mk(N1), wv)), mul(mk(N2), ww)));
+      const uint32_t word = fbits(P0.w) | (fbits(P1.w) != 0xFFFFFFFFu ? 0x80000000u : 0u);
+      n = make_float4(hn.x, hn.y, hn.z, bitsf(word));
+      p = make_float4(hv.x, hv.y, hv.z, h.t);
+    }
+    gn[i] = n;
+    gp[i] = p;
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void shade_kernel(DeviceScene sc, uint32_t W, uint32_t H, uint32_t f,
                                                        uint32_t L, const float4* noise,
                                                        const RefIntersection* isect, RefRay* rays,
@@ -2748,6 +2785,25 @@ hipError_t launch_intersect(const DeviceScene& sc, const void* rays, uint32_t st
     const size_t lds = (size_t)32 * kBlock * 4;
     const dim3 g(std::min<uint32_t>(blocks_for(count), kIntersectSpillGrid));
     intersect_kernel<-32><<<g, dim3(kBlock), lds, s>>>(sc, r, stride, count, out, spill);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_guides(const DeviceScene& sc, uint32_t W, uint32_t H, const CameraBlock* cam, float* guide_n,
+                         float* guide_p, uint32_t* spill, hipStream_t s) {
+  if (sc.width != 4 || (cam && cam->lens_radius != 0.0f)) return hipErrorInvalidValue;
+  float4* gn = reinterpret_cast<float4*>(guide_n);
+  float4* gp = reinterpret_cast<float4*>(guide_p);
+  const CameraBlock cb = cam ? *cam : CameraBlock{};
+  const uint32_t moved = cam ? 1u : 0u, count = W * H;
+  if (sc.max_stack <= (uint32_t)kMaxStack) {   // as launch_intersect: whole stack in LDS
+    const size_t lds = (size_t)kMaxStack * kBlock * 4;
+    guide_kernel<kMaxStack><<<dim3(blocks_for(count)), dim3(kBlock), lds, s>>>(sc, W, H, cb, moved, gn, gp, nullptr);
+  } else {                                      // 32 LDS entries + global spill, persistent grid
+    if (!spill) return hipErrorInvalidValue;
+    const size_t lds = (size_t)32 * kBlock * 4;
+    const dim3 g(std::min<uint32_t>(blocks_for(count), kIntersectSpillGrid));
+    guide_kernel<-32><<<g, dim3(kBlock), lds, s>>>(sc, W, H, cb, moved, gn, gp, spill);
   }
   return hipGetLastError();
 }

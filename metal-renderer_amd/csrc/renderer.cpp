@@ -14,6 +14,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -28,6 +29,7 @@
 #include "../../include/mrt.h"
 #include "bvh.h"
 #include "bvh_gpu.h"
+#include "denoise.h"
 #include "image.h"
 #include "kernels.h"
 #include "noise.h"
@@ -68,11 +70,13 @@ struct DevBuf {
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-// traversal-stack spill of the stage intersect kernel (trees deeper than its
-// kMaxStack-entry LDS stack): (need - 32) entries x its persistent grid
+// traversal-stack spill of the stage intersect and guide kernels (trees deeper
+// than their kMaxStack-entry LDS stack): one row of max_stack words per lane of
+// their persistent grid — the row stride the kernels address it with
+// (kernels.hip LdsCtx::spill_lane; a lane uses the first max_stack - 32 words)
 hipError_t alloc_isect_spill(DevBuf& b, uint32_t max_stack) {
   if (max_stack <= (uint32_t)mrt::kMaxStack) return b.alloc(0);
-  return b.alloc((size_t)(max_stack - 32) * mrt::kIntersectSpillGrid * 256 * 4);
+  return b.alloc((size_t)max_stack * mrt::kIntersectSpillGrid * 256 * 4);
 }
 
 #define NCCL_TRY(expr)                                                                            \
@@ -296,6 +300,12 @@ struct mrt_renderer {
   CameraGen* cam_cur = nullptr;
   Exchange x;
   DevBuf reference, display;   // comparison image (mrt_renderer_load_reference) and blit output
+  // denoised output (mrt_renderer_denoise): allocated at the first denoise,
+  // re-made by resize.  The guide planes belong to a size and a camera.
+  DevBuf guide_n, guide_p, denoised, denoise_scratch;
+  DevBuf guide_spill;              // the guide pass's own traversal-stack spill (deep trees; first denoise)
+  bool guides_current = false;     // the planes hold the camera in force at the current size
+  bool denoised_current = false;   // a denoise has run at the current size
   struct DisplaySlot {          // mrt_renderer_display_enqueue / _map: pinned copies of the blit
     float* host = nullptr;
     size_t floats = 0;
@@ -802,6 +812,7 @@ int mrt_shard_mask(uint32_t W, uint32_t H, uint32_t rank, uint32_t count, uint8_
 int mrt_display(const float* image, const float* reference, float* out, uint32_t W, uint32_t H, uint32_t flags,
                 float compare_scale, void* stream) {
   const uint32_t mode = (flags >> 8) & 0xFFu;
+  flags &= ~MRT_DISPLAY_DENOISED;   // a renderer-level choice of the source (mrt_renderer_display)
   if (!image || !out || W == 0 || H == 0 || mode > 4 || (mode && !reference) || (flags & ~0xFF03u))
     return fail(MRT_ERR_INVALID, "mrt_display: bad argument");
   HIP_TRY(mrt::fast::launch_display(reinterpret_cast<const float4*>(image), reinterpret_cast<const float4*>(reference),
@@ -1689,6 +1700,128 @@ int mrt_raygen_camera(const mrt_scene* scene, const mrt_camera* cam, uint32_t W,
   return MRT_OK;
 }
 
+// ---- denoised output (include/mrt.h) ---------------------------------------
+namespace {
+// mrt_guides with the caller's stack spill (a renderer's own, so that its guide
+// pass shares nothing with the stage calls on the scene or another renderer)
+int guides_with_spill(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, float* guide_n,
+                      float* guide_p, uint32_t flags, uint32_t* spill, void* stream) {
+  if (!scene || !guide_n || !guide_p || guide_n == guide_p || W < 2 || H < 2 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_guides: bad argument");
+  mrt_camera c;
+  if (cam) {
+    const int rc = mrt_camera_check(cam);
+    if (rc) return rc;
+    c = *cam;
+  } else {
+    (void)mrt_camera_default(&c);
+  }
+  c.lens_radius = 0.0f;   // the guide ray goes through the pinhole
+  c.focus_distance = 0.0f;
+  mrt_camera d;
+  (void)mrt_camera_default(&d);
+  d.focus_distance = 0.0f;
+  const bool moved = std::memcmp(&c, &d, sizeof(mrt_camera)) != 0;
+  const mrt::CameraBlock cb = camera_block(c);
+  STAGE_CALL(launch_guides(scene->dev, W, H, moved ? &cb : nullptr, guide_n, guide_p, spill, (hipStream_t)stream));
+  return MRT_OK;
+}
+}  // namespace
+
+int mrt_guides(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, float* guide_n, float* guide_p,
+               uint32_t flags, void* stream) {
+  return guides_with_spill(scene, cam, W, H, guide_n, guide_p, flags,
+                           scene ? scene->isect_spill.as<uint32_t>() : nullptr, stream);
+}
+
+int mrt_denoise_params_default(uint64_t frames, mrt_denoise_params* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_denoise_params_default: null params");
+  out->iterations = frames <= 2 ? 3u : (frames <= 16 ? 2u : 1u);
+  out->sigma_color = (float)(2.0 / std::sqrt((double)std::max<uint64_t>(frames, 1)));
+  out->sigma_plane = 0.01f;
+  out->normal_log2_power = 6;
+  return MRT_OK;
+}
+
+int mrt_denoise_params_check(const mrt_denoise_params* p) {
+  if (!p) return fail(MRT_ERR_INVALID, "denoise params: null");
+  if (p->iterations > 8) return fail(MRT_ERR_INVALID, "denoise params: iterations must be at most 8");
+  if (!std::isfinite(p->sigma_color) || p->sigma_color < 0.0f)
+    return fail(MRT_ERR_INVALID, "denoise params: sigma_color must be finite and not negative");
+  if (!std::isfinite(p->sigma_plane) || !(p->sigma_plane > 0.0f))
+    return fail(MRT_ERR_INVALID, "denoise params: sigma_plane must be finite and positive");
+  if (p->normal_log2_power > 8) return fail(MRT_ERR_INVALID, "denoise params: normal_log2_power must be at most 8");
+  return MRT_OK;
+}
+
+namespace {
+std::atomic<uint32_t> g_denoise_path{mrt::kAtrousAuto};
+
+// `iterations` iterations from step 2^first_log2 on, with implementation `path`
+int denoise_run(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
+                uint32_t W, uint32_t H, const mrt_denoise_params* params, uint32_t iterations, uint32_t first_log2,
+                uint32_t path, void* stream) {
+  if (!image || !guide_n || !guide_p || !out || !scratch || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_denoise: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  auto overlap = [bytes](const void* a, const void* b) {
+    const char* p = (const char*)a;
+    const char* q = (const char*)b;
+    return p < q + bytes && q < p + bytes;
+  };
+  if (overlap(image, out) || overlap(image, scratch) || overlap(out, scratch))
+    return fail(MRT_ERR_INVALID, "mrt_denoise: image, out and scratch must not overlap");
+  if (overlap(guide_n, out) || overlap(guide_n, scratch) || overlap(guide_p, out) || overlap(guide_p, scratch))
+    return fail(MRT_ERR_INVALID, "mrt_denoise: the guide planes must not overlap out or scratch");
+  const int rc = mrt_denoise_params_check(params);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t N = iterations;
+  if (N == 0) {
+    HIP_TRY(hipMemcpyAsync(out, image, bytes, hipMemcpyDeviceToDevice, s));
+    return MRT_OK;
+  }
+  mrt::AtrousArgs a{};
+  a.guide_n = reinterpret_cast<const float4*>(guide_n);
+  a.guide_p = reinterpret_cast<const float4*>(guide_p);
+  a.width = W;
+  a.height = H;
+  a.inv_sigma_c2 = params->sigma_color > 0.0f ? (float)(1.0 / ((double)params->sigma_color * params->sigma_color)) : 0.0f;
+  a.sigma_plane = params->sigma_plane;
+  a.normal_log2_power = params->normal_log2_power;
+  const float* src = image;
+  for (uint32_t i = 0; i < N; ++i) {
+    float* dst = ((N - 1 - i) & 1u) ? scratch : out;   // the last iteration writes `out`
+    a.image = reinterpret_cast<const float4*>(src);
+    a.out = reinterpret_cast<float4*>(dst);
+    a.step = 1u << (i + first_log2);
+    HIP_TRY(mrt::launch_atrous(a, path, s));
+    src = dst;
+  }
+  return MRT_OK;
+}
+}  // namespace
+
+int mrt_debug_denoise_path(uint32_t path) {
+  if (path > mrt::kAtrousStaged) return fail(MRT_ERR_INVALID, "mrt_debug_denoise_path: 0, 1 or 2");
+  g_denoise_path.store(path);
+  return MRT_OK;
+}
+
+int mrt_denoise(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
+                uint32_t W, uint32_t H, const mrt_denoise_params* params, void* stream) {
+  return denoise_run(image, guide_n, guide_p, out, scratch, W, H, params, params ? params->iterations : 0u, 0u,
+                     g_denoise_path.load(), stream);
+}
+
+int mrt_debug_denoise_step(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
+                           uint32_t W, uint32_t H, const mrt_denoise_params* params, uint32_t step_log2, uint32_t path,
+                           void* stream) {
+  if (step_log2 > 14 || path > mrt::kAtrousStaged)
+    return fail(MRT_ERR_INVALID, "mrt_debug_denoise_step: step at most 2^14, path 0, 1 or 2");
+  return denoise_run(image, guide_n, guide_p, out, scratch, W, H, params, 1u, step_log2, path, stream);
+}
+
 int mrt_intersect(const mrt_scene* scene, const void* rays, uint32_t stride, uint32_t count, void* isect,
                   uint32_t flags, void* stream) {
   if (!scene || (!rays && count) || (!isect && count) || stride < 32 || (stride % 4))
@@ -1865,6 +1998,14 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   r->desc.width = width;
   r->desc.height = height;
   r->x.slab_floats = 0;    // the exchange buffers are re-sized for the new image at the next exchange
+  r->guides_current = r->denoised_current = false;
+  if (r->denoised.p) {     // a renderer that has denoised keeps its buffers, at the new size
+    const size_t bytes = (size_t)width * height * 16;
+    HIP_TRY(r->guide_n.alloc(bytes));
+    HIP_TRY(r->guide_p.alloc(bytes));
+    HIP_TRY(r->denoised.alloc(bytes));
+    HIP_TRY(r->denoise_scratch.alloc(bytes));
+  }
   return alloc_frame_buffers(r);
 }
 
@@ -1901,6 +2042,7 @@ int mrt_renderer_set_camera(mrt_renderer* r, const mrt_camera* cam) {
     r->camera_moved = old_moved;
     return rc;
   }
+  r->guides_current = false;   // the guide planes were traced with the previous camera
   return mrt_renderer_reset(r);
 }
 
@@ -2184,17 +2326,78 @@ int mrt_renderer_read_image(mrt_renderer* r, float* rgba, size_t count) {
   return MRT_OK;
 }
 
+namespace {
+int save_rgba(const char* path, const std::vector<float>& img, uint32_t W, uint32_t H) {
+  const std::string p(path);
+  auto ends = [&](const char* s) { const size_t n = std::strlen(s); return p.size() >= n && p.compare(p.size() - n, n, s) == 0; };
+  if (ends(".pfm")) return write_pfm(path, img, W, H);
+  if (ends(".exr")) return write_exr(path, img, W, H);
+  return fail(MRT_ERR_INVALID, "unsupported image extension (use .pfm or .exr)");
+}
+}  // namespace
+
 int mrt_renderer_save_image(mrt_renderer* r, const char* path) {
   if (!r || !path) return fail(MRT_ERR_INVALID, "null argument");
   const uint32_t W = r->desc.width, H = r->desc.height;
   std::vector<float> img((size_t)W * H * 4);
   int rc = mrt_renderer_read_image(r, img.data(), img.size());
   if (rc) return rc;
-  const std::string p(path);
-  auto ends = [&](const char* s) { const size_t n = std::strlen(s); return p.size() >= n && p.compare(p.size() - n, n, s) == 0; };
-  if (ends(".pfm")) return write_pfm(path, img, W, H);
-  if (ends(".exr")) return write_exr(path, img, W, H);
-  return fail(MRT_ERR_INVALID, "unsupported image extension (use .pfm or .exr)");
+  return save_rgba(path, img, W, H);
+}
+
+int mrt_renderer_denoise(mrt_renderer* r, const mrt_denoise_params* params) {
+  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
+  if (r->frame_index == 0)
+    return fail(MRT_ERR_STATE, "mrt_renderer_denoise: no frame accumulated since create, resize, reset or set_camera");
+  mrt_denoise_params p;
+  if (params) p = *params;
+  else (void)mrt_denoise_params_default(r->frame_index, &p);
+  int rc = mrt_denoise_params_check(&p);
+  if (rc) return rc;
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  const size_t bytes = (size_t)W * H * 16;
+  HIP_TRY(hipSetDevice(r->scene->device));
+  if (r->denoised.bytes != bytes || !r->denoised.p) {   // first denoise (resize re-makes existing buffers)
+    r->guides_current = r->denoised_current = false;
+    HIP_TRY(r->guide_n.alloc(bytes));
+    HIP_TRY(r->guide_p.alloc(bytes));
+    HIP_TRY(r->denoised.alloc(bytes));
+    HIP_TRY(r->denoise_scratch.alloc(bytes));
+  }
+  rc = exchange_flush(r);   // a deferred (overlapped) exchange lands in the image first
+  if (rc) return rc;
+  if (!r->guides_current) {
+    if (!r->guide_spill.p) HIP_TRY(alloc_isect_spill(r->guide_spill, r->scene->dev.max_stack));
+    rc = guides_with_spill(r->scene, &r->camera, W, H, r->guide_n.as<float>(), r->guide_p.as<float>(),
+                           r->desc.flags & MRT_FLAG_PRECISE, r->guide_spill.as<uint32_t>(), r->stream);
+    if (rc) return rc;
+    r->guides_current = true;
+  }
+  rc = mrt_denoise(r->image, r->guide_n.as<float>(), r->guide_p.as<float>(), r->denoised.as<float>(),
+                   r->denoise_scratch.as<float>(), W, H, &p, r->stream);
+  if (rc) return rc;
+  r->denoised_current = true;
+  return MRT_OK;
+}
+
+int mrt_renderer_read_denoised(mrt_renderer* r, float* rgba, size_t count) {
+  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
+  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
+  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
+  if (!r->denoised_current) return fail(MRT_ERR_STATE, "no denoise has run at the renderer's current size");
+  const int rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(rgba, r->denoised.p, need * 4, hipMemcpyDeviceToHost));
+  return MRT_OK;
+}
+
+int mrt_renderer_save_denoised(mrt_renderer* r, const char* path) {
+  if (!r || !path) return fail(MRT_ERR_INVALID, "null argument");
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  std::vector<float> img((size_t)W * H * 4);
+  const int rc = mrt_renderer_read_denoised(r, img.data(), img.size());
+  if (rc) return rc;
+  return save_rgba(path, img, W, H);
 }
 
 int mrt_image_load_exr(const char* path, float* rgba, size_t capacity, uint32_t* width, uint32_t* height) {
@@ -2231,10 +2434,12 @@ int mrt_renderer_display(mrt_renderer* r, uint32_t flags, float compare_scale, f
   const size_t need = (size_t)r->desc.width * r->desc.height * 4;
   if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
   if (((flags >> 8) & 0xFFu) && !r->reference.p) return fail(MRT_ERR_STATE, "compare mode without a loaded reference");
+  const bool denoised = (flags & MRT_DISPLAY_DENOISED) != 0;
+  if (denoised && !r->denoised_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_DENOISED without a denoise at the current size");
   int rc = exchange_flush(r);
   if (rc) return rc;
   if (r->display.bytes < need * 4) HIP_TRY(r->display.alloc(need * 4));
-  rc = mrt_display(r->image, r->reference.as<float>(), r->display.as<float>(), r->desc.width, r->desc.height, flags,
+  rc = mrt_display(denoised ? r->denoised.as<float>() : r->image, r->reference.as<float>(), r->display.as<float>(), r->desc.width, r->desc.height, flags,
                    compare_scale, r->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(rgba, r->display.p, need * 4, hipMemcpyDeviceToHost, r->stream));
@@ -2246,6 +2451,8 @@ int mrt_renderer_display_enqueue(mrt_renderer* r, uint32_t flags, float compare_
   if (slot >= MRT_DISPLAY_SLOTS) return fail(MRT_ERR_INVALID, "display slot >= MRT_DISPLAY_SLOTS");
   if (((flags >> 8) & 0xFFu) && !r->reference.p) return fail(MRT_ERR_STATE, "compare mode without a loaded reference");
   const size_t need = (size_t)r->desc.width * r->desc.height * 4;
+  const bool denoised = (flags & MRT_DISPLAY_DENOISED) != 0;
+  if (denoised && !r->denoised_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_DENOISED without a denoise at the current size");
   auto& ds = r->shown[slot];
   if (ds.queued) HIP_TRY(hipEventSynchronize(ds.done));   // its previous copy may still be landing
   if (ds.floats != need) {
@@ -2260,8 +2467,8 @@ int mrt_renderer_display_enqueue(mrt_renderer* r, uint32_t flags, float compare_
   if (rc) return rc;
   // one device blit buffer: the next blit is queued behind this copy
   if (r->display.bytes < need * 4) HIP_TRY(r->display.alloc(need * 4));
-  rc = mrt_display(r->image, r->reference.as<float>(), r->display.as<float>(), r->desc.width, r->desc.height, flags,
-                   compare_scale, r->stream);
+  rc = mrt_display(denoised ? r->denoised.as<float>() : r->image, r->reference.as<float>(), r->display.as<float>(),
+                   r->desc.width, r->desc.height, flags, compare_scale, r->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(ds.host, r->display.p, need * 4, hipMemcpyDeviceToHost, r->stream));
   HIP_TRY(hipEventRecord(ds.done, r->stream));

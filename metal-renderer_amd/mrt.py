@@ -177,6 +177,27 @@ class Camera(ctypes.Structure):
         return {k: _plain(getattr(self, k)) for k, _ in self._fields_}
 
 
+class DenoiseParams(ctypes.Structure):
+    """mrt_denoise_params (include/mrt.h): the A-Trous filter's parameters."""
+    _fields_ = [
+        ("iterations", ctypes.c_uint32), ("sigma_color", ctypes.c_float), ("sigma_plane", ctypes.c_float),
+        ("normal_log2_power", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def default(cls, frames: int) -> "DenoiseParams":
+        """The library's defaults for an image of `frames` accumulated frames."""
+        p = cls()
+        _check(lib().mrt_denoise_params_default(frames, ctypes.byref(p)), "mrt_denoise_params_default")
+        return p
+
+    def check(self) -> None:
+        _check(lib().mrt_denoise_params_check(ctypes.byref(self)), "mrt_denoise_params_check")
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 EXPORTED = [
     "mrt_scene_create", "mrt_scene_info_get", "mrt_scene_export", "mrt_scene_destroy", "mrt_scene_check_bvh",
     "mrt_raygen", "mrt_intersect", "mrt_shade", "mrt_resolve_shadow", "mrt_accumulate",
@@ -196,6 +217,9 @@ EXPORTED = [
     "mrt_debug_magic_div", "mrt_comm_set_timeout", "mrt_comm_check", "mrt_debug_comm_fail",
     "mrt_camera_default", "mrt_camera_look_at", "mrt_camera_check", "mrt_raygen_camera",
     "mrt_renderer_set_camera", "mrt_renderer_get_camera",
+    "mrt_guides", "mrt_denoise_params_default", "mrt_denoise_params_check", "mrt_denoise",
+    "mrt_renderer_denoise", "mrt_renderer_read_denoised", "mrt_renderer_save_denoised", "mrt_debug_denoise_path",
+    "mrt_debug_denoise_step",
 ]
 
 _lib = None
@@ -285,6 +309,15 @@ def lib() -> ctypes.CDLL:
         "mrt_raygen_camera": [vp, ctypes.POINTER(Camera), u32, u32, vp, vp, u32, vp],
         "mrt_renderer_set_camera": [vp, ctypes.POINTER(Camera)],
         "mrt_renderer_get_camera": [vp, ctypes.POINTER(Camera)],
+        "mrt_guides": [vp, ctypes.POINTER(Camera), u32, u32, vp, vp, u32, vp],
+        "mrt_denoise_params_default": [u64, ctypes.POINTER(DenoiseParams)],
+        "mrt_denoise_params_check": [ctypes.POINTER(DenoiseParams)],
+        "mrt_denoise": [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(DenoiseParams), vp],
+        "mrt_renderer_denoise": [vp, ctypes.POINTER(DenoiseParams)],
+        "mrt_renderer_read_denoised": [vp, vp, ctypes.c_size_t],
+        "mrt_renderer_save_denoised": [vp, ctypes.c_char_p],
+        "mrt_debug_denoise_path": [u32],
+        "mrt_debug_denoise_step": [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(DenoiseParams), u32, u32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -508,6 +541,25 @@ class Renderer:
     def save_current_image(self, path: str) -> None:
         _check(lib().mrt_renderer_save_image(self._h, path.encode()), "mrt_renderer_save_image")
 
+    # ---- denoised output (include/mrt.h: mrt_renderer_denoise) ----
+    def denoise(self, params: "DenoiseParams | None" = None) -> None:
+        """Filter the accumulation image into the renderer's denoised buffer,
+        enqueued behind the draws queued so far (no host wait); params None =
+        DenoiseParams.default(frames accumulated).  The image is not written."""
+        _check(lib().mrt_renderer_denoise(self._h, ctypes.byref(params) if params is not None else None),
+               "mrt_renderer_denoise")
+
+    def read_denoised(self):
+        """[H, W, 4] float32 denoised image, row 0 = bottom."""
+        import numpy as np
+        img = np.zeros((self.height, self.width, 4), np.float32)
+        _check(lib().mrt_renderer_read_denoised(self._h, ctypes.c_void_p(img.ctypes.data), img.size),
+               "mrt_renderer_read_denoised")
+        return img
+
+    def save_denoised(self, path: str) -> None:
+        _check(lib().mrt_renderer_save_denoised(self._h, path.encode()), "mrt_renderer_save_denoised")
+
     # ---- multi-GPU exchange (include/mrt.h: mrt_renderer_exchange) ----
     def exchange(self, comm: "Comm", mode: int = EXCHANGE_GATHER) -> None:
         """Enqueue the image exchange of this shard renderer on its stream:
@@ -641,6 +693,39 @@ def accumulate(scene: Scene, width, height, frame_index, rays_ptr, image_ptr, pr
         synchronize(stream)
 
 
+def guides(scene: Scene, width: int, height: int, n_ptr: int, p_ptr: int, camera: Camera | None = None, precise=True,
+           stream=None, sync=True):
+    """First-hit guide planes of the denoiser (mrt_guides): (normal, bits(word))
+    and (position, t), W*H float4 each on the device."""
+    _check(lib().mrt_guides(scene.handle, ctypes.byref(camera) if camera is not None else None, width, height,
+                            n_ptr, p_ptr, _flags(precise), stream), "mrt_guides")
+    if sync:
+        synchronize(stream)
+
+
+def denoise(image_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, scratch_ptr: int, width: int, height: int,
+            params: DenoiseParams, stream=None, sync=True):
+    """The edge-avoiding A-Trous filter (mrt_denoise) on device buffers."""
+    _check(lib().mrt_denoise(image_ptr, n_ptr, p_ptr, out_ptr, scratch_ptr, width, height,
+                             ctypes.byref(params) if params is not None else None, stream), "mrt_denoise")
+    if sync:
+        synchronize(stream)
+
+
+def debug_denoise_path(path: int) -> None:
+    """Test entry: 0 = the shipped choice per step, 1 = direct, 2 = LDS-staged where supported."""
+    _check(lib().mrt_debug_denoise_path(path), "mrt_debug_denoise_path")
+
+
+def debug_denoise_step(image_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, scratch_ptr: int, width: int, height: int,
+                       params: DenoiseParams, step_log2: int, path: int, stream=None, sync=True) -> None:
+    """Measurement entry: one iteration at step 2^step_log2 with implementation `path`."""
+    _check(lib().mrt_debug_denoise_step(image_ptr, n_ptr, p_ptr, out_ptr, scratch_ptr, width, height,
+                                        ctypes.byref(params), step_log2, path, stream), "mrt_debug_denoise_step")
+    if sync:
+        synchronize(stream)
+
+
 def noise_table(seed: int, frame: int):
     import numpy as np
     out = np.zeros(64 * 64 * 4, np.float32)
@@ -659,6 +744,7 @@ def shard_mask(width: int, height: int, rank: int, count: int):
 
 
 DISPLAY_TONEMAP, DISPLAY_SRGB = 1, 2
+DISPLAY_DENOISED = 4   # Renderer.display / display_enqueue: blit the denoised buffer instead of the image
 
 
 def display_compare(mode: int) -> int:
