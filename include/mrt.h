@@ -291,6 +291,62 @@ int mrt_denoise_params_check(const mrt_denoise_params* p);
 int mrt_denoise(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
                 uint32_t width, uint32_t height, const mrt_denoise_params* params, void* stream);
 
+/* ---- temporal history -------------------------------------------------------
+ * Keep what has been accumulated across a camera move: the temporal half of
+ * SVGF (Schied et al., HPG 2017; DESIGN.md "Temporal reprojection"), driven by
+ * the guide planes of mrt_guides.  Not in the reference.  A COUNTED IMAGE is
+ * W*H float4 (r, g, b, h): h >= 0 is the number of frames behind the colour;
+ * h = 0 means no information, and the rgb is then (0, 0, 0).  Device pointers
+ * throughout. */
+typedef struct mrt_reproject_params {
+  float plane_tolerance;   /* > 0   */
+  float normal_cos_min;    /* [-1,1] */
+  float max_history;       /* >= 0: cap of the history length carried over a move */
+} mrt_reproject_params;
+/* Host only.  plane_tolerance = 0.01, normal_cos_min = 0.9, max_history = 32. */
+int mrt_reproject_params_default(mrt_reproject_params* out);
+/* Host only.  MRT_ERR_INVALID (with a message) for a field outside the ranges
+ * above, a non-finite one included. */
+int mrt_reproject_params_check(const mrt_reproject_params* p);
+
+/* Merge the accumulation image (`frames` frames of running mean) with a counted
+ * history (NULL = none) into the counted image `out`.  Per pixel, with
+ * h = history.w (0 without a history) and n = (float)frames:
+ *   h == 0:                            out = (image.rgb bitwise, n)
+ *   n == 0 (h > 0):                    out = history, bitwise
+ *   a component of image.rgb is not
+ *   finite (h > 0, n > 0):             out = history, bitwise (the history repairs the pixel)
+ *   otherwise:                         out.rgb = (h H.rgb + n I.rgb) / (h + n), out.w = h + n
+ * `out` may not alias `image` or `history` (MRT_ERR_INVALID). */
+int mrt_temporal_resolve(const float* image, uint64_t frames, const float* history /* may be NULL */, float* out,
+                         uint32_t width, uint32_t height, void* stream);
+
+/* Reproject the counted image `prev`, seen through prev_cam (NULL =
+ * mrt_camera_default; its lens is ignored, as mrt_guides ignores it) with guide
+ * planes prev_guide_n / prev_guide_p, into the view whose guide planes are
+ * cur_guide_n / cur_guide_p (all as mrt_guides writes them).  Per current
+ * pixel p:
+ *   p not filterable (word_p >= 0x80000000): (0, 0, 0, 0).
+ *   v = x_p - origin_prev, cz = v.forward_prev; cz <= 0: 0.
+ *   U = (v.right_prev) / cz, V = (v.up_prev) / cz, s = tan_half_fov_prev,
+ *   fx = (U / s + 1) (W - 1) / 2, fy = (V / (s H / W) + 1) (H - 1) / 2
+ *   (the inverse of the camera ray at the pixel centre);
+ *   x0 = floor(fx), y0 = floor(fy), ax = fx - x0, ay = fy - y0; the four taps
+ *   q = (x0 + i, y0 + j), bilinear weight b = (i ? ax : 1 - ax)(j ? ay : 1 - ay).
+ *   A tap counts iff q is inside the image, b > 0, word_q == word_p (previous
+ *   guide word against current), n_p.n_q >= normal_cos_min,
+ *   |n_p.(x_q - x_p)| <= plane_tolerance t_p, prev_q.w > 0 and prev_q.rgb finite.
+ *   B = sum of b over the taps that count; B == 0: 0.  Otherwise
+ *   rgb = sum b prev_q.rgb / B, h = min(max_history, sum b prev_q.w / B)
+ *   (a count of 0, possible only with max_history = 0, goes with rgb 0).
+ * The inputs are only read.  params == NULL, W < 2, H < 2, or history_out
+ * overlapping an input, is MRT_ERR_INVALID.  Static geometry only (no motion
+ * vectors). */
+int mrt_reproject(const float* prev, const float* prev_guide_n, const float* prev_guide_p,
+                  const mrt_camera* prev_cam /* NULL = default */, const float* cur_guide_n, const float* cur_guide_p,
+                  float* history_out, uint32_t width, uint32_t height, const mrt_reproject_params* params,
+                  void* stream);
+
 /* ---- renderer (B-1) ------------------------------------------------------ */
 typedef struct mrt_renderer_desc {
   const mrt_scene* scene;          /* not owned; must outlive the renderer */
@@ -410,6 +466,47 @@ int mrt_renderer_denoise(mrt_renderer* r, const mrt_denoise_params* params);
  * current size. */
 int mrt_renderer_read_denoised(mrt_renderer* r, float* rgba, size_t count);
 int mrt_renderer_save_denoised(mrt_renderer* r, const char* path);   /* .pfm / .exr */
+/* Temporal history (the section of that name above).  mrt_renderer_move_camera
+ * is mrt_renderer_set_camera that carries what has been accumulated into the
+ * new view, as a counted history image that lives BESIDE the accumulation
+ * image: the image itself is never written, and after move_camera(C); draw(n)
+ * it is bitwise that of a fresh renderer with set_camera(C); draw(n).
+ * Everything is enqueued on the renderer's main stream behind the draws queued
+ * so far, without a host wait; the buffers (previous guides 32 B, and three
+ * counted images of 16 B per pixel, beside the denoiser's guide planes, which
+ * are these same ones) are allocated at the first call only and re-made by
+ * resize.  In stream order: the guide planes of the camera in force are traced
+ * if they are not current; prev = resolve(image, frames accumulated, history if
+ * valid); the guide planes become the previous ones; the new camera is
+ * installed and the accumulation reset exactly as set_camera does; the new
+ * camera's guide planes are traced; history = reproject(prev, ...) with
+ * params (NULL = mrt_reproject_params_default).  A camera or params that fail
+ * their check, or a camera that cannot be installed, leave the renderer, its
+ * image and its history as they were.  A failure after the camera is installed
+ * (the reset, the new guide pass or the reprojection: a HIP error) leaves the
+ * new camera in force with the history dropped, as after set_camera.  With no
+ * frame accumulated and no valid
+ * history there is nothing to carry: the call is set_camera.
+ * mrt_renderer_set_camera, _reset and _resize invalidate the history.
+ * MRT_ERR_STATE on a sharded renderer (shard_count > 1): its image is whole
+ * only on rank 0 after an exchange, and a sharded history is not supported. */
+int mrt_renderer_move_camera(mrt_renderer* r, const mrt_camera* cam, const mrt_reproject_params* params);
+/* resolved = resolve(image, frames accumulated, history if valid), into a
+ * buffer the renderer owns, enqueued without a host wait.  With a valid history
+ * and no new frame it is the pure reprojection: the zero-latency frame after a
+ * move.  MRT_ERR_STATE when no frame has been accumulated and there is no
+ * valid history; MRT_ERR_STATE on a sharded renderer. */
+int mrt_renderer_resolve(mrt_renderer* r);
+/* The resolved buffer, as read_denoised / save_denoised give the denoised one;
+ * its fourth channel is the sample count h + n, not alpha (save writes it as
+ * the .exr's A).  MRT_ERR_STATE until a resolve has run at the current size. */
+int mrt_renderer_read_resolved(mrt_renderer* r, float* rgba, size_t count);
+int mrt_renderer_save_resolved(mrt_renderer* r, const char* path);   /* .pfm / .exr */
+/* mrt_renderer_resolve, then mrt_denoise of the resolved buffer into the
+ * renderer's denoised buffer (read_denoised, MRT_DISPLAY_DENOISED).  params
+ * NULL = mrt_denoise_params_default(max(frames accumulated, 1)), which ignores
+ * the history's length: conservative; a host that knows better passes its own. */
+int mrt_renderer_denoise_resolved(mrt_renderer* r, const mrt_denoise_params* params);
 int mrt_renderer_stats(const mrt_renderer* r, mrt_stats* stats);
 int mrt_renderer_destroy(mrt_renderer* r);
 
@@ -434,6 +531,8 @@ int mrt_shard_mask(uint32_t width, uint32_t height, uint32_t shard_rank, uint32_
 #define MRT_DISPLAY_SRGB 2u
 #define MRT_DISPLAY_DENOISED 4u   /* mrt_renderer_display / _display_enqueue: blit the denoised buffer instead of the
                                      image (MRT_ERR_STATE without a denoise at the current size); mrt_display ignores it */
+#define MRT_DISPLAY_RESOLVED 8u   /* ... blit the resolved buffer (MRT_ERR_STATE without a resolve at the current size;
+                                     MRT_ERR_INVALID together with MRT_DISPLAY_DENOISED); mrt_display ignores it */
 #define MRT_DISPLAY_COMPARE(mode) ((uint32_t)(mode) << 8)   /* 1 abs, 2 ref-to-color, 3 color-to-ref, 4 luminance */
 int mrt_display(const float* image, const float* reference, float* out, uint32_t width, uint32_t height,
                 uint32_t flags, float compare_scale, void* stream);

@@ -29,6 +29,16 @@
  *                   [--eye x,y,z] [--target x,y,z] [--up x,y,z] [--fov DEGREES]
  *                   [--aperture LENS_RADIUS] [--focus DISTANCE]
  *                   [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]
+ *                   [--orbit-steps K --orbit-degrees D]
+ * --orbit-steps K --orbit-degrees D (single rank only): after the first --spp
+ * frames, K times: the eye turns about the vertical axis through the target
+ * by D degrees (step k stands at k D from the first eye; the axis is the
+ * world's y axis whatever --up says; --orbit-degrees without --orbit-steps is
+ * an error), the camera moves
+ * with mrt_renderer_move_camera, which carries the accumulated history along,
+ * and --spp frames are drawn.  --out then receives the resolved image
+ * (mrt_renderer_resolve / _save_resolved), or with --denoise the image of
+ * mrt_renderer_denoise_resolved.
  * --denoise: after the last draw (and the exchange: only rank 0, which holds
  * the whole image, denoises) mrt_renderer_denoise with the defaults for --spp
  * frames, and --out receives the denoised image (mrt_renderer_save_denoised);
@@ -41,6 +51,7 @@
 #include <errno.h>
 #include <inttypes.h>
 #include <limits.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -67,6 +78,10 @@ typedef struct {
   int denoise, denoise_iterations_set, denoise_sigma_set;
   uint32_t denoise_iterations;
   float denoise_sigma_color;
+  /* orbit with temporal history (mrt_renderer_move_camera) */
+  uint32_t orbit_steps;
+  int orbit_degrees_set;
+  float orbit_degrees;
 } options;
 
 /* "x,y,z" -> three floats */
@@ -88,7 +103,12 @@ static void usage(void) {
           "                  [--gpus N] [--device D] [--exchange rccl|host]\n"
           "                  [--eye x,y,z] [--target x,y,z] [--up x,y,z] [--fov DEGREES]\n"
           "                  [--aperture LENS_RADIUS] [--focus DISTANCE]\n"
-          "                  [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]\n");
+          "                  [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]\n"
+          "                  [--orbit-steps K --orbit-degrees D]\n"
+          "  --orbit-steps K --orbit-degrees D (one rank): after the first --spp frames, K times: turn the eye by D\n"
+          "  degrees about the world's vertical (y) axis through the target, whatever --up says, move the camera\n"
+          "  keeping the accumulated history, draw --spp frames; --out gets the resolved image.  --orbit-degrees\n"
+          "  alone is an error.\n");
 }
 
 /* --scene cornellbox -> <dir of this executable>/../scenes/cornellbox.obj */
@@ -137,6 +157,8 @@ static int parse(int argc, char** argv, options* o) {
     else if (VAL("--focus")) { o->focus = strtof(v, NULL); o->camera_set = o->focus_set = 1; }
     else if (VAL("--denoise-iterations")) { o->denoise_iterations = (uint32_t)strtoul(v, NULL, 0); o->denoise = o->denoise_iterations_set = 1; }
     else if (VAL("--denoise-sigma-color")) { o->denoise_sigma_color = strtof(v, NULL); o->denoise = o->denoise_sigma_set = 1; }
+    else if (VAL("--orbit-steps")) o->orbit_steps = (uint32_t)strtoul(v, NULL, 0);
+    else if (VAL("--orbit-degrees")) { o->orbit_degrees = strtof(v, NULL); o->orbit_degrees_set = 1; }
     else if (strcmp(a, "--denoise") == 0) o->denoise = 1;
     else if (strcmp(a, "--precise") == 0) o->flags |= MRT_FLAG_PRECISE;
     else if (strcmp(a, "--static-noise") == 0) o->flags |= MRT_FLAG_STATIC_NOISE;
@@ -151,6 +173,33 @@ static int parse(int argc, char** argv, options* o) {
   if (o->gpus == 0 || o->spp == 0 || (strcmp(o->exchange, "rccl") && strcmp(o->exchange, "host"))) {
     usage();
     return -1;
+  }
+  if (o->orbit_degrees_set && !o->orbit_steps) {
+    fprintf(stderr, "mrt_render: --orbit-degrees needs --orbit-steps K, K > 0\n");
+    return -1;
+  }
+  if (o->orbit_steps && o->gpus > 1) {
+    fprintf(stderr, "mrt_render: --orbit-steps is single rank only (a sharded renderer keeps no temporal history)\n");
+    return -1;
+  }
+  return 0;
+}
+
+/* the camera of the options, seen from `eye`; look_at == 0 (only a lens was
+ * given): the reference's pose, bit for bit */
+static int make_camera(const options* o, const float eye[3], int look_at, mrt_camera* cam) {
+  if (!look_at) {
+    if (mrt_camera_default(cam)) return die("mrt_camera_default");
+  } else if (mrt_camera_look_at(eye, o->target, o->up, o->fov, cam)) {
+    return die("mrt_camera_look_at");
+  }
+  cam->lens_radius = o->aperture;
+  if (o->focus_set) {
+    cam->focus_distance = o->focus;
+  } else if (o->aperture > 0.0f) {   /* focused on the target */
+    float d = 0.0f;
+    for (int k = 0; k < 3; ++k) d += (o->target[k] - eye[k]) * cam->forward[k];
+    cam->focus_distance = d;
   }
   return 0;
 }
@@ -232,24 +281,22 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
   if (mrt_renderer_create(&rd, &r)) return die("mrt_renderer_create");
   if (o->camera_set) {   /* every rank sets the same camera */
     mrt_camera cam;
-    if (!o->pose_set) {   /* only a lens: the reference's pose, bit for bit */
-      if (mrt_camera_default(&cam)) return die("mrt_camera_default");
-    } else if (mrt_camera_look_at(o->eye, o->target, o->up, o->fov, &cam)) {
-      return die("mrt_camera_look_at");
-    }
-    cam.lens_radius = o->aperture;
-    if (o->focus_set) {
-      cam.focus_distance = o->focus;
-    } else if (o->aperture > 0.0f) {   /* focused on the target */
-      float d = 0.0f;
-      for (int k = 0; k < 3; ++k) d += (o->target[k] - o->eye[k]) * cam.forward[k];
-      cam.focus_distance = d;
-    }
+    if (make_camera(o, o->eye, o->pose_set, &cam)) return 1;
     if (mrt_renderer_set_camera(r, &cam)) return die("mrt_renderer_set_camera");
   }
   struct timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
   if (mrt_renderer_draw_n(r, o->spp)) return die("mrt_renderer_draw_n");
+  for (uint32_t k = 1; k <= o->orbit_steps; ++k) {   /* nothing here waits for the GPU */
+    const double a = (double)o->orbit_degrees * (double)k * (3.14159265358979323846 / 180.0);
+    const double dx = (double)o->eye[0] - (double)o->target[0], dz = (double)o->eye[2] - (double)o->target[2];
+    const float eye[3] = {(float)((double)o->target[0] + dx * cos(a) + dz * sin(a)), o->eye[1],
+                          (float)((double)o->target[2] - dx * sin(a) + dz * cos(a))};
+    mrt_camera cam;
+    if (make_camera(o, eye, 1, &cam)) return 1;
+    if (mrt_renderer_move_camera(r, &cam, NULL)) return die("mrt_renderer_move_camera");
+    if (mrt_renderer_draw_n(r, o->spp)) return die("mrt_renderer_draw_n");
+  }
   if (rccl) {
     if (mrt_renderer_exchange(r, comm, MRT_EXCHANGE_GATHER)) return die("mrt_renderer_exchange");
   } else if (N > 1) {
@@ -283,8 +330,15 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
       if (mrt_denoise_params_default(st.frame_index, &dp)) return die("mrt_denoise_params_default");
       if (o->denoise_iterations_set) dp.iterations = o->denoise_iterations;
       if (o->denoise_sigma_set) dp.sigma_color = o->denoise_sigma_color;
-      if (mrt_renderer_denoise(r, &dp)) return die("mrt_renderer_denoise");
+      if (o->orbit_steps) {
+        if (mrt_renderer_denoise_resolved(r, &dp)) return die("mrt_renderer_denoise_resolved");
+      } else if (mrt_renderer_denoise(r, &dp)) {
+        return die("mrt_renderer_denoise");
+      }
       if (mrt_renderer_save_denoised(r, o->out)) return die("mrt_renderer_save_denoised");
+    } else if (o->orbit_steps) {
+      if (mrt_renderer_resolve(r)) return die("mrt_renderer_resolve");
+      if (mrt_renderer_save_resolved(r, o->out)) return die("mrt_renderer_save_resolved");
     } else if (mrt_renderer_save_image(r, o->out)) {
       return die("mrt_renderer_save_image");
     }

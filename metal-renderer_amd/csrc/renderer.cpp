@@ -30,6 +30,7 @@
 #include "bvh.h"
 #include "bvh_gpu.h"
 #include "denoise.h"
+#include "temporal.h"
 #include "image.h"
 #include "kernels.h"
 #include "noise.h"
@@ -306,6 +307,12 @@ struct mrt_renderer {
   DevBuf guide_spill;              // the guide pass's own traversal-stack spill (deep trees; first denoise)
   bool guides_current = false;     // the planes hold the camera in force at the current size
   bool denoised_current = false;   // a denoise has run at the current size
+  // temporal history (mrt_renderer_move_camera): allocated at the first move
+  // (resolved: at the first resolve), re-made by resize.  The history is a
+  // counted image beside the accumulation image, in the view of `camera`.
+  DevBuf prev_guide_n, prev_guide_p, temporal_prev, history, resolved;
+  bool history_valid = false;      // `history` holds the reprojection into the camera in force
+  bool resolved_current = false;   // a resolve has run at the current size
   struct DisplaySlot {          // mrt_renderer_display_enqueue / _map: pinned copies of the blit
     float* host = nullptr;
     size_t floats = 0;
@@ -812,7 +819,7 @@ int mrt_shard_mask(uint32_t W, uint32_t H, uint32_t rank, uint32_t count, uint8_
 int mrt_display(const float* image, const float* reference, float* out, uint32_t W, uint32_t H, uint32_t flags,
                 float compare_scale, void* stream) {
   const uint32_t mode = (flags >> 8) & 0xFFu;
-  flags &= ~MRT_DISPLAY_DENOISED;   // a renderer-level choice of the source (mrt_renderer_display)
+  flags &= ~(MRT_DISPLAY_DENOISED | MRT_DISPLAY_RESOLVED);   // a renderer-level choice of the source (mrt_renderer_display)
   if (!image || !out || W == 0 || H == 0 || mode > 4 || (mode && !reference) || (flags & ~0xFF03u))
     return fail(MRT_ERR_INVALID, "mrt_display: bad argument");
   HIP_TRY(mrt::fast::launch_display(reinterpret_cast<const float4*>(image), reinterpret_cast<const float4*>(reference),
@@ -1822,6 +1829,94 @@ int mrt_debug_denoise_step(const float* image, const float* guide_n, const float
   return denoise_run(image, guide_n, guide_p, out, scratch, W, H, params, 1u, step_log2, path, stream);
 }
 
+// ---- temporal history (include/mrt.h) --------------------------------------
+int mrt_reproject_params_default(mrt_reproject_params* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_reproject_params_default: null params");
+  out->plane_tolerance = 0.01f;
+  out->normal_cos_min = 0.9f;
+  out->max_history = 32.0f;
+  return MRT_OK;
+}
+
+int mrt_reproject_params_check(const mrt_reproject_params* p) {
+  if (!p) return fail(MRT_ERR_INVALID, "reproject params: null");
+  if (!std::isfinite(p->plane_tolerance) || !(p->plane_tolerance > 0.0f))
+    return fail(MRT_ERR_INVALID, "reproject params: plane_tolerance must be finite and positive");
+  if (!std::isfinite(p->normal_cos_min) || p->normal_cos_min < -1.0f || p->normal_cos_min > 1.0f)
+    return fail(MRT_ERR_INVALID, "reproject params: normal_cos_min must be in [-1, 1]");
+  if (!std::isfinite(p->max_history) || p->max_history < 0.0f)
+    return fail(MRT_ERR_INVALID, "reproject params: max_history must be finite and not negative");
+  return MRT_OK;
+}
+
+namespace {
+bool planes_overlap(const void* a, const void* b, size_t bytes) {
+  const char* p = (const char*)a;
+  const char* q = (const char*)b;
+  return p < q + bytes && q < p + bytes;
+}
+}  // namespace
+
+int mrt_temporal_resolve(const float* image, uint64_t frames, const float* history, float* out, uint32_t W, uint32_t H,
+                         void* stream) {
+  if (!image || !out || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_temporal_resolve: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  if (planes_overlap(image, out, bytes) || (history && planes_overlap(history, out, bytes)))
+    return fail(MRT_ERR_INVALID, "mrt_temporal_resolve: out must not overlap image or history");
+  mrt::ResolveArgs a{};
+  a.image = reinterpret_cast<const float4*>(image);
+  a.history = reinterpret_cast<const float4*>(history);
+  a.out = reinterpret_cast<float4*>(out);
+  a.count = W * H;
+  a.frames = (float)frames;
+  HIP_TRY(mrt::launch_temporal_resolve(a, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+int mrt_reproject(const float* prev, const float* prev_guide_n, const float* prev_guide_p, const mrt_camera* prev_cam,
+                  const float* cur_guide_n, const float* cur_guide_p, float* history_out, uint32_t W, uint32_t H,
+                  const mrt_reproject_params* params, void* stream) {
+  if (!prev || !prev_guide_n || !prev_guide_p || !cur_guide_n || !cur_guide_p || !history_out || !params || W < 2 ||
+      H < 2 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_reproject: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  for (const float* in : {prev, prev_guide_n, prev_guide_p, cur_guide_n, cur_guide_p})
+    if (planes_overlap(in, history_out, bytes))
+      return fail(MRT_ERR_INVALID, "mrt_reproject: history_out must not overlap an input");
+  int rc = mrt_reproject_params_check(params);
+  if (rc) return rc;
+  mrt_camera c;
+  if (prev_cam) {
+    rc = mrt_camera_check(prev_cam);
+    if (rc) return rc;
+    c = *prev_cam;
+  } else {
+    (void)mrt_camera_default(&c);
+  }
+  mrt::ReprojectArgs a{};
+  a.prev = reinterpret_cast<const float4*>(prev);
+  a.prev_n = reinterpret_cast<const float4*>(prev_guide_n);
+  a.prev_p = reinterpret_cast<const float4*>(prev_guide_p);
+  a.cur_n = reinterpret_cast<const float4*>(cur_guide_n);
+  a.cur_p = reinterpret_cast<const float4*>(cur_guide_p);
+  a.out = reinterpret_cast<float4*>(history_out);
+  a.width = W;
+  a.height = H;
+  for (int k = 0; k < 3; ++k) {
+    a.origin[k] = c.origin[k];
+    a.right[k] = c.right[k];
+    a.up[k] = c.up[k];
+    a.forward[k] = c.forward[k];
+  }
+  a.tan_half_fov = c.tan_half_fov;   // the lens is ignored, as the guide pass ignores it
+  a.plane_tolerance = params->plane_tolerance;
+  a.normal_cos_min = params->normal_cos_min;
+  a.max_history = params->max_history;
+  HIP_TRY(mrt::launch_reproject(a, (hipStream_t)stream));
+  return MRT_OK;
+}
+
 int mrt_intersect(const mrt_scene* scene, const void* rays, uint32_t stride, uint32_t count, void* isect,
                   uint32_t flags, void* stream) {
   if (!scene || (!rays && count) || (!isect && count) || stride < 32 || (stride % 4))
@@ -1999,12 +2094,19 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   r->desc.height = height;
   r->x.slab_floats = 0;    // the exchange buffers are re-sized for the new image at the next exchange
   r->guides_current = r->denoised_current = false;
+  r->history_valid = r->resolved_current = false;
   if (r->denoised.p) {     // a renderer that has denoised keeps its buffers, at the new size
     const size_t bytes = (size_t)width * height * 16;
     HIP_TRY(r->guide_n.alloc(bytes));
     HIP_TRY(r->guide_p.alloc(bytes));
     HIP_TRY(r->denoised.alloc(bytes));
     HIP_TRY(r->denoise_scratch.alloc(bytes));
+  }
+  {   // likewise the temporal history's buffers, each where it exists
+    const size_t bytes = (size_t)width * height * 16;
+    for (DevBuf* b : {&r->guide_n, &r->guide_p, &r->prev_guide_n, &r->prev_guide_p, &r->temporal_prev, &r->history,
+                      &r->resolved})
+      if (b->p && b->bytes != bytes) HIP_TRY(b->alloc(bytes));
   }
   return alloc_frame_buffers(r);
 }
@@ -2023,6 +2125,7 @@ int mrt_renderer_reset(mrt_renderer* r) {
   }
   r->frame_index = 0;
   r->stats.frame_index = 0;   // cumulative counters (paths, A, kernel time) persist
+  r->history_valid = false;   // (mrt_renderer_move_camera sets it again once it has reprojected)
   return MRT_OK;
 }
 
@@ -2400,6 +2503,160 @@ int mrt_renderer_save_denoised(mrt_renderer* r, const char* path) {
   return save_rgba(path, img, W, H);
 }
 
+// ---- temporal history (include/mrt.h: mrt_renderer_move_camera) -------------
+namespace {
+// the guide planes of the camera in force, on the main stream (allocated here
+// when neither a denoise nor a move has made them yet).  The same allocation
+// and trace as in mrt_renderer_denoise, which stays as it was: keep the two in
+// step.  Known cost of leaving it alone: a renderer that moves before it has
+// a denoised buffer (made by the first mrt_renderer_denoise or
+// _denoise_resolved) has its guide planes freed (a host-synchronising
+// hipFree), re-made and traced again by its first mrt_renderer_denoise, whose
+// first-call test looks at the denoised buffer only.  Once per renderer and
+// size, and the result is the same.
+int ensure_guides(mrt_renderer* r) {
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  const size_t bytes = (size_t)W * H * 16;
+  if (r->guide_n.bytes != bytes || !r->guide_n.p || r->guide_p.bytes != bytes || !r->guide_p.p) {
+    r->guides_current = false;
+    HIP_TRY(r->guide_n.alloc(bytes));
+    HIP_TRY(r->guide_p.alloc(bytes));
+  }
+  if (r->guides_current) return MRT_OK;
+  if (!r->guide_spill.p) HIP_TRY(alloc_isect_spill(r->guide_spill, r->scene->dev.max_stack));
+  const int rc = guides_with_spill(r->scene, &r->camera, W, H, r->guide_n.as<float>(), r->guide_p.as<float>(),
+                                   r->desc.flags & MRT_FLAG_PRECISE, r->guide_spill.as<uint32_t>(), r->stream);
+  if (rc) return rc;
+  r->guides_current = true;
+  return MRT_OK;
+}
+
+int temporal_usable(const mrt_renderer* r, const char* what) {
+  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
+  if (r->desc.shard_count > 1)
+    return fail(MRT_ERR_STATE, std::string(what) + ": a sharded renderer keeps no temporal history");
+  return MRT_OK;
+}
+
+// resolve(image, frame_index, history if valid) into `out`, on the main stream
+int resolve_into(mrt_renderer* r, DevBuf& out) {
+  const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
+  if (out.bytes != bytes || !out.p) HIP_TRY(out.alloc(bytes));
+  return mrt_temporal_resolve(r->image, r->frame_index, r->history_valid ? r->history.as<float>() : nullptr,
+                              out.as<float>(), r->desc.width, r->desc.height, r->stream);
+}
+}  // namespace
+
+int mrt_renderer_move_camera(mrt_renderer* r, const mrt_camera* cam, const mrt_reproject_params* params) {
+  int rc = temporal_usable(r, "mrt_renderer_move_camera");
+  if (rc) return rc;
+  rc = mrt_camera_check(cam);
+  if (rc) return rc;
+  mrt_reproject_params p;
+  if (params) p = *params;
+  else (void)mrt_reproject_params_default(&p);
+  rc = mrt_reproject_params_check(&p);
+  if (rc) return rc;
+  if (r->frame_index == 0 && !r->history_valid) return mrt_renderer_set_camera(r, cam);   // nothing to carry
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  const size_t bytes = (size_t)W * H * 16;
+  HIP_TRY(hipSetDevice(r->scene->device));
+  for (DevBuf* b : {&r->prev_guide_n, &r->prev_guide_p, &r->temporal_prev, &r->history})   // the first move only
+    if (b->bytes != bytes || !b->p) HIP_TRY(b->alloc(bytes));
+  // what the old camera saw: its guide planes, and everything accumulated
+  // through it (a scratch image: the history itself is replaced last)
+  rc = ensure_guides(r);
+  if (rc) return rc;
+  rc = resolve_into(r, r->temporal_prev);
+  if (rc) return rc;
+  // the new camera, as mrt_renderer_set_camera installs it: failing here
+  // leaves the previous camera in force, nothing reset, the history as it was
+  const mrt_camera old = r->camera;
+  const bool old_moved = r->camera_moved;
+  r->camera = *cam;
+  r->camera_moved = !camera_is_default(*cam);
+  rc = install_camera(r, false);
+  if (rc) {
+    r->camera = old;
+    r->camera_moved = old_moved;
+    return rc;
+  }
+  std::swap(r->guide_n.p, r->prev_guide_n.p);   // equal sizes: the planes of `old` become the previous ones
+  std::swap(r->guide_p.p, r->prev_guide_p.p);
+  r->guides_current = false;
+  r->history_valid = false;     // from here on a failure leaves the new camera without a history, as set_camera would
+  rc = mrt_renderer_reset(r);
+  if (rc) return rc;
+  rc = ensure_guides(r);
+  if (rc) return rc;
+  rc = mrt_reproject(r->temporal_prev.as<float>(), r->prev_guide_n.as<float>(), r->prev_guide_p.as<float>(), &old,
+                     r->guide_n.as<float>(), r->guide_p.as<float>(), r->history.as<float>(), W, H, &p, r->stream);
+  if (rc) return rc;
+  r->history_valid = true;
+  return MRT_OK;
+}
+
+int mrt_renderer_resolve(mrt_renderer* r) {
+  int rc = temporal_usable(r, "mrt_renderer_resolve");
+  if (rc) return rc;
+  if (r->frame_index == 0 && !r->history_valid)
+    return fail(MRT_ERR_STATE, "mrt_renderer_resolve: no frame accumulated and no valid history");
+  HIP_TRY(hipSetDevice(r->scene->device));
+  rc = resolve_into(r, r->resolved);
+  if (rc) return rc;
+  r->resolved_current = true;
+  return MRT_OK;
+}
+
+int mrt_renderer_read_resolved(mrt_renderer* r, float* rgba, size_t count) {
+  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
+  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
+  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
+  if (!r->resolved_current) return fail(MRT_ERR_STATE, "no resolve has run at the renderer's current size");
+  const int rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(rgba, r->resolved.p, need * 4, hipMemcpyDeviceToHost));
+  return MRT_OK;
+}
+
+int mrt_renderer_save_resolved(mrt_renderer* r, const char* path) {
+  if (!r || !path) return fail(MRT_ERR_INVALID, "null argument");
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  std::vector<float> img((size_t)W * H * 4);
+  const int rc = mrt_renderer_read_resolved(r, img.data(), img.size());
+  if (rc) return rc;
+  return save_rgba(path, img, W, H);
+}
+
+int mrt_renderer_denoise_resolved(mrt_renderer* r, const mrt_denoise_params* params) {
+  int rc = temporal_usable(r, "mrt_renderer_denoise_resolved");
+  if (rc) return rc;
+  if (r->frame_index == 0 && !r->history_valid)
+    return fail(MRT_ERR_STATE, "mrt_renderer_denoise_resolved: no frame accumulated and no valid history");
+  mrt_denoise_params p;
+  if (params) p = *params;
+  else (void)mrt_denoise_params_default(std::max<uint64_t>(r->frame_index, 1), &p);
+  rc = mrt_denoise_params_check(&p);
+  if (rc) return rc;
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  const size_t bytes = (size_t)W * H * 16;
+  HIP_TRY(hipSetDevice(r->scene->device));
+  for (DevBuf* b : {&r->denoised, &r->denoise_scratch})
+    if (b->bytes != bytes || !b->p) {
+      r->denoised_current = false;
+      HIP_TRY(b->alloc(bytes));
+    }
+  rc = mrt_renderer_resolve(r);
+  if (rc) return rc;
+  rc = ensure_guides(r);
+  if (rc) return rc;
+  rc = mrt_denoise(r->resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(), r->denoised.as<float>(),
+                   r->denoise_scratch.as<float>(), W, H, &p, r->stream);
+  if (rc) return rc;
+  r->denoised_current = true;
+  return MRT_OK;
+}
+
 int mrt_image_load_exr(const char* path, float* rgba, size_t capacity, uint32_t* width, uint32_t* height) {
   if (!path || !width || !height) return fail(MRT_ERR_INVALID, "mrt_image_load_exr: null argument");
   std::vector<float> img;
@@ -2435,11 +2692,14 @@ int mrt_renderer_display(mrt_renderer* r, uint32_t flags, float compare_scale, f
   if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
   if (((flags >> 8) & 0xFFu) && !r->reference.p) return fail(MRT_ERR_STATE, "compare mode without a loaded reference");
   const bool denoised = (flags & MRT_DISPLAY_DENOISED) != 0;
+  const bool resolved = (flags & MRT_DISPLAY_RESOLVED) != 0;
+  if (denoised && resolved) return fail(MRT_ERR_INVALID, "MRT_DISPLAY_DENOISED and MRT_DISPLAY_RESOLVED are exclusive");
   if (denoised && !r->denoised_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_DENOISED without a denoise at the current size");
+  if (resolved && !r->resolved_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_RESOLVED without a resolve at the current size");
   int rc = exchange_flush(r);
   if (rc) return rc;
   if (r->display.bytes < need * 4) HIP_TRY(r->display.alloc(need * 4));
-  rc = mrt_display(denoised ? r->denoised.as<float>() : r->image, r->reference.as<float>(), r->display.as<float>(), r->desc.width, r->desc.height, flags,
+  rc = mrt_display(denoised ? r->denoised.as<float>() : (resolved ? r->resolved.as<float>() : r->image), r->reference.as<float>(), r->display.as<float>(), r->desc.width, r->desc.height, flags,
                    compare_scale, r->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(rgba, r->display.p, need * 4, hipMemcpyDeviceToHost, r->stream));
@@ -2452,7 +2712,10 @@ int mrt_renderer_display_enqueue(mrt_renderer* r, uint32_t flags, float compare_
   if (((flags >> 8) & 0xFFu) && !r->reference.p) return fail(MRT_ERR_STATE, "compare mode without a loaded reference");
   const size_t need = (size_t)r->desc.width * r->desc.height * 4;
   const bool denoised = (flags & MRT_DISPLAY_DENOISED) != 0;
+  const bool resolved = (flags & MRT_DISPLAY_RESOLVED) != 0;
+  if (denoised && resolved) return fail(MRT_ERR_INVALID, "MRT_DISPLAY_DENOISED and MRT_DISPLAY_RESOLVED are exclusive");
   if (denoised && !r->denoised_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_DENOISED without a denoise at the current size");
+  if (resolved && !r->resolved_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_RESOLVED without a resolve at the current size");
   auto& ds = r->shown[slot];
   if (ds.queued) HIP_TRY(hipEventSynchronize(ds.done));   // its previous copy may still be landing
   if (ds.floats != need) {
@@ -2467,7 +2730,7 @@ int mrt_renderer_display_enqueue(mrt_renderer* r, uint32_t flags, float compare_
   if (rc) return rc;
   // one device blit buffer: the next blit is queued behind this copy
   if (r->display.bytes < need * 4) HIP_TRY(r->display.alloc(need * 4));
-  rc = mrt_display(denoised ? r->denoised.as<float>() : r->image, r->reference.as<float>(), r->display.as<float>(),
+  rc = mrt_display(denoised ? r->denoised.as<float>() : (resolved ? r->resolved.as<float>() : r->image), r->reference.as<float>(), r->display.as<float>(),
                    r->desc.width, r->desc.height, flags, compare_scale, r->stream);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(ds.host, r->display.p, need * 4, hipMemcpyDeviceToHost, r->stream));

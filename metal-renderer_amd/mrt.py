@@ -198,6 +198,25 @@ class DenoiseParams(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ReprojectParams(ctypes.Structure):
+    """mrt_reproject_params (include/mrt.h): the history reprojection's tests."""
+    _fields_ = [
+        ("plane_tolerance", ctypes.c_float), ("normal_cos_min", ctypes.c_float), ("max_history", ctypes.c_float),
+    ]
+
+    @classmethod
+    def default(cls) -> "ReprojectParams":
+        p = cls()
+        _check(lib().mrt_reproject_params_default(ctypes.byref(p)), "mrt_reproject_params_default")
+        return p
+
+    def check(self) -> None:
+        _check(lib().mrt_reproject_params_check(ctypes.byref(self)), "mrt_reproject_params_check")
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 EXPORTED = [
     "mrt_scene_create", "mrt_scene_info_get", "mrt_scene_export", "mrt_scene_destroy", "mrt_scene_check_bvh",
     "mrt_raygen", "mrt_intersect", "mrt_shade", "mrt_resolve_shadow", "mrt_accumulate",
@@ -220,6 +239,9 @@ EXPORTED = [
     "mrt_guides", "mrt_denoise_params_default", "mrt_denoise_params_check", "mrt_denoise",
     "mrt_renderer_denoise", "mrt_renderer_read_denoised", "mrt_renderer_save_denoised", "mrt_debug_denoise_path",
     "mrt_debug_denoise_step",
+    "mrt_reproject_params_default", "mrt_reproject_params_check", "mrt_temporal_resolve", "mrt_reproject",
+    "mrt_renderer_move_camera", "mrt_renderer_resolve", "mrt_renderer_read_resolved", "mrt_renderer_save_resolved",
+    "mrt_renderer_denoise_resolved",
 ]
 
 _lib = None
@@ -318,6 +340,15 @@ def lib() -> ctypes.CDLL:
         "mrt_renderer_save_denoised": [vp, ctypes.c_char_p],
         "mrt_debug_denoise_path": [u32],
         "mrt_debug_denoise_step": [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(DenoiseParams), u32, u32, vp],
+        "mrt_reproject_params_default": [ctypes.POINTER(ReprojectParams)],
+        "mrt_reproject_params_check": [ctypes.POINTER(ReprojectParams)],
+        "mrt_temporal_resolve": [vp, u64, vp, vp, u32, u32, vp],
+        "mrt_reproject": [vp, vp, vp, ctypes.POINTER(Camera), vp, vp, vp, u32, u32, ctypes.POINTER(ReprojectParams), vp],
+        "mrt_renderer_move_camera": [vp, ctypes.POINTER(Camera), ctypes.POINTER(ReprojectParams)],
+        "mrt_renderer_resolve": [vp],
+        "mrt_renderer_read_resolved": [vp, vp, ctypes.c_size_t],
+        "mrt_renderer_save_resolved": [vp, ctypes.c_char_p],
+        "mrt_renderer_denoise_resolved": [vp, ctypes.POINTER(DenoiseParams)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -560,6 +591,38 @@ class Renderer:
     def save_denoised(self, path: str) -> None:
         _check(lib().mrt_renderer_save_denoised(self._h, path.encode()), "mrt_renderer_save_denoised")
 
+    # ---- temporal history (include/mrt.h: mrt_renderer_move_camera) ----
+    def move_camera(self, camera: Camera, params: "ReprojectParams | None" = None) -> None:
+        """set_camera() that carries what has been accumulated into the new
+        view, as a counted history beside the image (no host wait); params
+        None = ReprojectParams.default()."""
+        _check(lib().mrt_renderer_move_camera(self._h, ctypes.byref(camera),
+                                              ctypes.byref(params) if params is not None else None),
+               "mrt_renderer_move_camera")
+
+    def resolve(self) -> None:
+        """Merge the image with the history into the renderer's resolved
+        buffer, enqueued behind the draws queued so far (no host wait)."""
+        _check(lib().mrt_renderer_resolve(self._h), "mrt_renderer_resolve")
+
+    def read_resolved(self):
+        """[H, W, 4] float32 resolved image, row 0 = bottom; the fourth channel
+        is the sample count behind the pixel."""
+        import numpy as np
+        img = np.zeros((self.height, self.width, 4), np.float32)
+        _check(lib().mrt_renderer_read_resolved(self._h, ctypes.c_void_p(img.ctypes.data), img.size),
+               "mrt_renderer_read_resolved")
+        return img
+
+    def save_resolved(self, path: str) -> None:
+        _check(lib().mrt_renderer_save_resolved(self._h, path.encode()), "mrt_renderer_save_resolved")
+
+    def denoise_resolved(self, params: "DenoiseParams | None" = None) -> None:
+        """resolve(), then the A-Trous filter of the resolved buffer into the
+        denoised buffer; params None = DenoiseParams.default(max(frames, 1))."""
+        _check(lib().mrt_renderer_denoise_resolved(self._h, ctypes.byref(params) if params is not None else None),
+               "mrt_renderer_denoise_resolved")
+
     # ---- multi-GPU exchange (include/mrt.h: mrt_renderer_exchange) ----
     def exchange(self, comm: "Comm", mode: int = EXCHANGE_GATHER) -> None:
         """Enqueue the image exchange of this shard renderer on its stream:
@@ -712,6 +775,29 @@ def denoise(image_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, scratch_ptr: i
         synchronize(stream)
 
 
+def temporal_resolve(image_ptr: int, frames: int, history_ptr: "int | None", out_ptr: int, width: int, height: int,
+                     stream=None, sync=True) -> None:
+    """Merge an accumulation image of `frames` frames with a counted history
+    (None = no history) into a counted image (mrt_temporal_resolve)."""
+    _check(lib().mrt_temporal_resolve(image_ptr, frames, history_ptr, out_ptr, width, height, stream),
+           "mrt_temporal_resolve")
+    if sync:
+        synchronize(stream)
+
+
+def reproject(prev_ptr: int, prev_n_ptr: int, prev_p_ptr: int, prev_camera: "Camera | None", cur_n_ptr: int,
+              cur_p_ptr: int, out_ptr: int, width: int, height: int, params: "ReprojectParams | None", stream=None,
+              sync=True) -> None:
+    """Reproject a counted image through the guide planes of the previous and
+    the current camera (mrt_reproject)."""
+    _check(lib().mrt_reproject(prev_ptr, prev_n_ptr, prev_p_ptr,
+                               ctypes.byref(prev_camera) if prev_camera is not None else None, cur_n_ptr, cur_p_ptr,
+                               out_ptr, width, height, ctypes.byref(params) if params is not None else None, stream),
+           "mrt_reproject")
+    if sync:
+        synchronize(stream)
+
+
 def debug_denoise_path(path: int) -> None:
     """Test entry: 0 = the shipped choice per step, 1 = direct, 2 = LDS-staged where supported."""
     _check(lib().mrt_debug_denoise_path(path), "mrt_debug_denoise_path")
@@ -745,6 +831,7 @@ def shard_mask(width: int, height: int, rank: int, count: int):
 
 DISPLAY_TONEMAP, DISPLAY_SRGB = 1, 2
 DISPLAY_DENOISED = 4   # Renderer.display / display_enqueue: blit the denoised buffer instead of the image
+DISPLAY_RESOLVED = 8   # ... the resolved buffer (Renderer.resolve); not together with DISPLAY_DENOISED
 
 
 def display_compare(mode: int) -> int:
