@@ -655,12 +655,25 @@ int mrt_debug_wave_times(uint64_t* out, size_t n);
  * the last reset — per traversal loop the wave iterations and the active
  * lanes in them (tools/lane_stats.py names the slots).  Zeros otherwise. */
 int mrt_debug_lanes(uint64_t* out, size_t n, int reset);
+/* Test entry: the scene's leaf-box sweep list (kernels.hip sweep_nearest) —
+ * *count leaf records of the main tree, of which min(*count, capacity) are
+ * copied to `records` (may be NULL) as 8 floats each: (lo.xyz, bits(leaf
+ * ref)), (hi.xyz, 0), the leaf's child box as its parent node holds it, in
+ * node and slot order; 0 records for a tree the sweep cannot take (more than
+ * 32 leaves, or a leaf root).  *enabled: nearest queries of the bounce and
+ * stream kernels sweep this list instead of walking the tree (the whole
+ * scene is staged in LDS and MRT_SWEEP=0 is not set under MRT_DIAG=1). */
+int mrt_debug_sweep_list(const mrt_scene* scene, float* records, uint32_t capacity, uint32_t* count,
+                         uint32_t* enabled);
 /* Test entry (ABI 7): rank 0's unpack of an N-rank gather without a
  * communicator.  `gathered` (host) holds nranks slabs of
  * mrt_tiles_packed_floats(W, H, 0, nranks) floats, rank k's at slab k, as the
  * gather of MRT_EXCHANGE_GATHER delivers them; the renderer (shard_rank 0,
  * shard_count nranks) unpacks slabs 1..N-1 into its image with the RCCL
  * path's own unpack.  Synchronises the renderer. */
+/* Test entry: the main tree's BVH4 nodes as the host holds them (128 bytes
+ * each, mrt_layout.h); *count nodes, min(*count, capacity) copied. */
+int mrt_debug_bvh_nodes(const mrt_scene* scene, float* nodes, uint32_t capacity, uint32_t* count);
 int mrt_debug_exchange_unpack(mrt_renderer* r, uint32_t nranks, const float* gathered, size_t floats);
 /* Test entry (ABI 9, host only, no device): the traversal culling slack each
  * ray's nearest hit needs in the scene's main tree.  For ray record i

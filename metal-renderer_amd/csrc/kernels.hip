@@ -270,7 +270,7 @@ __device__ __forceinline__ void box4(const float4* q, V3 o, const RayBox& rb, fl
 //   kAllLds  — small scenes: every node, leaf triangle, per-primitive shading
 //              record, material and light entry is staged in LDS once per
 //              block, so traversal and shading never leave the CU.
-// LDS image: [nodes][triangles][prims][materials][lights] as float4, then the
+// LDS image: [nodes][triangles][prims][materials][lights][sweep list] as float4, then the
 // uint32 scratch (segment prefix), then the stack laid out [entry][lane]
 // (consecutive lanes hit consecutive banks).  All LDS accesses index the
 // __shared__ symbol directly so they lower to ds_read/ds_write (a pointer
@@ -284,6 +284,7 @@ struct LdsCtx {
   uint32_t prim_base;
   uint32_t mat_base;
   uint32_t light_base;
+  uint32_t sweep_base;    // the sweep list's leaf records (kAllLds, sc.sweep_leaves of them)
   uint32_t scratch_base;  // uint32 offset of the per-block scratch
   uint32_t stack_base;    // uint32 offset of the block's stack slot 0 (lane 0's); lanes add threadIdx.x
   uint32_t* spill;        // stack entries >= STACK: the block's rows of a global [lane][word] spill
@@ -316,7 +317,8 @@ __host__ __device__ inline uint32_t scene_nodes(const DeviceScene& sc) { return 
 __host__ __device__ inline uint32_t scene_tri_records(const DeviceScene& sc) { return sc.num_triangles + sc.occ_tris; }
 __host__ __device__ inline uint32_t lds_scene_float4s(int mode, const DeviceScene& sc) {
   return lds_scene_float4s(mode, node_float4s(sc.width), scene_nodes(sc), sc.lds_nodes, scene_tri_records(sc),
-                           sc.num_triangles, sc.num_materials, sc.num_lights + 1);
+                           sc.num_triangles, sc.num_materials, sc.num_lights + 1) +
+         (mode == kAllLds ? 2 * sc.sweep_leaves : 0u);   // the sweep list's leaf records (sweep_nearest)
 }
 
 // 16-B buffer load at a 32-bit byte offset from a wave-uniform descriptor
@@ -430,6 +432,7 @@ __device__ __forceinline__ LdsCtx stage_lds(const DeviceScene& sc, uint32_t scra
   const uint32_t T = (MODE == kAllLds) ? sc.num_triangles : 0u;          // per-primitive records
   const uint32_t M = (MODE == kAllLds) ? sc.num_materials : 0u;
   const uint32_t NL = (MODE == kAllLds) ? sc.num_lights + 1 : 0u;
+  const uint32_t SW = (MODE == kAllLds) ? sc.sweep_leaves : 0u;
   cx.n_lds_nodes = n_nodes;
   const uint32_t node_f4 = node_stride_f4(MODE, nf4);
   const bool copies = node_f4 != nf4;
@@ -437,18 +440,19 @@ __device__ __forceinline__ LdsCtx stage_lds(const DeviceScene& sc, uint32_t scra
   cx.prim_base = cx.tri_base + 3 * TR;
   cx.mat_base = cx.prim_base + 6 * T;
   cx.light_base = cx.mat_base + 2 * M;
-  const uint32_t f4 = cx.light_base + 7 * NL;
+  cx.sweep_base = cx.light_base + 7 * NL;
+  const uint32_t f4 = cx.sweep_base + 2 * SW;
   cx.scratch_base = 4 * f4;
   cx.stack_base = cx.scratch_base + ((scratch_u32 + 3) & ~3u);
   cx.spill_lane = sc.max_stack;
   cx.spill = spill ? spill + (size_t)blockIdx.x * kBlock * cx.spill_lane : nullptr;
   if (MODE != kGlobal) {
-    const float4* src[5] = {reinterpret_cast<const float4*>(sc.nodes), reinterpret_cast<const float4*>(sc.tris),
+    const float4* src[6] = {reinterpret_cast<const float4*>(sc.nodes), reinterpret_cast<const float4*>(sc.tris),
                             reinterpret_cast<const float4*>(sc.prims), reinterpret_cast<const float4*>(sc.materials),
-                            reinterpret_cast<const float4*>(sc.lights)};
-    const uint32_t base[5] = {0u, cx.tri_base, cx.prim_base, cx.mat_base, cx.light_base};
-    const uint32_t len[5] = {nf4 * n_nodes, 3 * TR, 6 * T, 2 * M, 7 * NL};
-    for (int r = copies ? 1 : 0; r < 5; ++r)
+                            reinterpret_cast<const float4*>(sc.lights), reinterpret_cast<const float4*>(sc.sweep)};
+    const uint32_t base[6] = {0u, cx.tri_base, cx.prim_base, cx.mat_base, cx.light_base, cx.sweep_base};
+    const uint32_t len[6] = {nf4 * n_nodes, 3 * TR, 6 * T, 2 * M, 7 * NL, 2 * SW};
+    for (int r = copies ? 1 : 0; r < 6; ++r)
       for (uint32_t i = threadIdx.x; i < len[r]; i += kBlock) g_lds[base[r] + i] = src[r][i];
     if (copies) {   // quadrant copies: x, y rows (near, far), z rows (lo, hi), refs
       for (uint32_t i = threadIdx.x; i < node_f4 * n_nodes; i += kBlock) {
@@ -480,6 +484,8 @@ __device__ __forceinline__ LdsCtx stage_lds(const DeviceScene& sc, uint32_t scra
 //   20-25 path kernel: service rounds, lanes serviced, traversal rounds,
 //         lanes traversing in them, lanes refilled, outer iterations
 //   26-27 stream kernel: camera iterations, queue-level iterations
+//   30-31 leaf-box sweep (nearest queries; their leaf tests count in 4-5):
+//         pop-and-cull rounds, lanes in them
 // ---------------------------------------------------------------------------
 #ifndef MRT_LANESTATS
 #define MRT_LANESTATS 0
@@ -743,6 +749,93 @@ __device__ __forceinline__ bool traverse(const DeviceScene& sc, const LdsCtx& cx
 }
 
 
+// Leaf-box sweep: the nearest hit of a small all-in-LDS tree without a walk
+// (DESIGN §2.1i).  The while-while walk parks a lane's first leaf and pushes
+// the rest before any h.t exists, so its culling removes almost nothing in a
+// shallow tree and the wave runs as many leaf rounds as its unluckiest lane.
+// Phase 1 tests every leaf box of the sweep list (DeviceScene::sweep; the
+// records are wave-uniform: scalar loads into SGPRs, no VGPR or LDS traffic)
+// with the walk's own slab arithmetic and keeps, per lane, the two nearest leaves by
+// box entry as packed keys (entry bits with the low five cleared | leaf id:
+// non-negative floats order as unsigned integers, and lowering an entry only
+// culls less) and the other hit leaves as a bit mask.  Phase 2 tests the
+// nearest leaf, the second if its entry is within h.t (1 + 2^-11), then the
+// masked ones, lowest id first, each culled by its recomputed entry under the
+// same rule.  The leaves tested are among those whose boxes the ray hits, and
+// a leaf left out lies behind h.t by more than the walk's own slack, so the
+// answer is the walk's: the minimum of (t, prim) over the box-hit leaves'
+// triangles, independent of the order (§3.1).
+__device__ __forceinline__ bool sweep_box(float4 lo, float4 hi, V3 o, const RayBox& rb, float tmin, float& tnear) {
+#if MRT_PRECISE
+  const float ox = o.x, oy = o.y, oz = o.z, oix = 0.0f, oiy = 0.0f, oiz = 0.0f;
+#else
+  const float ox = 0.0f, oy = 0.0f, oz = 0.0f, oix = rb.oinv.x, oiy = rb.oinv.y, oiz = rb.oinv.z;
+  (void)o;
+#endif
+  // slab distances are monotone in the plane coordinate: min / max of the
+  // pair are the (near, far) planes box4 reads from the ray's quadrant copy
+  const float x0 = slab(lo.x, ox, rb.inv.x, oix), x1 = slab(hi.x, ox, rb.inv.x, oix);
+  const float y0 = slab(lo.y, oy, rb.inv.y, oiy), y1 = slab(hi.y, oy, rb.inv.y, oiy);
+  const float z0 = slab(lo.z, oz, rb.inv.z, oiz), z1 = slab(hi.z, oz, rb.inv.z, oiz);
+  tnear = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin));
+  const float tfar = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
+  return tnear <= tfar;
+}
+
+typedef float SweepRec __attribute__((ext_vector_type(8)));           // one leaf record
+typedef const __attribute__((address_space(4))) SweepRec* SweepList;   // constant address space: scalar loads
+
+template <int MODE>
+__device__ __forceinline__ void sweep_leaf(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
+                                           uint32_t ref, Hit& h) {
+  LS_ADD(4, 1);
+  LS_ADD(5, ls_lanes());
+  const uint32_t lr = ~ref;
+  leaf_tests<MODE>(sc, cx, o, d, tmin, lr >> kLeafCountBits, (lr & (kMaxLeafSize - 1)) + 1, h, false, 0u, nullptr);
+}
+
+template <int MODE>
+__device__ __forceinline__ void sweep_nearest(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
+                                              Hit& h) {
+  const RayBox rb = make_raybox(o, d);
+  LS_ADD(0, ls_lanes());
+  LS_ADD(1, 1);
+  constexpr uint32_t kNone = 0xFFFFFFFFu;
+  uint32_t k1 = kNone, k2 = kNone, rest = 0u;   // rest: in phase 1 every leaf hit, then those beyond the pair
+  const uint32_t n = sc.sweep_leaves;
+  const SweepList list = (SweepList)(uintptr_t)sc.sweep;
+  for (uint32_t i = 0; i < n; ++i) {
+    // (no record loaded ahead: the eight more scalar registers of a second
+    // record cost the stream kernel scalar spills inside this loop, and the
+    // other resident waves cover the load: measured)
+    const SweepRec rec = list[i];
+    float te;
+    const bool hit = sweep_box(make_float4(rec[0], rec[1], rec[2], rec[3]), make_float4(rec[4], rec[5], rec[6], rec[7]),
+                               o, rb, tmin, te);
+    // one v_bfi: entry bits above the leaf id (an entry of -0 sorts last and is never culled: still exact)
+    const uint32_t key = hit ? ((fbits(te) & ~31u) | (i & 31u)) : kNone;
+    const uint32_t mid = max(k1, key);
+    k1 = min(k1, key);
+    k2 = min(k2, mid);
+    rest |= (hit ? 1u : 0u) << (i & 31u);
+  }
+  // the pair's leaves leave the mask (a lone hit: k2 is kNone, whose id bits name leaf 31 — not set, or k1's own)
+  rest &= ~((1u << (k1 & 31u)) | (1u << (k2 & 31u)));
+  if (k1 != kNone) sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(g_lds[cx.sweep_base + 2u * (k1 & 31u)].w), h);
+  if (k2 != kNone && bitsf(k2 & ~31u) <= h.t * kCullScale)
+    sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(g_lds[cx.sweep_base + 2u * (k2 & 31u)].w), h);
+  while (rest) {
+    LS_ADD(30, 1);
+    LS_ADD(31, ls_lanes());
+    const uint32_t id = (uint32_t)__ffs((int)rest) - 1u;
+    rest &= rest - 1u;
+    const float4 blo = g_lds[cx.sweep_base + 2u * id], bhi = g_lds[cx.sweep_base + 2u * id + 1u];
+    float te;
+    if (sweep_box(blo, bhi, o, rb, tmin, te) && te <= h.t * kCullScale)
+      sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(blo.w), h);
+  }
+}
+
 template <int STACK, int MODE>
 __device__ __forceinline__ Hit trace_nearest(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
                                              float tmax) {
@@ -751,6 +844,10 @@ __device__ __forceinline__ Hit trace_nearest(const DeviceScene& sc, const LdsCtx
   h.u = h.v = 0.0f;
   h.prim = 0xFFFFFFFFu;
   h.found = false;
+  if (MODE == kAllLds && sc.sweep_leaves) {   // wave-uniform (kernel argument)
+    sweep_nearest<MODE>(sc, cx, o, d, tmin, h);
+    return h;
+  }
   traverse<STACK, MODE, false>(sc, cx, o, d, tmin, h, 0u, sc.root);
   return h;
 }

@@ -147,7 +147,18 @@ struct DeviceScene {
   uint32_t conv_count;
   float conv_obb[4][16];             // [kMaxConvex]
   uint32_t conv_face_tris[4][8];
+  // leaf-box sweep (kernels.hip sweep_nearest): nearest queries of a
+  // whole-scene-in-LDS tree with at most kSweepLeaves leaves test every leaf
+  // box instead of walking the tree.  sweep = float4 x 2 per leaf of the main
+  // tree, interior nodes in index order and their slots in slot order:
+  // (lo.xyz, bits(leaf ref)), (hi.xyz, 0) — the padded child box as it stands
+  // in the leaf's parent node; a leaf's id is its position in the list.
+  // sweep_leaves == 0: the queries walk.  Last, so that no other field moves.
+  const float* sweep;
+  uint32_t sweep_leaves;
 };
+// a leaf id fits 5 bits and a lane's set of leaves one 32-bit mask
+constexpr uint32_t kSweepLeaves = 32;
 constexpr uint32_t kMaxOccPlanes = 8;
 // convex occluders (DeviceScene::conv_*): at most this many solids, and the
 // least d . n (n: the outward normal of the face a shadow ray starts on) for

@@ -117,6 +117,12 @@ struct mrt_scene {
   int32_t occ_root = 0;
   uint32_t occ_node_base = 0, occ_max_stack = 0;
   DevBuf nodes, tris, prims, materials, lights;
+  // leaf-box sweep (mrt_layout.h DeviceScene::sweep): the main tree's leaf
+  // records, 8 floats each (empty for a tree over kSweepLeaves leaves or a
+  // leaf root), and whether nearest queries use them
+  std::vector<float> sweep_list;
+  bool sweep_on = false;
+  DevBuf sweep;
   mrt::DeviceScene dev{};
   mrt_scene_info info{};
 };
@@ -1145,6 +1151,35 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
     for (size_t k = 0; k < occ.planes.size() && k < 8; ++k)
       for (int c = 0; c < 4; ++c) in.occluder_plane[k][c] = occ.planes[k][c];
   }
+  // leaf-box sweep: one record per leaf of the main tree, in node and slot
+  // order, with the child box as the parent node holds it.  Eligible: at most
+  // kSweepLeaves leaves under an interior root, and the scene still staged
+  // whole in LDS with the records added (MRT_SWEEP=0: the walk)
+  if (s->bvh.root >= 0 && s->bvh.num_leaves <= mrt::kSweepLeaves) {
+    for (uint32_t k = 0; k < s->bvh.num_nodes; ++k) {
+      const float* nd = &s->bvh.nodes[32 * (size_t)k];
+      for (int c = 0; c < 4; ++c)
+        if ((int32_t)fbits(nd[24 + c]) < 0)
+          s->sweep_list.insert(s->sweep_list.end(), {nd[c], nd[8 + c], nd[16 + c], nd[24 + c],
+                                                     nd[4 + c], nd[12 + c], nd[20 + c], 0.0f});
+    }
+  }
+  const uint32_t sweep_leaves = (uint32_t)(s->sweep_list.size() / 8);
+  const uint32_t up_occ_nodes = occ_on ? (uint32_t)(up_nodes.size() / 32) - s->bvh.num_nodes : 0u;
+  if (sweep_leaves >= 1 && sweep_leaves <= mrt::kSweepLeaves && s->bvh.width == 4) {
+    mrt::DeviceScene probe{};   // the counts the staging mode is chosen by
+    probe.num_nodes = s->bvh.num_nodes;
+    probe.num_triangles = T;
+    probe.num_materials = (uint32_t)h.materials.size();
+    probe.num_lights = h.light_count;
+    probe.lds_nodes = s->bvh.lds_nodes;
+    probe.width = s->bvh.width;
+    probe.occ_nodes = up_occ_nodes;
+    probe.occ_tris = occ_on ? (uint32_t)occ.keep.size() : 0u;
+    probe.sweep_leaves = sweep_leaves;
+    s->sweep_on = !mrt::fast::path_preferred(probe);
+  }
+  if (const char* v = mrt::diag_env("MRT_SWEEP")) s->sweep_on = s->sweep_on && std::atoi(v) != 0;
   in.vertices = (uint32_t)h.vertices.size();
   in.triangles = T;
   in.materials = (uint32_t)h.materials.size();
@@ -1200,7 +1235,7 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
   d.occ_lights = 0;
   if (occ_on) {
     d.occ_lights = occ_lights ? 1u : 0u;
-    d.occ_nodes = (uint32_t)(up_nodes.size() / 32) - s->bvh.num_nodes;   // (a leaf-root main tree keeps one dummy node)
+    d.occ_nodes = up_occ_nodes;   // (a leaf-root main tree keeps one dummy node)
     d.occ_tris = (uint32_t)occ.keep.size();
     d.occ_planes = (uint32_t)occ.planes.size();
     d.occ_margin = occ.margin;
@@ -1213,8 +1248,16 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
   d.conv_count = in.convex_solids;
   std::memcpy(d.conv_obb, in.convex_obb, sizeof(d.conv_obb));
   std::memcpy(d.conv_face_tris, in.convex_face_tris, sizeof(d.conv_face_tris));
+  d.sweep = nullptr;
+  d.sweep_leaves = 0;
+  if (s->sweep_on) {
+    HIP_TRY(upload(s->sweep, s->sweep_list.data(), s->sweep_list.size() * 4));
+    d.sweep = s->sweep.as<float>();
+    d.sweep_leaves = sweep_leaves;
+  }
   HIP_TRY(alloc_isect_spill(s->isect_spill, d.max_stack));
-  in.device_bytes = s->nodes.bytes + s->tris.bytes + s->prims.bytes + s->materials.bytes + s->lights.bytes;
+  in.device_bytes = s->nodes.bytes + s->tris.bytes + s->prims.bytes + s->materials.bytes + s->lights.bytes +
+                    s->sweep.bytes;
   *out = s.release();
   return MRT_OK;
 }
@@ -1222,6 +1265,24 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
 int mrt_scene_info_get(const mrt_scene* scene, mrt_scene_info* info) {
   if (!scene || !info) return fail(MRT_ERR_INVALID, "null argument");
   *info = scene->info;
+  return MRT_OK;
+}
+
+int mrt_debug_sweep_list(const mrt_scene* scene, float* records, uint32_t capacity, uint32_t* count,
+                         uint32_t* enabled) {
+  if (!scene || !count || !enabled) return fail(MRT_ERR_INVALID, "mrt_debug_sweep_list: null argument");
+  const uint32_t n = (uint32_t)(scene->sweep_list.size() / 8);
+  if (records) std::memcpy(records, scene->sweep_list.data(), (size_t)std::min(n, capacity) * 32);
+  *count = n;
+  *enabled = scene->sweep_on ? 1u : 0u;
+  return MRT_OK;
+}
+
+int mrt_debug_bvh_nodes(const mrt_scene* scene, float* nodes, uint32_t capacity, uint32_t* count) {
+  if (!scene || !count) return fail(MRT_ERR_INVALID, "mrt_debug_bvh_nodes: null argument");
+  const uint32_t n = scene->bvh.num_nodes;
+  if (nodes) std::memcpy(nodes, scene->bvh.nodes.data(), (size_t)std::min(n, capacity) * 128);
+  *count = n;
   return MRT_OK;
 }
 

@@ -232,7 +232,7 @@ EXPORTED = [
     "mrt_renderer_exchange_flush", "mrt_renderer_tiles_read", "mrt_renderer_tiles_write",
     "mrt_image_load_exr", "mrt_renderer_load_reference", "mrt_renderer_display",
     "mrt_renderer_display_enqueue", "mrt_renderer_display_map",
-    "mrt_debug_lanes", "mrt_debug_exchange_unpack", "mrt_debug_box_margin",
+    "mrt_debug_lanes", "mrt_debug_sweep_list", "mrt_debug_bvh_nodes", "mrt_debug_exchange_unpack", "mrt_debug_box_margin",
     "mrt_debug_magic_div", "mrt_comm_set_timeout", "mrt_comm_check", "mrt_debug_comm_fail",
     "mrt_camera_default", "mrt_camera_look_at", "mrt_camera_check", "mrt_raygen_camera",
     "mrt_renderer_set_camera", "mrt_renderer_get_camera",
@@ -295,6 +295,8 @@ def lib() -> ctypes.CDLL:
         "mrt_debug_stamps": [vp, c_int],
         "mrt_debug_wave_times": [vp, ctypes.c_size_t],
         "mrt_debug_lanes": [vp, ctypes.c_size_t, c_int],
+        "mrt_debug_sweep_list": [vp, vp, u32, vp, vp],
+        "mrt_debug_bvh_nodes": [vp, vp, u32, vp],
         "mrt_debug_exchange_unpack": [vp, u32, vp, ctypes.c_size_t],
         "mrt_debug_box_margin": [vp, vp, u32, u32, vp, vp],
         "mrt_debug_magic_div": [u32, vp, u32, vp],
@@ -915,6 +917,29 @@ def debug_lanes(reset: bool = True):
     out = np.zeros(64, np.uint64)
     _check(lib().mrt_debug_lanes(ctypes.c_void_p(out.ctypes.data), out.size, int(reset)), "mrt_debug_lanes")
     return out
+
+
+def debug_sweep_list(scene: "Scene"):
+    """(enabled, records) of the scene's leaf-box sweep list (test entry):
+    records is an (n, 8) uint32 view of the float records (lo.xyz, leaf ref,
+    hi.xyz, 0), empty for a tree the sweep cannot take; enabled tells whether
+    nearest queries sweep it instead of walking the tree."""
+    import numpy as np
+    out = np.zeros((32, 8), np.uint32)
+    count, enabled = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(lib().mrt_debug_sweep_list(scene.handle, ctypes.c_void_p(out.ctypes.data), len(out), ctypes.byref(count),
+                                      ctypes.byref(enabled)), "mrt_debug_sweep_list")
+    return bool(enabled.value), out[:min(count.value, len(out))].copy()
+
+
+def debug_bvh_nodes(scene: "Scene"):
+    """The main tree's BVH4 nodes as an (n, 32) uint32 array (test entry)."""
+    import numpy as np
+    out = np.zeros((scene.info["bvh_nodes"], 32), np.uint32)
+    count = ctypes.c_uint32()
+    _check(lib().mrt_debug_bvh_nodes(scene.handle, ctypes.c_void_p(out.ctypes.data), len(out), ctypes.byref(count)),
+           "mrt_debug_bvh_nodes")
+    return out[:count.value]
 
 
 def debug_wave_times():

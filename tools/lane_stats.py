@@ -26,7 +26,7 @@ NAMES = ["near_lanes", "near_calls", "near_int_iters", "near_int_lanes", "near_l
          "shade_calls", "shade_lanes", "wave_calls", "wave_active", "shadow_rays", "shadow_calls",
          "list_calls", "list_lanes", "svc_rounds", "svc_lanes", "trav_rounds", "trav_lanes", "refill_lanes",
          "outer_iters", "stream_camera_iters", "stream_level_iters", "stream_queue_wait_cycles",
-         "stream_queue_waits"]
+         "stream_queue_waits", "sweep_cull_rounds", "sweep_cull_lanes"]
 
 
 def main():
@@ -73,6 +73,9 @@ def main():
             out[f"{q}_leaf_steps_per_ray"] = round(c[f"{q}_leaf_lanes"] / max(1, c[f"{q}_lanes"]), 3)
             out[f"{q}_int_iters_per_call"] = round(c[f"{q}_int_iters"] / max(1, c[f"{q}_calls"]), 3)
             out[f"{q}_leaf_iters_per_call"] = round(c[f"{q}_leaf_iters"] / max(1, c[f"{q}_calls"]), 3)
+        if c.get("sweep_cull_rounds"):   # leaf-box sweep: the masked leaves' pop-and-cull rounds
+            out["sweep_cull_rounds_per_call"] = round(c["sweep_cull_rounds"] / max(1, c["near_calls"]), 3)
+            out["sweep_cull_util"] = util(c["sweep_cull_lanes"], c["sweep_cull_rounds"])
         out["wave_entry_util"] = util(c["wave_active"], c["wave_calls"])
         out["shade_util"] = util(c["shade_lanes"], c["shade_calls"])
         out["shadow_phase_util"] = util(c["shadow_rays"], c["shadow_calls"])

@@ -1,0 +1,423 @@
+// walk_model — CPU model of the stream kernel's nearest-hit queries on a small
+// all-in-LDS scene (C2: the Cornell box), to count what a 64-lane wave spends
+// in the while-while walk (kernels.hip traverse) and what other query shapes
+// would spend on the same rays in the same waves.
+//
+// Builds the product tree (scene.cpp, bvh.cpp, the options mrt_scene_create
+// uses), generates paths of L = 4 bounces — camera rays of 8x8 pixel blocks
+// from the reference's camera, then cosine-distributed directions about the
+// hit triangle's normal (a diffuse stand-in for the shader: the ray
+// distribution is close to, not equal to, the renderer's) — and groups them
+// into waves by the stream kernel's wave-local queue policy: the deepest
+// bounce level holding 64 rays runs, else 64 new camera rays; the queues'
+// remainders run as partial waves at the end.  Binned by octant, either a
+// level holding 64 rays runs its fullest bin (its 128 slots cannot wait for
+// more), or every bin waits for a whole wave (eight times the slots).  Bounce 0 (candidate lists)
+// and the last bounce (light shortcut) are not walks in the product and are
+// not counted; bounces 1 and 2 are.
+//
+// Every query is answered by a lock-step restatement of traverse() /
+// interior_step() / leaf_tests() in the precise build's arithmetic, and:
+//   1. with each level's queue binned by ray-direction octant;
+//   2. by leaves in order of box entry, culled against the hit so far (the
+//      order an ideal walk would have), and by the walk with a full child sort;
+//   3. by the two-phase sweep (sweep_nearest): all leaf boxes, the two nearest
+//      kept as keys and the rest as a mask, then entry-ordered leaf tests.
+// The sweep's (found, t, prim) is compared with the walk's for every ray.
+//
+// build (in tools/): g++ -O2 -std=c++17 -ffp-contract=off -I../metal-renderer_amd/csrc walk_model.cpp
+//        ../metal-renderer_amd/csrc/{scene,bvh}.cpp -o walk_model -lpthread
+// usage: walk_model <scene.obj> [camera blocks = 2000]
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "bvh.h"
+#include "scene.h"
+
+using namespace mrt;
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int32_t kDone = 0x7FFFFFFF;
+constexpr float kCull = 1.0f + 0x1p-11f;
+const float kInf = INFINITY;
+
+uint32_t fb(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+float bf(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+
+struct Ray { float o[3], d[3]; };
+struct Hit { bool found = false; float t = INFINITY; uint32_t prim = 0xFFFFFFFFu; };
+
+BvhResult g_bvh;
+std::vector<float> g_sweep;   // 8 floats per leaf, as mrt_scene_create builds them
+
+float safe_inv(float d) { return 1.0f / (std::fabs(d) > 1e-20f ? d : std::copysign(1e-20f, d)); }
+float tdot(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+void tcross(const float* a, const float* b, float* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// kernels.hip tri_bary + tri_pair's acceptance (nearest; ties -> lowest primitive)
+void tri_test(const Ray& r, uint32_t k, Hit& h) {
+  const float* T = &g_bvh.tris[12 * (size_t)k];
+  float p[3], s[3], q[3];
+  tcross(r.d, T + 8, p);
+  const float det = tdot(T + 4, p), inv = 1.0f / det;
+  for (int a = 0; a < 3; ++a) s[a] = r.o[a] - T[a];
+  const float b1 = tdot(s, p) * inv;
+  tcross(s, T + 4, q);
+  const float b2 = tdot(r.d, q) * inv, t = tdot(T + 8, q) * inv;
+  const bool ok = (det != 0.0f) & (b1 >= 0.0f) & (b1 <= 1.0f) & (b2 >= 0.0f) & (b1 + b2 <= 1.0f);
+  const uint32_t prim = fb(T[3]);
+  if (ok && t >= 0.0f && t <= h.t && (!h.found || t < h.t || prim < h.prim)) {
+    h.found = true;
+    h.t = t;
+    h.prim = prim;
+  }
+}
+void leaf_test(const Ray& r, int32_t leaf, Hit& h) {
+  const uint32_t lr = ~(uint32_t)leaf, first = lr >> kLeafCountBits, cnt = (lr & (kMaxLeafSize - 1)) + 1;
+  for (uint32_t k = 0; k < cnt; ++k) tri_test(r, first + k, h);
+}
+
+// box entry (tmin = 0) of (lo, hi) by the precise build's slab arithmetic; false: missed
+bool box_entry(const Ray& r, const float* inv, const float* lo, const float* hi, float& tn) {
+  float n[3], f[3];
+  for (int a = 0; a < 3; ++a) {
+    const float t0 = (lo[a] - r.o[a]) * inv[a], t1 = (hi[a] - r.o[a]) * inv[a];
+    n[a] = std::fmin(t0, t1);
+    f[a] = std::fmax(t0, t1);
+  }
+  tn = std::fmax(std::fmax(n[0], n[1]), std::fmax(n[2], 0.0f));
+  return tn <= std::fmin(std::fmin(f[0], f[1]), f[2]);
+}
+
+struct WalkStats {
+  double calls = 0, rays = 0, int_iter = 0, int_steps = 0, leaf_iter = 0, leaf_steps = 0;
+  void print(const char* what) const {
+    std::printf("%s: %.0f wave calls, %.1f lanes; interior %.2f iterations/call, %.2f steps/ray, utilisation %.3f; "
+                "leaf %.2f iterations/call, %.2f steps/ray, utilisation %.3f\n",
+                what, calls, rays / calls, int_iter / calls, int_steps / rays, int_steps / (64.0 * int_iter),
+                leaf_iter / calls, leaf_steps / rays, leaf_steps / (64.0 * leaf_iter));
+  }
+};
+
+// traverse<STACK, kAllLds, false> for one wave, lanes in lock step
+void walk_wave(const Ray* rays, int n, Hit* out, WalkStats& st, bool full_sort) {
+  struct Lane { int32_t node, leaf; int sp; int32_t stack[64]; float inv[3]; Hit h; };
+  static Lane L[kWave];
+  for (int l = 0; l < n; ++l) {
+    L[l].node = g_bvh.root; L[l].leaf = 0; L[l].sp = 0; L[l].h = Hit();
+    for (int a = 0; a < 3; ++a) L[l].inv[a] = safe_inv(rays[l].d[a]);
+    if (L[l].node < 0) { L[l].leaf = L[l].node; L[l].node = kDone; }
+  }
+  st.calls += 1;
+  st.rays += n;
+  auto pop = [](Lane& x) { const int32_t v = x.sp > 0 ? x.stack[x.sp - 1] : kDone; x.sp = std::max(x.sp - 1, 0); return v; };
+  auto interior = [&](Lane& x, const Ray& r) {
+    const float* nd = &g_bvh.nodes[32 * (size_t)x.node];
+    float t[4]; int32_t c[4];
+    const float tmax = x.h.t * kCull;
+    for (int k = 0; k < 4; ++k) {
+      const float lo[3] = {nd[k], nd[8 + k], nd[16 + k]}, hi[3] = {nd[4 + k], nd[12 + k], nd[20 + k]};
+      float tn;
+      c[k] = (int32_t)fb(nd[24 + k]);
+      t[k] = (c[k] != kEmptyChild && box_entry(r, x.inv, lo, hi, tn) && tn <= tmax) ? tn : kInf;
+    }
+    auto ce = [&](int i, int j) { if (t[j] < t[i]) { std::swap(t[i], t[j]); std::swap(c[i], c[j]); } };
+    if (full_sort) { ce(0, 1); ce(2, 3); ce(0, 2); ce(1, 3); ce(1, 2); }
+    else { ce(0, 1); ce(0, 2); ce(0, 3); }
+    for (int k = 3; k >= 1; --k) if (t[k] < kInf) x.stack[x.sp++] = c[k];
+    return t[0] < kInf ? c[0] : pop(x);
+  };
+  for (;;) {
+    bool any = false, in[kWave];
+    for (int l = 0; l < n; ++l) any |= L[l].node != kDone || L[l].leaf != 0;
+    if (!any) break;
+    for (int l = 0; l < n; ++l) in[l] = L[l].node != kDone && L[l].node >= 0;
+    for (;;) {
+      int act = 0;
+      for (int l = 0; l < n; ++l) act += in[l];
+      if (!act) break;
+      st.int_iter += 1;
+      st.int_steps += act;
+      bool seeking = false;
+      for (int l = 0; l < n; ++l) if (in[l]) {
+        Lane& x = L[l];
+        x.node = interior(x, rays[l]);
+        if (x.node < 0 && x.leaf == 0) { x.leaf = x.node; x.node = pop(x); }
+        seeking |= x.leaf == 0;
+      }
+      if (!seeking) break;   // every lane in the loop holds a leaf
+      for (int l = 0; l < n; ++l) in[l] = in[l] && L[l].node != kDone && L[l].node >= 0;
+    }
+    for (;;) {
+      int act = 0;
+      for (int l = 0; l < n; ++l) act += L[l].leaf < 0;
+      if (!act) break;
+      st.leaf_iter += 1;
+      st.leaf_steps += act;
+      for (int l = 0; l < n; ++l) if (L[l].leaf < 0) {
+        Lane& x = L[l];
+        leaf_test(rays[l], x.leaf, x.h);
+        x.leaf = 0;
+        if (x.node < 0) { x.leaf = x.node; x.node = pop(x); }
+      }
+    }
+  }
+  for (int l = 0; l < n; ++l) out[l] = L[l].h;
+}
+
+struct SweepStats { double calls = 0, rays = 0, tests[3] = {0, 0, 0}, rounds = 0, mismatches = 0; };
+
+// sweep_nearest for one wave
+void sweep_wave(const Ray* rays, int n, Hit* out, SweepStats& st) {
+  const uint32_t N = (uint32_t)(g_sweep.size() / 8), kNone = 0xFFFFFFFFu;
+  uint32_t k1[kWave], k2[kWave], rest[kWave];
+  float inv[kWave][3];
+  st.calls += 1;
+  st.rays += n;
+  for (int l = 0; l < n; ++l) {
+    k1[l] = k2[l] = kNone; rest[l] = 0; out[l] = Hit();
+    for (int a = 0; a < 3; ++a) inv[l][a] = safe_inv(rays[l].d[a]);
+    for (uint32_t i = 0; i < N; ++i) {
+      float te;
+      const bool hit = box_entry(rays[l], inv[l], &g_sweep[8 * i], &g_sweep[8 * i + 4], te);
+      const uint32_t key = hit ? ((fb(te) & ~31u) | i) : kNone;
+      const uint32_t mid = std::max(k1[l], key);
+      k1[l] = std::min(k1[l], key);
+      k2[l] = std::min(k2[l], mid);
+      if (hit) rest[l] |= 1u << i;
+    }
+    rest[l] &= ~((1u << (k1[l] & 31u)) | (1u << (k2[l] & 31u)));
+  }
+  auto ref = [&](uint32_t id) { return (int32_t)fb(g_sweep[8 * id + 3]); };
+  bool any = false;
+  for (int l = 0; l < n; ++l) if (k1[l] != kNone) { any = true; leaf_test(rays[l], ref(k1[l] & 31u), out[l]); }
+  st.tests[0] += any;
+  any = false;
+  for (int l = 0; l < n; ++l)
+    if (k2[l] != kNone && bf(k2[l] & ~31u) <= out[l].t * kCull) { any = true; leaf_test(rays[l], ref(k2[l] & 31u), out[l]); }
+  st.tests[1] += any;
+  for (;;) {
+    bool more = false;
+    any = false;
+    for (int l = 0; l < n; ++l) if (rest[l]) {
+      more = true;
+      const uint32_t id = (uint32_t)__builtin_ctz(rest[l]);
+      rest[l] &= rest[l] - 1;
+      float te;
+      if (box_entry(rays[l], inv[l], &g_sweep[8 * id], &g_sweep[8 * id + 4], te) && te <= out[l].t * kCull) {
+        any = true;
+        leaf_test(rays[l], ref(id), out[l]);
+      }
+    }
+    if (!more) break;
+    st.rounds += 1;
+    st.tests[2] += any;
+  }
+}
+
+// leaves in order of box entry, culled against the hit so far: tests per ray,
+// and the leaf boxes hit with no culling at all
+struct OrderStats { double rays = 0, waves = 0, tests = 0, wave_max = 0, boxes = 0; };
+void ordered_wave(const Ray* rays, int n, OrderStats& st) {
+  const uint32_t N = (uint32_t)(g_sweep.size() / 8);
+  int mx = 0;
+  for (int l = 0; l < n; ++l) {
+    float inv[3];
+    for (int a = 0; a < 3; ++a) inv[a] = safe_inv(rays[l].d[a]);
+    std::vector<std::pair<float, uint32_t>> c;
+    for (uint32_t i = 0; i < N; ++i) {
+      float te;
+      if (box_entry(rays[l], inv, &g_sweep[8 * i], &g_sweep[8 * i + 4], te)) c.push_back({te, i});
+    }
+    std::sort(c.begin(), c.end());
+    Hit h;
+    int tests = 0;
+    for (auto& e : c) {
+      if (!(e.first <= h.t * kCull)) break;
+      leaf_test(rays[l], (int32_t)fb(g_sweep[8 * e.second + 3]), h);
+      ++tests;
+    }
+    st.tests += tests;
+    st.boxes += (double)c.size();
+    mx = std::max(mx, tests);
+  }
+  st.rays += n;
+  st.waves += 1;
+  st.wave_max += mx;
+}
+
+uint64_t g_rng = 0x9E3779B97F4A7C15ull;
+float rnd() {
+  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
+  return (float)((g_rng >> 40) * (1.0 / 16777216.0));
+}
+
+// the next ray of a path: a cosine-distributed direction about the hit triangle's normal
+bool bounce(const Ray& r, const Hit& h, const HostScene& sc, Ray& next) {
+  if (!h.found || h.t < kDistanceEpsilon) return false;
+  const RefTriangleReference& tr = sc.references[h.prim];
+  const float *v0 = sc.vertices[tr.tri[0]].v, *v1 = sc.vertices[tr.tri[1]].v, *v2 = sc.vertices[tr.tri[2]].v;
+  float e1[3], e2[3], nrm[3];
+  for (int a = 0; a < 3; ++a) { e1[a] = v1[a] - v0[a]; e2[a] = v2[a] - v0[a]; }
+  tcross(e1, e2, nrm);
+  const float len = std::sqrt(tdot(nrm, nrm));
+  if (!(len > 0.0f)) return false;
+  const float flip = tdot(nrm, r.d) > 0.0f ? -1.0f : 1.0f;
+  for (int a = 0; a < 3; ++a) nrm[a] *= flip / len;
+  float t1[3] = {0, 0, 0}, t2[3];
+  t1[std::fabs(nrm[0]) < 0.5f ? 0 : 1] = 1.0f;
+  tcross(nrm, t1, t2);
+  const float l2 = std::sqrt(tdot(t2, t2));
+  for (int a = 0; a < 3; ++a) t2[a] /= l2;
+  tcross(t2, nrm, t1);
+  const float u = rnd(), phi = 2.0f * kPi * rnd(), rr = std::sqrt(u), z = std::sqrt(1.0f - u);
+  for (int a = 0; a < 3; ++a) {
+    next.o[a] = r.o[a] + r.d[a] * h.t + nrm[a] * kDistanceEpsilon;
+    next.d[a] = t1[a] * (rr * std::cos(phi)) + t2[a] * (rr * std::sin(phi)) + nrm[a] * z;
+  }
+  return true;
+}
+
+Hit brute(const Ray& r) {
+  Hit h;
+  for (uint32_t k = 0; k < (uint32_t)(g_bvh.tris.size() / 12); ++k) tri_test(r, k, h);
+  return h;
+}
+
+struct Totals {
+  WalkStats walk, sorted;
+  SweepStats sweep;
+  OrderStats ordered;
+};
+
+// one wave of bounce-`level` rays: every query shape on the same rays
+void run_wave(const std::vector<Ray>& w, Totals& T, Hit* hits, bool stats_only_walk) {
+  const int n = (int)w.size();
+  walk_wave(w.data(), n, hits, T.walk, false);
+  if (stats_only_walk) return;
+  Hit tmp[kWave];
+  walk_wave(w.data(), n, tmp, T.sorted, true);
+  ordered_wave(w.data(), n, T.ordered);
+  sweep_wave(w.data(), n, tmp, T.sweep);
+  for (int l = 0; l < n; ++l)
+    T.sweep.mismatches += tmp[l].found != hits[l].found || (tmp[l].found && (fb(tmp[l].t) != fb(hits[l].t) || tmp[l].prim != hits[l].prim));
+}
+
+// the wave-local queue policy over `blocks` camera blocks; bins = 1 or 8 (octant)
+// bounded: today's 128 slots per level; else a bin waits until it holds a whole wave (8 x the slots)
+void simulate(const HostScene& sc, int blocks, int bins, bool bounded, Totals& T) {
+  constexpr int kLevels = 2;   // bounces 1 and 2 walk (L = 4)
+  std::vector<Ray> q[kLevels][8];
+  g_rng = 0x9E3779B97F4A7C15ull;
+  Hit hits[kWave];
+  auto bin_of = [&](const Ray& r) {
+    return bins == 1 ? 0 : (int)((fb(r.d[0]) >> 31) | ((fb(r.d[1]) >> 31) << 1) | ((fb(r.d[2]) >> 31) << 2));
+  };
+  auto run = [&](int lvl, int b, size_t count) {
+    std::vector<Ray>& Q = q[lvl][b];
+    std::vector<Ray> w(Q.end() - (long)count, Q.end());
+    Q.resize(Q.size() - count);
+    run_wave(w, T, hits, bins != 1);
+    if (lvl + 1 < kLevels)
+      for (size_t l = 0; l < w.size(); ++l) {
+        Ray nx;
+        if (bounce(w[l], hits[l], sc, nx)) q[lvl + 1][bin_of(nx)].push_back(nx);
+      }
+  };
+  // a level holding 64 rays runs (its slots, kStreamCap = 128 per level, leave
+  // no room to wait for more): binned, its fullest bin, as a partial wave if need be
+  auto deepest_full = [&](int& lvl, int& b) {
+    for (lvl = kLevels - 1; lvl >= 0; --lvl) {
+      size_t total = 0;
+      b = 0;
+      for (int k = 0; k < bins; ++k) {
+        total += q[lvl][k].size();
+        if (q[lvl][k].size() > q[lvl][b].size()) b = k;
+      }
+      if (bounded ? total >= (size_t)kWave : q[lvl][b].size() >= (size_t)kWave) return true;
+    }
+    return false;
+  };
+  const int bx = 240;   // 1080p: 240 x 135 blocks of 8 x 8 pixels
+  for (int blk = 0; blk < blocks;) {
+    int lvl, b;
+    if (deepest_full(lvl, b)) { run(lvl, b, std::min<size_t>(kWave, q[lvl][b].size())); continue; }
+    // camera rays of one block, spread over the frame (rayGenerator's pinhole, no jitter)
+    const int bi = (int)(((long long)blk * 32400) / blocks), px = (bi % bx) * 8, py = (bi / bx) * 8;
+    ++blk;
+    for (int i = 0; i < kWave; ++i) {
+      const float x = ((float)(px + i % 8) + rnd()) / 1920.0f * 2.0f - 1.0f;
+      const float y = ((float)(py + i / 8) + rnd()) / 1080.0f * 2.0f - 1.0f;
+      Ray r;
+      r.o[0] = kCameraX; r.o[1] = kCameraY; r.o[2] = kCameraZ;
+      const float d[3] = {x * (1920.0f / 1080.0f) * 0.4f, y * 0.4f, -1.0f}, len = std::sqrt(tdot(d, d));
+      for (int a = 0; a < 3; ++a) r.d[a] = d[a] / len;
+      Ray nx;
+      if (bounce(r, brute(r), sc, nx)) q[0][bin_of(nx)].push_back(nx);
+    }
+  }
+  for (int lvl = 0; lvl < kLevels; ++lvl)   // the remainders: partial waves
+    for (int b = 0; b < bins; ++b)
+      while (!q[lvl][b].empty()) run(lvl, b, std::min<size_t>(kWave, q[lvl][b].size()));
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc < 2) { std::fprintf(stderr, "usage: walk_model <scene.obj> [camera blocks]\n"); return 1; }
+  const int blocks = argc > 2 ? std::max(1, std::atoi(argv[2])) : 2000;
+  HostScene sc;
+  std::string err;
+  if (!import_obj(argv[1], "", sc, err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+  flatten(sc);
+  BvhBuildOptions opt;   // mrt_scene_create for a small scene
+  opt.width = 4;
+  opt.lds_node_budget = 256;
+  if (!build_bvh(sc.vertices.data()->v, sizeof(RefVertex), sc.indices.data(), (uint32_t)sc.references.size(), opt, g_bvh,
+                 err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+  if (g_bvh.root < 0 || g_bvh.num_leaves > kSweepLeaves) {
+    std::fprintf(stderr, "the tree has %u leaves: the sweep takes at most %u under an interior root\n", g_bvh.num_leaves,
+                 kSweepLeaves);
+    return 1;
+  }
+  for (uint32_t k = 0; k < g_bvh.num_nodes; ++k) {   // the sweep list, as mrt_scene_create builds it
+    const float* nd = &g_bvh.nodes[32 * (size_t)k];
+    for (int c = 0; c < 4; ++c)
+      if ((int32_t)fb(nd[24 + c]) < 0)
+        g_sweep.insert(g_sweep.end(), {nd[c], nd[8 + c], nd[16 + c], nd[24 + c], nd[4 + c], nd[12 + c], nd[20 + c], 0.0f});
+  }
+  std::printf("%zu triangles, %u nodes, %u leaves, %d camera blocks\n", sc.references.size(), g_bvh.num_nodes,
+              g_bvh.num_leaves, blocks);
+  Totals T, B[2];
+  simulate(sc, blocks, 1, true, T);
+  T.walk.print("walk");
+  for (int k = 0; k < 2; ++k) {
+    simulate(sc, blocks, 8, k == 0, B[k]);
+    B[k].walk.print(k == 0 ? "1. walk, queues binned by octant, 128 slots per level" : "   the same, 1024 slots per level");
+    std::printf("   wave calls x%.2f, interior iterations x%.2f, leaf iterations x%.2f in total\n",
+                B[k].walk.calls / T.walk.calls, B[k].walk.int_iter / T.walk.int_iter, B[k].walk.leaf_iter / T.walk.leaf_iter);
+  }
+  const OrderStats& o = T.ordered;
+  std::printf("2. leaf boxes hit per ray %.2f; the walk tests %.2f leaves per ray; in entry order with culling %.2f per ray, "
+              "wave maximum %.2f (walk: %.2f leaf iterations)\n",
+              o.boxes / o.rays, T.walk.leaf_steps / T.walk.rays, o.tests / o.rays, o.wave_max / o.waves,
+              T.walk.leaf_iter / T.walk.calls);
+  T.sorted.print("   walk with a full child sort");
+  const SweepStats& s = T.sweep;
+  std::printf("3. two-phase: %.2f leaf tests per call (%.2f + %.2f + %.2f), %.2f pop-and-cull rounds per call\n",
+              (s.tests[0] + s.tests[1] + s.tests[2]) / s.calls, s.tests[0] / s.calls, s.tests[1] / s.calls,
+              s.tests[2] / s.calls, s.rounds / s.calls);
+  std::printf("two-phase vs walk: rays %.0f mismatches %.0f\n", s.rays, s.mismatches);
+  return s.mismatches == 0 ? 0 : 2;
+}
