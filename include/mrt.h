@@ -665,6 +665,11 @@ int mrt_debug_lanes(uint64_t* out, size_t n, int reset);
  * scene is staged in LDS and MRT_SWEEP=0 is not set under MRT_DIAG=1). */
 int mrt_debug_sweep_list(const mrt_scene* scene, float* records, uint32_t capacity, uint32_t* count,
                          uint32_t* enabled);
+/* Test entry: the rest pops one pass of the stream kernel's queue levels makes
+ * before it recycles a ray with leaves left to test (kernels.hip bounce_wave),
+ * for a scene whose nearest queries sweep.  32: never, the default (every cap
+ * measured slower); MRT_SWEEP_CAP=<n> under MRT_DIAG=1 sets another. */
+int mrt_debug_sweep_cap(const mrt_scene* scene, uint32_t* cap);
 /* Test entry (ABI 7): rank 0's unpack of an N-rank gather without a
  * communicator.  `gathered` (host) holds nranks slabs of
  * mrt_tiles_packed_floats(W, H, 0, nranks) floats, rank k's at slab k, as the

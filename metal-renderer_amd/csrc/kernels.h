@@ -60,6 +60,11 @@ constexpr uint32_t kSegSlack = 1024;
 // level k of wave w at slots ((w * (L - 1)) + k - 1) * kStreamCap) and always
 // runs 64 rays of one bounce: the deepest level holding >= 64 rays, else 64
 // new camera rays; survivors go to the next level (< 2 * 64 rays each).
+// Where nearest queries sweep under a cap (DeviceScene::sweep_cap), a ray with
+// leaves left to test returns to its own level: plane 1's w then holds the
+// mask of those leaves (0 in a survivor's record) and a fifth plane of the
+// same slots, out_q.plane[0] (the stream kernel writes no second queue), its
+// partial hit (t, u, v, bits(prim); prim ~0: none yet).
 constexpr uint32_t kStreamCap = 128;
 constexpr uint32_t kStreamMaxL = 64;
 inline size_t stream_slots(uint32_t L, uint32_t G) { return (size_t)G * 4 * (L > 1 ? L - 1 : 1) * kStreamCap; }

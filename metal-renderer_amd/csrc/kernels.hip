@@ -486,12 +486,14 @@ __device__ __forceinline__ LdsCtx stage_lds(const DeviceScene& sc, uint32_t scra
 //   26-27 stream kernel: camera iterations, queue-level iterations
 //   30-31 leaf-box sweep (nearest queries; their leaf tests count in 4-5):
 //         pop-and-cull rounds, lanes in them
+//   32-33 recycling (stream kernel, capped sweep): lanes recycled, passes
+//         that held a resumed lane
 // ---------------------------------------------------------------------------
 #ifndef MRT_LANESTATS
 #define MRT_LANESTATS 0
 #endif
 #if MRT_LANESTATS
-constexpr int kLaneStats = 32;
+constexpr int kLaneStats = 34;
 __shared__ unsigned long long s_lanes[kBlock / 64][kLaneStats];
 __device__ unsigned long long g_lanes[kLaneStats];
 __device__ __forceinline__ void ls_add(int k, uint32_t v) {
@@ -794,9 +796,17 @@ __device__ __forceinline__ void sweep_leaf(const DeviceScene& sc, const LdsCtx& 
   leaf_tests<MODE>(sc, cx, o, d, tmin, lr >> kLeafCountBits, (lr & (kMaxLeafSize - 1)) + 1, h, false, 0u, nullptr);
 }
 
-template <int MODE>
-__device__ __forceinline__ void sweep_nearest(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
-                                              Hit& h) {
+// CAP (the stream kernel's queue levels): a pass makes at most
+// `cap` pops of the rest mask and returns the mask it leaves; the caller puts
+// a lane with a non-zero mask back on its queue with h as it stands, and a
+// later pass continues it with `resume` = that mask and h = that partial hit.
+// A resumed lane rides through phase 1 (wave-uniform) and ignores its keys;
+// it spends the two key rounds on its next two pops, so every pass clears a
+// bit of every unfinished lane's mask even with cap = 0.  The tested leaves
+// and the cull rule are those of one uncapped pass, so is the answer.
+template <int MODE, bool CAP = false>
+__device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
+                                                  Hit& h, uint32_t cap = 0xFFFFFFFFu, uint32_t resume = 0u) {
   const RayBox rb = make_raybox(o, d);
   LS_ADD(0, ls_lanes());
   LS_ADD(1, 1);
@@ -821,19 +831,42 @@ __device__ __forceinline__ void sweep_nearest(const DeviceScene& sc, const LdsCt
   }
   // the pair's leaves leave the mask (a lone hit: k2 is kNone, whose id bits name leaf 31 — not set, or k1's own)
   rest &= ~((1u << (k1 & 31u)) | (1u << (k2 & 31u)));
-  if (k1 != kNone) sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(g_lds[cx.sweep_base + 2u * (k1 & 31u)].w), h);
-  if (k2 != kNone && bitsf(k2 & ~31u) <= h.t * kCullScale)
-    sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(g_lds[cx.sweep_base + 2u * (k2 & 31u)].w), h);
-  while (rest) {
-    LS_ADD(30, 1);
-    LS_ADD(31, ls_lanes());
+  // the lowest masked leaf leaves the mask: its reference, and whether its recomputed entry passes the cull
+  auto pop = [&](uint32_t& ref) {
     const uint32_t id = (uint32_t)__ffs((int)rest) - 1u;
     rest &= rest - 1u;
     const float4 blo = g_lds[cx.sweep_base + 2u * id], bhi = g_lds[cx.sweep_base + 2u * id + 1u];
     float te;
-    if (sweep_box(blo, bhi, o, rb, tmin, te) && te <= h.t * kCullScale)
-      sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(blo.w), h);
+    ref = fbits(blo.w);
+    return sweep_box(blo, bhi, o, rb, tmin, te) && te <= h.t * kCullScale;
+  };
+  if (!CAP) {
+    if (k1 != kNone) sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(g_lds[cx.sweep_base + 2u * (k1 & 31u)].w), h);
+    if (k2 != kNone && bitsf(k2 & ~31u) <= h.t * kCullScale)
+      sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(g_lds[cx.sweep_base + 2u * (k2 & 31u)].w), h);
+  } else {
+    if (resume) rest = resume;
+#pragma unroll
+    for (int round = 0; round < 2; ++round) {   // the key rounds, shared with the resumed lanes' pops
+      const uint32_t k = round == 0 ? k1 : k2;
+      bool test = k != kNone && (round == 0 || bitsf(k & ~31u) <= h.t * kCullScale);
+      uint32_t ref = 0u;
+      if (resume) {
+        test = false;
+        if (rest) test = pop(ref);
+      } else if (test) {
+        ref = fbits(g_lds[cx.sweep_base + 2u * (k & 31u)].w);
+      }
+      if (test) sweep_leaf<MODE>(sc, cx, o, d, tmin, ref, h);
+    }
   }
+  for (uint32_t c = 0; rest && (!CAP || c < cap); ++c) {
+    LS_ADD(30, 1);
+    LS_ADD(31, ls_lanes());
+    uint32_t ref;
+    if (pop(ref)) sweep_leaf<MODE>(sc, cx, o, d, tmin, ref, h);
+  }
+  return CAP ? rest : 0u;
 }
 
 template <int STACK, int MODE>
@@ -1624,12 +1657,19 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t* v, uint32_t n
 // Used by bounce_kernel (one launch per bounce) and, with WAVEQ (the wave's
 // own queue: survivors at out_base + their rank among the wave's survivors,
 // no cursors, no class split), by stream_kernel.
+// WAVEQ, a queue level of a scene the leaf-box sweep takes: a
+// pass makes at most sc.sweep_cap rest pops, and a lane left with untested
+// leaves is recycled instead of shaded — its record goes back on its own
+// level unchanged, with the mask in plane 1's w and the partial hit in the
+// partial-hit plane (a.out_q.plane[0], which the stream kernel has no other
+// use for), at the level's first slot of this pass + its rank among the
+// recycled lanes.  `recycled` returns their count; they are not survivors.
 template <int STACK, int MODE, bool WAVEQ = false, bool CAM = false>
 __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const LdsCtx& cx, const BounceArgs& a,
                                                uint32_t bounce, bool active, uint32_t idx, uint32_t slot,
                                                const RayQueue& in_q, const RayQueue& out_q, uint32_t* cursor,
                                                uint32_t out_base, uint32_t cap,
-                                               StampRef st) {
+                                               StampRef st, uint32_t& recycled) {
   const uint32_t lane = threadIdx.x & 63u;
   const bool last = (bounce + 1 == a.max_path_length);
   LS_ADD(14, 1);
@@ -1637,6 +1677,8 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
   // -- phase 0: generate (bounce 0) or load (SoA queue planes 0-1) the ray
   PathState s;
   uint32_t tag = 0;   // tag = global owned slot | prevDiffuse << 31
+  uint32_t resume = 0, unfinished = 0;   // WAVEQ: the rest mask a recycled ray came with / leaves with (sweep_nearest)
+  recycled = 0;
   uint32_t pblk = 0xFFFFFFFFu;   // bounce 0: the pixel's 8x8 block (camera-ray candidate lists)
   if (active) {
     if (bounce == 0) {
@@ -1661,6 +1703,7 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
       tag = fbits(q0.w);
       s.d = mk(q1);
       s.prevDiffuse = (tag >> 31) ? 1.0f : 0.0f;
+      if (WAVEQ) resume = fbits(q1.w);   // a recycled ray's untested leaves (0: a survivor's record)
     }
   }
   STAMP_AT(st, 0);
@@ -1696,6 +1739,22 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
         const int32_t root = shadow_root(sc, s.o, graze);
         if (!(a.debug & 64u) && traverse<STACK, MODE, true>(sc, cx, s.o, s.d, 0.0f, hh, h.prim, root)) h.found = false;
       }
+    } else if (WAVEQ && MODE == kAllLds && sc.sweep_leaves) {   // wave-uniform (kernel argument)
+      // the capped sweep; camera rays have no queue slot to return to: no cap
+      h.t = __builtin_inff();
+      h.u = h.v = 0.0f;
+      h.prim = 0xFFFFFFFFu;
+      if (resume) {
+        const float4 ph = a.out_q.plane[0][slot];
+        h.t = ph.x;
+        h.u = ph.y;
+        h.v = ph.z;
+        h.prim = fbits(ph.w);
+        h.found = h.prim != 0xFFFFFFFFu;
+      }
+      // (wave-uniform; the level comes from LDS: named scalar so that the cap holds no VGPR through the sweep)
+      const uint32_t pops = __builtin_amdgcn_readfirstlane(bounce == 0 ? 0xFFFFFFFFu : sc.sweep_cap);
+      unfinished = sweep_nearest<MODE, true>(sc, cx, s.o, s.d, 0.0f, h, pops, resume);
     } else {
       h = trace_nearest<STACK, MODE>(sc, cx, s.o, s.d, 0.0f, __builtin_inff());
     }
@@ -1718,6 +1777,27 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
       s.R = mk(q3);
       s.ior = q3.w;
     }
+  }
+  if (WAVEQ) {
+    // recycle: the slots written are among those this pass read (rank <=
+    // lane), so every lane's plane-2/3 loads above land first; the loop top's
+    // wait orders the wave's later loads behind these stores
+    const uint64_t rmask = __ballot(unfinished != 0u);
+    if (rmask) {
+      LS_ADD(32, (uint32_t)__popcll(rmask));
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (unfinished) {
+        const uint32_t r = slot - lane + lanes_below_in(rmask);
+        in_q.plane[0][r] = make_float4(s.o.x, s.o.y, s.o.z, bitsf(tag));
+        in_q.plane[1][r] = make_float4(s.d.x, s.d.y, s.d.z, bitsf(unfinished));
+        in_q.plane[2][r] = make_float4(s.T.x, s.T.y, s.T.z, s.pdf);
+        in_q.plane[3][r] = make_float4(s.R.x, s.R.y, s.R.z, s.ior);
+        a.out_q.plane[0][r] = make_float4(h.t, h.u, h.v, bitsf(h.prim));
+      }
+      recycled = (uint32_t)__popcll(rmask);
+      active = active && !unfinished;   // neither shaded nor ended here
+    }
+    if (__ballot(resume != 0u)) LS_ADD(33, 1);
   }
   const bool hit_ok = active && h.found && !(h.t < kDistanceEpsilon);
   ShadowRay sh;
@@ -1901,8 +1981,9 @@ __global__ __launch_bounds__(kBlock, MRT_BOUNCE_WAVES) void bounce_kernel(Device
                          : (lo - g_in) * in_chunk + in_chunk - (seg[lo + 1] - seg[lo]) + (idx - seg[lo]);
       }
       STAMP_BEGIN();
+      uint32_t none;   // (no recycling between launches)
       wrote += bounce_wave<STACK, MODE, false, CAM>(sc, cx, a, a.bounce, active, idx, slot, a.in_q, a.out_q, s_cursor,
-                                               out_base, cap, STAMP_REF());
+                                               out_base, cap, STAMP_REF(), none);
     }
     STAMP_WORK();
     if (dynamic && lane == 0) atomicSub(&s_res, kGrab - wrote);
@@ -2046,12 +2127,16 @@ __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(Device
     if (!camera) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     LS_ADD(camera ? 26 : 27, 1);
+    uint32_t recycled;   // lanes back on level lvl with leaves left to test: never camera rays
     const uint32_t wrote = bounce_wave<STACK, MODE, true, CAM>(sc, cx, a, camera ? 0u : lvl, active, idx, slot,
-                                                                 a.in_q, a.in_q, nullptr, out, 0u, st);
+                                                                 a.in_q, a.in_q, nullptr, out, 0u, st, recycled);
     if (lvl + 1u < L && lane == 0) {
       cnt[lvl + 1u] += wrote;
       s_alive[wave][lvl] += wrote;
     }
+    // at most the n lanes that left the level return to it: it stays within
+    // kStreamCap, and every pass clears a mask bit of each, so they finish
+    if (recycled && lane == 0) cnt[lvl] += recycled;
   }
   // stats: survivors of bounce b = rays alive at the start of bounce b + 1
   for (uint32_t b = lane; b + 1 < L; b += 64u)

@@ -154,11 +154,19 @@ struct DeviceScene {
   // (lo.xyz, bits(leaf ref)), (hi.xyz, 0) — the padded child box as it stands
   // in the leaf's parent node; a leaf's id is its position in the list.
   // sweep_leaves == 0: the queries walk.  Last, so that no other field moves.
+  // sweep_cap: rest pops of one pass in the stream kernel's queue levels
+  // before a lane with leaves left is recycled (kernels.hip bounce_wave;
+  // >= kSweepLeaves: never); it fills the struct's tail padding.
   const float* sweep;
   uint32_t sweep_leaves;
+  uint32_t sweep_cap;
 };
+static_assert(sizeof(DeviceScene) == 648, "DeviceScene: kernel argument offsets of every kernel");
 // a leaf id fits 5 bits and a lane's set of leaves one 32-bit mask
 constexpr uint32_t kSweepLeaves = 32;
+// DeviceScene::sweep_cap of the product: never recycle — every cap measured
+// slower than none; MRT_SWEEP_CAP sets another for A/B runs
+constexpr uint32_t kSweepCap = kSweepLeaves;
 constexpr uint32_t kMaxOccPlanes = 8;
 // convex occluders (DeviceScene::conv_*): at most this many solids, and the
 // least d . n (n: the outward normal of the face a shadow ray starts on) for

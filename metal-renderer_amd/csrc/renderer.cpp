@@ -122,6 +122,7 @@ struct mrt_scene {
   // leaf root), and whether nearest queries use them
   std::vector<float> sweep_list;
   bool sweep_on = false;
+  uint32_t sweep_cap = mrt::kSweepCap;   // DeviceScene::sweep_cap
   DevBuf sweep;
   mrt::DeviceScene dev{};
   mrt_scene_info info{};
@@ -539,9 +540,14 @@ int alloc_frame_buffers(mrt_renderer* r) {
     // the path kernel keeps the path state in LDS: no ray queues; the
     // streaming wavefront needs only its per-wave queues
     const size_t qslots = r->stream_mode ? mrt::stream_slots(r->desc.max_path_length, r->grid) : slots;
+    // (stream mode: queue[1] is unused but for its plane 0, the partial hits
+    // of recycled rays — 16 B a slot, as the other planes — where the scene's
+    // nearest queries sweep under a cap, kernels.hip bounce_wave)
+    const mrt::DeviceScene& dev = r->scene->dev;
+    const bool partial = r->stream_mode && dev.sweep_leaves && dev.sweep_cap < mrt::kSweepLeaves;
     for (int q = 0; q < 2; ++q)
       for (int p = 0; p < mrt::kQueuePlanes; ++p)
-        HIP_TRY(fs.queue[q][p].alloc(r->path_mode || (r->stream_mode && q == 1) ? 0 : qslots * 16));
+        HIP_TRY(fs.queue[q][p].alloc(r->path_mode || (r->stream_mode && q == 1 && !(partial && p == 0)) ? 0 : qslots * 16));
     HIP_TRY(fs.radiance.alloc(owned_slots * r->batch * 16));
     const uint32_t need = r->scene->dev.max_stack;
     // spill rows of max_stack words per lane (kernels.hip LdsCtx::spill_lane)
@@ -1180,6 +1186,10 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
     s->sweep_on = !mrt::fast::path_preferred(probe);
   }
   if (const char* v = mrt::diag_env("MRT_SWEEP")) s->sweep_on = s->sweep_on && std::atoi(v) != 0;
+  // rest pops per pass of the stream kernel's queue levels before a ray is
+  // recycled (MRT_SWEEP_CAP: kSweepLeaves or more never recycles — the uncapped sweep)
+  if (const char* v = mrt::diag_env("MRT_SWEEP_CAP"))
+    s->sweep_cap = (uint32_t)std::min<unsigned long>(std::strtoul(v, nullptr, 0), mrt::kSweepLeaves);
   in.vertices = (uint32_t)h.vertices.size();
   in.triangles = T;
   in.materials = (uint32_t)h.materials.size();
@@ -1250,6 +1260,7 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
   std::memcpy(d.conv_face_tris, in.convex_face_tris, sizeof(d.conv_face_tris));
   d.sweep = nullptr;
   d.sweep_leaves = 0;
+  d.sweep_cap = s->sweep_cap;
   if (s->sweep_on) {
     HIP_TRY(upload(s->sweep, s->sweep_list.data(), s->sweep_list.size() * 4));
     d.sweep = s->sweep.as<float>();
@@ -1275,6 +1286,12 @@ int mrt_debug_sweep_list(const mrt_scene* scene, float* records, uint32_t capaci
   if (records) std::memcpy(records, scene->sweep_list.data(), (size_t)std::min(n, capacity) * 32);
   *count = n;
   *enabled = scene->sweep_on ? 1u : 0u;
+  return MRT_OK;
+}
+
+int mrt_debug_sweep_cap(const mrt_scene* scene, uint32_t* cap) {
+  if (!scene || !cap) return fail(MRT_ERR_INVALID, "mrt_debug_sweep_cap: null argument");
+  *cap = scene->sweep_cap;
   return MRT_OK;
 }
 

@@ -232,7 +232,7 @@ EXPORTED = [
     "mrt_renderer_exchange_flush", "mrt_renderer_tiles_read", "mrt_renderer_tiles_write",
     "mrt_image_load_exr", "mrt_renderer_load_reference", "mrt_renderer_display",
     "mrt_renderer_display_enqueue", "mrt_renderer_display_map",
-    "mrt_debug_lanes", "mrt_debug_sweep_list", "mrt_debug_bvh_nodes", "mrt_debug_exchange_unpack", "mrt_debug_box_margin",
+    "mrt_debug_lanes", "mrt_debug_sweep_list", "mrt_debug_sweep_cap", "mrt_debug_bvh_nodes", "mrt_debug_exchange_unpack", "mrt_debug_box_margin",
     "mrt_debug_magic_div", "mrt_comm_set_timeout", "mrt_comm_check", "mrt_debug_comm_fail",
     "mrt_camera_default", "mrt_camera_look_at", "mrt_camera_check", "mrt_raygen_camera",
     "mrt_renderer_set_camera", "mrt_renderer_get_camera",
@@ -296,6 +296,7 @@ def lib() -> ctypes.CDLL:
         "mrt_debug_wave_times": [vp, ctypes.c_size_t],
         "mrt_debug_lanes": [vp, ctypes.c_size_t, c_int],
         "mrt_debug_sweep_list": [vp, vp, u32, vp, vp],
+        "mrt_debug_sweep_cap": [vp, vp],
         "mrt_debug_bvh_nodes": [vp, vp, u32, vp],
         "mrt_debug_exchange_unpack": [vp, u32, vp, ctypes.c_size_t],
         "mrt_debug_box_margin": [vp, vp, u32, u32, vp, vp],
@@ -930,6 +931,14 @@ def debug_sweep_list(scene: "Scene"):
     _check(lib().mrt_debug_sweep_list(scene.handle, ctypes.c_void_p(out.ctypes.data), len(out), ctypes.byref(count),
                                       ctypes.byref(enabled)), "mrt_debug_sweep_list")
     return bool(enabled.value), out[:min(count.value, len(out))].copy()
+
+
+def debug_sweep_cap(scene: "Scene") -> int:
+    """Rest pops per pass of the stream kernel's queue levels before a ray
+    with leaves left is recycled (test entry; 32: never)."""
+    cap = ctypes.c_uint32()
+    _check(lib().mrt_debug_sweep_cap(scene.handle, ctypes.byref(cap)), "mrt_debug_sweep_cap")
+    return cap.value
 
 
 def debug_bvh_nodes(scene: "Scene"):

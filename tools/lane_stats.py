@@ -26,7 +26,7 @@ NAMES = ["near_lanes", "near_calls", "near_int_iters", "near_int_lanes", "near_l
          "shade_calls", "shade_lanes", "wave_calls", "wave_active", "shadow_rays", "shadow_calls",
          "list_calls", "list_lanes", "svc_rounds", "svc_lanes", "trav_rounds", "trav_lanes", "refill_lanes",
          "outer_iters", "stream_camera_iters", "stream_level_iters", "stream_queue_wait_cycles",
-         "stream_queue_waits", "sweep_cull_rounds", "sweep_cull_lanes"]
+         "stream_queue_waits", "sweep_cull_rounds", "sweep_cull_lanes", "recycled_lanes", "resumed_passes"]
 
 
 def main():
@@ -76,6 +76,10 @@ def main():
         if c.get("sweep_cull_rounds"):   # leaf-box sweep: the masked leaves' pop-and-cull rounds
             out["sweep_cull_rounds_per_call"] = round(c["sweep_cull_rounds"] / max(1, c["near_calls"]), 3)
             out["sweep_cull_util"] = util(c["sweep_cull_lanes"], c["sweep_cull_rounds"])
+        if c.get("recycled_lanes"):   # capped sweep: against tools/walk_model's table
+            # near_lanes counts a recycled ray once per pass: finished rays = lanes - recycled
+            out["recycled_share_of_rays"] = round(c["recycled_lanes"] / max(1, c["near_lanes"] - c["recycled_lanes"]), 4)
+            out["resumed_pass_share"] = round(c["resumed_passes"] / max(1, c["near_calls"]), 4)
         out["wave_entry_util"] = util(c["wave_active"], c["wave_calls"])
         out["shade_util"] = util(c["shade_lanes"], c["shade_calls"])
         out["shadow_phase_util"] = util(c["shadow_rays"], c["shadow_calls"])

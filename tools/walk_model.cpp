@@ -23,7 +23,11 @@
 //      order an ideal walk would have), and by the walk with a full child sort;
 //   3. by the two-phase sweep (sweep_nearest): all leaf boxes, the two nearest
 //      kept as keys and the rest as a mask, then entry-ordered leaf tests.
-// The sweep's (found, t, prim) is compared with the walk's for every ray.
+//   4. by the sweep with a cap on a pass's rest pops, unfinished rays going
+//      back on their level's queue (recycling): caps 0-3 and
+//      unbounded, on rays that are the same for every cap.
+// The sweep's (found, t, prim) is compared with the walk's for every ray, and
+// so is every recycled ray's once it finishes; no queue may pass kStreamCap.
 //
 // build (in tools/): g++ -O2 -std=c++17 -ffp-contract=off -I../metal-renderer_amd/csrc walk_model.cpp
 //        ../metal-renderer_amd/csrc/{scene,bvh}.cpp -o walk_model -lpthread
@@ -372,6 +376,141 @@ void simulate(const HostScene& sc, int blocks, int bins, bool bounded, Totals& T
       while (!q[lvl][b].empty()) run(lvl, b, std::min<size_t>(kWave, q[lvl][b].size()));
 }
 
+// 4. Recycling: a pass of the sweep tests key 1, key 2 (culled)
+// and then at most `cap` pops of the rest mask; a lane whose mask is still
+// non-zero goes back on its own level's queue with its partial hit and the
+// mask, and a later pass of that level continues it (phase 1 is wave-uniform:
+// a resumed lane rides through it and ignores its keys).  keys_pop: a resumed
+// lane spends the key-1 and key-2 rounds on its next two pops.  The rays are
+// the same for every cap: a ray carries its own random state, so what a path
+// does next does not depend on the pass it finished in.
+constexpr int kStreamCap = 128;   // kernels.h: a level's slots
+struct RRay { Ray r; uint64_t seed = 0; Hit h; uint32_t rest = 0, passes = 0; };
+struct RecycleStats {
+  double calls = 0, lanes = 0, rays = 0, leaf_rounds = 0, cull_rounds = 0, tests = 0, recycled = 0, resumed_calls = 0;
+  double mismatches = 0;
+  uint32_t max_passes = 0, max_queue = 0;
+};
+
+void recycle_wave(RRay* w, int n, int cap, bool keys_pop, RecycleStats& st) {
+  const uint32_t N = (uint32_t)(g_sweep.size() / 8), kNone = 0xFFFFFFFFu;
+  uint32_t k1[kWave], k2[kWave];
+  float inv[kWave][3];
+  bool resumed[kWave], any_resumed = false;
+  st.calls += 1;
+  st.lanes += n;
+  for (int l = 0; l < n; ++l) {
+    resumed[l] = w[l].rest != 0;
+    any_resumed |= resumed[l];
+    k1[l] = k2[l] = kNone;
+    for (int a = 0; a < 3; ++a) inv[l][a] = safe_inv(w[l].r.d[a]);
+    if (resumed[l]) continue;
+    w[l].h = Hit();
+    uint32_t rest = 0;
+    for (uint32_t i = 0; i < N; ++i) {
+      float te;
+      const bool hit = box_entry(w[l].r, inv[l], &g_sweep[8 * i], &g_sweep[8 * i + 4], te);
+      const uint32_t key = hit ? ((fb(te) & ~31u) | i) : kNone;
+      const uint32_t mid = std::max(k1[l], key);
+      k1[l] = std::min(k1[l], key);
+      k2[l] = std::min(k2[l], mid);
+      if (hit) rest |= 1u << i;
+    }
+    w[l].rest = rest & ~((1u << (k1[l] & 31u)) | (1u << (k2[l] & 31u)));
+  }
+  st.resumed_calls += any_resumed;
+  auto ref = [&](uint32_t id) { return (int32_t)fb(g_sweep[8 * id + 3]); };
+  auto pop = [&](int l) {   // the lowest masked leaf, culled by its recomputed entry
+    const uint32_t id = (uint32_t)__builtin_ctz(w[l].rest);
+    w[l].rest &= w[l].rest - 1;
+    float te;
+    if (!(box_entry(w[l].r, inv[l], &g_sweep[8 * id], &g_sweep[8 * id + 4], te) && te <= w[l].h.t * kCull)) return false;
+    leaf_test(w[l].r, ref(id), w[l].h);
+    st.tests += 1;
+    return true;
+  };
+  for (int round = 0; round < 2; ++round) {
+    bool any = false, culls = false;
+    for (int l = 0; l < n; ++l) {
+      if (resumed[l]) {
+        if (keys_pop && w[l].rest) { culls = true; any |= pop(l); }
+        continue;
+      }
+      const uint32_t k = round == 0 ? k1[l] : k2[l];
+      if (k == kNone || (round == 1 && !(bf(k & ~31u) <= w[l].h.t * kCull))) continue;
+      leaf_test(w[l].r, ref(k & 31u), w[l].h);
+      st.tests += 1;
+      any = true;
+    }
+    st.leaf_rounds += any;
+    st.cull_rounds += culls;
+  }
+  for (int c = 0; cap < 0 || c < cap; ++c) {
+    bool more = false, any = false;
+    for (int l = 0; l < n; ++l)
+      if (w[l].rest) { more = true; any |= pop(l); }
+    if (!more) break;
+    st.cull_rounds += 1;
+    st.leaf_rounds += any;
+  }
+}
+
+void simulate_recycle(const HostScene& sc, int blocks, int cap, bool keys_pop, RecycleStats& st) {
+  constexpr int kLevels = 2;
+  std::vector<RRay> q[kLevels];
+  WalkStats scratch;
+  auto run = [&](int lvl, size_t count) {
+    std::vector<RRay>& Q = q[lvl];
+    std::vector<RRay> w(Q.end() - (long)count, Q.end());
+    Q.resize(Q.size() - count);
+    recycle_wave(w.data(), (int)w.size(), cap, keys_pop, st);
+    for (RRay& x : w)   // unfinished lanes return to their own level first (the slots the pass read)
+      if (x.rest) { ++x.passes; st.recycled += 1; st.max_passes = std::max(st.max_passes, x.passes); Q.push_back(x); }
+    st.max_queue = std::max<uint32_t>(st.max_queue, (uint32_t)Q.size());
+    for (RRay& x : w) {
+      if (x.rest) continue;
+      st.rays += 1;
+      Hit ref;
+      walk_wave(&x.r, 1, &ref, scratch, false);
+      st.mismatches += x.h.found != ref.found || (ref.found && (fb(x.h.t) != fb(ref.t) || x.h.prim != ref.prim));
+      if (lvl + 1 >= kLevels) continue;
+      RRay nx;
+      g_rng = x.seed;
+      if (bounce(x.r, x.h, sc, nx.r)) { nx.seed = g_rng; q[lvl + 1].push_back(nx); }
+    }
+    if (lvl + 1 < kLevels) st.max_queue = std::max<uint32_t>(st.max_queue, (uint32_t)q[lvl + 1].size());
+  };
+  const int bx = 240;
+  for (int blk = 0; blk < blocks;) {
+    int lvl = kLevels - 1;
+    while (lvl >= 0 && q[lvl].size() < (size_t)kWave) --lvl;
+    if (lvl >= 0) { run(lvl, kWave); continue; }
+    const int bi = (int)(((long long)blk * 32400) / blocks), px = (bi % bx) * 8, py = (bi / bx) * 8;
+    for (int i = 0; i < kWave; ++i) {
+      uint64_t z = 0x9E3779B97F4A7C15ull * (uint64_t)(blk * kWave + i + 1);   // splitmix64: the ray's own stream
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      g_rng = z ^ (z >> 31);
+      const float x = ((float)(px + i % 8) + rnd()) / 1920.0f * 2.0f - 1.0f;
+      const float y = ((float)(py + i / 8) + rnd()) / 1080.0f * 2.0f - 1.0f;
+      Ray r;
+      r.o[0] = kCameraX; r.o[1] = kCameraY; r.o[2] = kCameraZ;
+      const float d[3] = {x * (1920.0f / 1080.0f) * 0.4f, y * 0.4f, -1.0f}, len = std::sqrt(tdot(d, d));
+      for (int a = 0; a < 3; ++a) r.d[a] = d[a] / len;
+      RRay nx;
+      if (bounce(r, brute(r), sc, nx.r)) { nx.seed = g_rng; q[0].push_back(nx); }
+    }
+    ++blk;
+    st.max_queue = std::max<uint32_t>(st.max_queue, (uint32_t)q[0].size());
+  }
+  for (;;) {   // the tail: the deepest non-empty level, as a partial wave
+    int lvl = kLevels - 1;
+    while (lvl >= 0 && q[lvl].empty()) --lvl;
+    if (lvl < 0) break;
+    run(lvl, std::min<size_t>(kWave, q[lvl].size()));
+  }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -419,5 +558,30 @@ int main(int argc, char** argv) {
               (s.tests[0] + s.tests[1] + s.tests[2]) / s.calls, s.tests[0] / s.calls, s.tests[1] / s.calls,
               s.tests[2] / s.calls, s.rounds / s.calls);
   std::printf("two-phase vs walk: rays %.0f mismatches %.0f\n", s.rays, s.mismatches);
-  return s.mismatches == 0 ? 0 : 2;
+  // 4. recycling: caps 0..3 and unbounded (today's sweep on these rays), in both variants
+  std::printf("4. recycling (cap: rest pops per pass; keys: resumed lanes pop in the key rounds)\n");
+  double bad = 0, base_calls = 0, base_leaf = 0, base_cull = 0;
+  uint32_t max_queue = 0;
+  const int caps[5] = {-1, 0, 1, 2, 3};
+  for (int keys = 0; keys < 2; ++keys)
+    for (int cap : caps) {
+      if (cap == 0 && !keys) continue;   // no progress: a resumed lane would never clear a bit
+      if (cap < 0 && keys) continue;     // unbounded never resumes: one row
+      RecycleStats r;
+      simulate_recycle(sc, blocks, cap, keys != 0, r);
+      if (cap < 0) { base_calls = r.calls; base_leaf = r.leaf_rounds; base_cull = r.cull_rounds; }
+      char name[32];
+      if (cap < 0) std::snprintf(name, sizeof name, "unbounded");
+      else std::snprintf(name, sizeof name, "cap %d%s", cap, keys ? " keys" : "");
+      std::printf("   %-11s %6.0f calls (x%.3f), %.1f lanes; leaf rounds %.2f/call (x%.3f in total), cull rounds %.2f/call "
+                  "(x%.3f); %.3f tests/ray; recycled %.2f %% of rays, %.1f %% of calls hold a resumed lane, most passes %u; "
+                  "longest queue %u; mismatches %.0f of %.0f\n",
+                  name, r.calls, r.calls / base_calls, r.lanes / r.calls, r.leaf_rounds / r.calls, r.leaf_rounds / base_leaf,
+                  r.cull_rounds / r.calls, r.cull_rounds / base_cull, r.tests / r.rays, 100.0 * r.recycled / r.rays,
+                  100.0 * r.resumed_calls / r.calls, r.max_passes + 1, r.max_queue, r.mismatches, r.rays);
+      bad += r.mismatches;
+      max_queue = std::max(max_queue, r.max_queue);
+    }
+  std::printf("recycling vs walk: mismatches %.0f, longest queue %u of %d slots\n", bad, max_queue, kStreamCap);
+  return s.mismatches == 0 && bad == 0 && max_queue <= (uint32_t)kStreamCap ? 0 : 2;
 }
