@@ -488,12 +488,18 @@ __device__ __forceinline__ LdsCtx stage_lds(const DeviceScene& sc, uint32_t scra
 //         pop-and-cull rounds, lanes in them
 //   32-33 recycling (stream kernel, capped sweep): lanes recycled, passes
 //         that held a resumed lane
+//   34-45 stream kernel, exposed memory waits, pairs of shader-
+//         clock cycles and events as 28-29: queue planes 0-1, queue planes
+//         2-3, candidate-list header + entries (per listed camera iteration),
+//         the shadow query's root select, the sweep's phase-1 record loads
+//         (per record), and a back-to-back pair of clock reads (the cost of
+//         the measurement itself, to be subtracted per event)
 // ---------------------------------------------------------------------------
 #ifndef MRT_LANESTATS
 #define MRT_LANESTATS 0
 #endif
 #if MRT_LANESTATS
-constexpr int kLaneStats = 34;
+constexpr int kLaneStats = 46;
 __shared__ unsigned long long s_lanes[kBlock / 64][kLaneStats];
 __device__ unsigned long long g_lanes[kLaneStats];
 __device__ __forceinline__ void ls_add(int k, uint32_t v) {
@@ -505,10 +511,25 @@ __device__ __forceinline__ uint32_t ls_lanes() { return (uint32_t)__popcll(__bal
 #define LS_INIT() do { if ((threadIdx.x & 63u) < (uint32_t)kLaneStats) s_lanes[threadIdx.x >> 6][threadIdx.x & 63u] = 0; } while (0)
 #define LS_FLUSH() do { const uint32_t l_ = threadIdx.x & 63u; \
     if (l_ < (uint32_t)kLaneStats && s_lanes[threadIdx.x >> 6][l_]) atomicAdd(&g_lanes[l_], s_lanes[threadIdx.x >> 6][l_]); } while (0)
+// the shader clock, read and waited for (the wait is for the scalar and LDS
+// counter only: outstanding vector memory operations stay outstanding)
+__device__ __forceinline__ uint64_t ls_clock() {
+  uint64_t t;
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  return t;
+}
+#define LS_T0() const uint64_t ls_t0_ = ls_clock()
+// cycles since LS_T0 into slot k, one event into slot k + 1
+#define LS_T1(k) do { LS_ADD((k), (uint32_t)(ls_clock() - ls_t0_)); LS_ADD((k) + 1, 1); } while (0)
+// cycles the wave waits here for its outstanding vector memory operations
+#define LS_WAIT_VM(k) do { LS_T0(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); LS_T1(k); } while (0)
 #else
 #define LS_ADD(k, v) do {} while (0)
 #define LS_INIT() do {} while (0)
 #define LS_FLUSH() do {} while (0)
+#define LS_T0() do {} while (0)
+#define LS_T1(k) do {} while (0)
+#define LS_WAIT_VM(k) do {} while (0)
 #endif
 
 // While-while traversal with postponed leaves (Aila & Laine 2009, recast for
@@ -696,9 +717,13 @@ __device__ __forceinline__ bool leaf_tests(const DeviceScene& sc, const LdsCtx& 
 // (primary.h): the nearest hit over the listed triangles with the leaf test's
 // arithmetic and tie rule — the traversal's answer, since the list holds
 // every triangle a ray of the block can hit.  `list` / `cnt` are
-// wave-uniform (scalar loads; LDS-resident triangles are broadcast reads).
+// wave-uniform, and the list is read through the constant address space:
+// that is what makes its reads scalar loads (through a plain global pointer
+// they are vector loads of a uniform address).  LDS-resident triangles are
+// broadcast reads.
+typedef const __attribute__((address_space(4))) uint32_t* PrimaryWords;
 template <int MODE>
-__device__ __forceinline__ void primary_nearest(const DeviceScene& sc, const LdsCtx& cx, const uint32_t* list,
+__device__ __forceinline__ void primary_nearest(const DeviceScene& sc, const LdsCtx& cx, PrimaryWords list,
                                                 uint32_t cnt, V3 o, V3 d, Hit& h) {
   h.t = __builtin_inff();
   h.u = h.v = 0.0f;
@@ -706,6 +731,12 @@ __device__ __forceinline__ void primary_nearest(const DeviceScene& sc, const Lds
   h.found = false;
   for (uint32_t j = 0; j < cnt; j += 2) {
     const uint32_t j1 = min(j + 1, cnt - 1);
+#if MRT_LANESTATS   // the pair's wait joins the header's in slot 38 (one event per header)
+    const uint64_t t0_ = ls_clock();
+    const uint32_t e0_ = list[j], e1_ = list[j1];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(e0_), "s"(e1_) : "memory");
+    LS_ADD(38, (uint32_t)(ls_clock() - t0_));
+#endif
     tri_pair<MODE>(sc, cx, o, d, 0.0f, list[j], list[j1], j1 != j, h, false, 0u, nullptr);
   }
 }
@@ -818,7 +849,12 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
     // (no record loaded ahead: the eight more scalar registers of a second
     // record cost the stream kernel scalar spills inside this loop, and the
     // other resident waves cover the load: measured)
+    LS_T0();
     const SweepRec rec = list[i];
+#if MRT_LANESTATS
+    asm volatile("" ::"s"(rec[0]), "s"(rec[7]));
+    LS_T1(42);
+#endif
     float te;
     const bool hit = sweep_box(make_float4(rec[0], rec[1], rec[2], rec[3]), make_float4(rec[4], rec[5], rec[6], rec[7]),
                                o, rb, tmin, te);
@@ -890,8 +926,25 @@ __device__ __forceinline__ Hit trace_nearest(const DeviceScene& sc, const LdsCtx
 // can then stand between o and a light) and the ray does not graze the
 // light's plane (`graze`: cosine below occ_cos_min, where the light's own t
 // error could reach a culled crossing), else the main tree.  The plane data
-// is wave-uniform (kernel argument, scalar registers).
+// is wave-uniform (kernel argument, scalar registers).  So are the two roots:
+// named scalars, because a per-lane select of two kernel arguments compiles
+// to a select of their addresses and one vector load from the kernel-argument
+// segment, waited for at once.
 __device__ __forceinline__ int32_t shadow_root(const DeviceScene& sc, V3 o, bool graze) {
+  const int32_t main_root = __builtin_amdgcn_readfirstlane(sc.root);
+  if (sc.occ_planes == 0) return main_root;
+  const int32_t occ_root = __builtin_amdgcn_readfirstlane(sc.occ_root);
+  bool inside = !graze;
+  for (uint32_t k = 0; k < sc.occ_planes; ++k) {
+    const float* p = sc.occ_plane[k];
+    inside &= fmaf(p[0], o.x, fmaf(p[1], o.y, fmaf(p[2], o.z, -p[3]))) <= -sc.occ_margin;
+  }
+  return inside ? occ_root : main_root;
+}
+// The same with the per-lane select of the two kernel arguments: the path
+// kernel's, whose register allocation is left as it is (its queries have no
+// stores in flight before them).
+__device__ __forceinline__ int32_t shadow_root_select(const DeviceScene& sc, V3 o, bool graze) {
   if (sc.occ_planes == 0 || graze) return sc.root;
   bool inside = true;
   for (uint32_t k = 0; k < sc.occ_planes; ++k) {
@@ -1044,7 +1097,12 @@ __device__ __forceinline__ bool trace_occluded(const DeviceScene& sc, const LdsC
   Hit h;
   h.t = t_target;
   h.found = false;
+  LS_T0();
   int32_t root = shadow_root(sc, o, graze);
+#if MRT_LANESTATS
+  asm volatile("" ::"v"(root));
+  LS_T1(40);
+#endif
   const bool via_occ = root == sc.occ_root;
   if (sc.conv_count && via_occ) {
     if (!(dbg & 512u) && convex_occlusion<MODE>(sc, cx, o, d, target, t_target, origin)) return true;
@@ -1646,6 +1704,18 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t* v, uint32_t n
   return total;
 }
 
+#ifndef MRT_STREAM_WAITS   // 0: no wait before the survivor stores (bounce_wave; A/B variants)
+#define MRT_STREAM_WAITS 1
+#endif
+// The wave's vector memory operations retired, as an instruction the
+// compiler's own wait insertion sees (a wait written in assembly it does not):
+// it then forgets the loads it still counts as pending.
+__device__ __forceinline__ void wait_vmem() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), no wait on the export and LDS / scalar counters
+  asm volatile("" ::: "memory");
+}
+
 // One wave iteration of the fused bounce: up to 64 rays of bounce `bounce`.
 // Each active lane generates its camera ray (bounce 0: `idx` = the launch's
 // dense index = global slot) or loads its ray from `slot` of `in_q`, finds
@@ -1699,6 +1769,7 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
       // traversal: they are not needed there, and keeping them out of the
       // traversal's live set saves 8 VGPRs
       const float4 q0 = in_q.plane[0][slot], q1 = in_q.plane[1][slot];
+      if (WAVEQ) LS_WAIT_VM(34);
       s.o = mk(q0);
       tag = fbits(q0.w);
       s.d = mk(q1);
@@ -1716,13 +1787,19 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
     // candidate list, when every active lane is in the same block
     const uint32_t b0 = __builtin_amdgcn_readfirstlane(pblk);
     const bool uniform = b0 != 0xFFFFFFFFu && __ballot(active && pblk != b0) == 0;
-    const uint32_t hd = uniform ? __builtin_amdgcn_readfirstlane(a.primary[b0]) : kPrimaryFallback;
+    LS_T0();
+    const PrimaryWords words = (PrimaryWords)(uintptr_t)a.primary;   // header and list: scalar loads
+    const uint32_t hd = uniform ? words[b0] : kPrimaryFallback;
+#if MRT_LANESTATS
+    asm volatile("" ::"s"(hd));
+    if (WAVEQ && uniform) LS_T1(38);
+#endif
     const uint32_t cnt = hd & 0xFFu;
     if (cnt != kPrimaryFallback) {
       listed = true;
       LS_ADD(18, 1);
       LS_ADD(19, (uint32_t)__popcll(__ballot(active)));
-      if (active) primary_nearest<MODE>(sc, cx, a.primary + (hd >> 8), cnt, s.o, s.d, h);
+      if (active) primary_nearest<MODE>(sc, cx, words + (hd >> 8), cnt, s.o, s.d, h);
     }
   }
   if (active && !listed) {
@@ -1772,6 +1849,7 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
       s.ior = 1.00029f;
     } else {
       const float4 q2 = in_q.plane[2][slot], q3 = in_q.plane[3][slot];
+      if (WAVEQ) LS_WAIT_VM(36);
       s.T = mk(q2);
       s.pdf = q2.w;
       s.R = mk(q3);
@@ -1825,6 +1903,13 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
   //    survivors are compacted into this block's segment of the next queue.
   //    Planes 0-2 are written before the shadow traversal so the next ray
   //    is not live across it; plane 3 (radiance, ior) after it.
+  // WAVEQ: every load of this iteration has been used by now, so this wait
+  // costs nothing — but without it the compiler still counts a queue load as
+  // pending (presumably on the paths that skip its use: a wave without an
+  // active lane) and waits for "it" at the first reuse of its registers: at
+  // the start of the shadow query, behind the stores below, whose whole
+  // round trip that s_waitcnt vmcnt(0) then exposed.
+  if (WAVEQ && MRT_STREAM_WAITS) wait_vmem();
   if (active && (!hit_ok || last)) a.radiance[gslot] = make_float4(s.R.x, s.R.y, s.R.z, 0.0f);
   const bool alive = hit_ok && !last;
   // re-sort by material between bounces: survivors that left a diffuse
@@ -2127,6 +2212,10 @@ __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(Device
     if (!camera) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     LS_ADD(camera ? 26 : 27, 1);
+    {   // the cost of one timed pair with nothing between
+      LS_T0();
+      LS_T1(44);
+    }
     uint32_t recycled;   // lanes back on level lvl with leaves left to test: never camera rays
     const uint32_t wrote = bounce_wave<STACK, MODE, true, CAM>(sc, cx, a, camera ? 0u : lvl, active, idx, slot,
                                                                  a.in_q, a.in_q, nullptr, out, 0u, st, recycled);
@@ -2487,7 +2576,7 @@ __global__ __launch_bounds__(kBlock, MRT_PATH_WAVES) void path_kernel(DeviceScen
           const V3 p0 = mk(fetch_prim<MODE>(sc, cx, sh.target, 0)), p1 = mk(P1);
           const V3 p2 = mk(fetch_prim<MODE>(sc, cx, sh.target, 2));
           float tT, u, v;
-          const int32_t sroot = shadow_root(sc, ro, sh.graze);
+          const int32_t sroot = shadow_root_select(sc, ro, sh.graze);
           if (tri_test(ro, sh.d, p0, sub(p1, p0), sub(p2, p0), 0.0f, __builtin_inff(), tT, u, v) &&
               !(tT < kDistanceEpsilon) && !origin_occludes<MODE>(sc, cx, ro, sh.d, h.prim, sh.target, tT) &&
               !(sc.occ_lights && sroot == sc.occ_root &&

@@ -26,7 +26,15 @@ NAMES = ["near_lanes", "near_calls", "near_int_iters", "near_int_lanes", "near_l
          "shade_calls", "shade_lanes", "wave_calls", "wave_active", "shadow_rays", "shadow_calls",
          "list_calls", "list_lanes", "svc_rounds", "svc_lanes", "trav_rounds", "trav_lanes", "refill_lanes",
          "outer_iters", "stream_camera_iters", "stream_level_iters", "stream_queue_wait_cycles",
-         "stream_queue_waits", "sweep_cull_rounds", "sweep_cull_lanes", "recycled_lanes", "resumed_passes"]
+         "stream_queue_waits", "sweep_cull_rounds", "sweep_cull_lanes", "recycled_lanes", "resumed_passes",
+         # exposed memory waits of a stream-kernel iteration: shader-clock cycles, events
+         "q01_wait_cycles", "q01_waits", "q23_wait_cycles", "q23_waits", "list_wait_cycles", "list_waits",
+         "root_wait_cycles", "root_waits", "sweep_rec_wait_cycles", "sweep_rec_waits",
+         "clock_pair_cycles", "clock_pairs"]
+# (cycles slot, events slot, output name) of the timed waits
+WAITS = [("q01_wait_cycles", "q01_waits", "q01"), ("q23_wait_cycles", "q23_waits", "q23"),
+         ("list_wait_cycles", "list_waits", "list"), ("root_wait_cycles", "root_waits", "root"),
+         ("sweep_rec_wait_cycles", "sweep_rec_waits", "sweep_rec")]
 
 
 def main():
@@ -88,6 +96,17 @@ def main():
             # shader-clock cycles (s_memtime) a wave spends in the queue
             # iteration's wait for its own stores, per level iteration
             out["queue_wait_cycles_per_iter"] = round(c["stream_queue_wait_cycles"] / c["stream_queue_waits"], 2)
+        if c.get("clock_pairs"):
+            # each timed wait: cycles per event less the cost of an empty timed
+            # pair, and its total per wave iteration (camera + level iterations)
+            iters = max(1, c["stream_camera_iters"] + c["stream_level_iters"])
+            pair = c["clock_pair_cycles"] / c["clock_pairs"]
+            out["clock_pair_cycles"] = round(pair, 2)
+            for cyc, ev, nm in WAITS:
+                if c.get(ev):
+                    out[f"{nm}_wait_cycles_per_event"] = round(c[cyc] / c[ev] - pair, 2)
+                    out[f"{nm}_wait_cycles_per_iter"] = round((c[cyc] - pair * c[ev]) / iters, 2)
+            # (the list slot's events are headers; each listed pair adds one more timed pair to its cycles)
     print(json.dumps(out))
 
 
