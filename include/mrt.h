@@ -665,6 +665,21 @@ int mrt_debug_lanes(uint64_t* out, size_t n, int reset);
  * scene is staged in LDS and MRT_SWEEP=0 is not set under MRT_DIAG=1). */
 int mrt_debug_sweep_list(const mrt_scene* scene, float* records, uint32_t capacity, uint32_t* count,
                          uint32_t* enabled);
+/* Test entry: the list the sweep kernels get, derived from the per-leaf list
+ * above — *count records (at most 32; more, from a non-default leaf size,
+ * and the scene walks), one per group of at most two triangles: a
+ * two-triangle leaf, two single-triangle leaves paired (repeatedly the pair
+ * whose union box has the smallest surface area, if below the sum of the
+ * members' areas), a single left alone, or ceil(n / 2) records with the
+ * leaf's box for a leaf of n > 2 triangles.  min(*count, capacity) are copied
+ * to `records` (may be NULL) as 8 floats each: (lo.xyz, bits(ka | kb << 16)),
+ * (hi.xyz, 0) — the component-wise min / max of the members' boxes and the
+ * two leaf-ordered triangle indices (kb == ka: one) — and their primitive ids
+ * to prims[2 i], prims[2 i + 1] (may be NULL).  A record stands at its first
+ * member's position.  MRT_SWEEP_PAIRS=0 under MRT_DIAG=1: no two leaves share
+ * a record. */
+int mrt_debug_sweep_pairs(const mrt_scene* scene, float* records, uint32_t* prims, uint32_t capacity,
+                          uint32_t* count);
 /* Test entry: the rest pops one pass of the stream kernel's queue levels makes
  * before it recycles a ray with leaves left to test (kernels.hip bounce_wave),
  * for a scene whose nearest queries sweep.  32: never, the default (every cap

@@ -284,7 +284,7 @@ struct LdsCtx {
   uint32_t prim_base;
   uint32_t mat_base;
   uint32_t light_base;
-  uint32_t sweep_base;    // the sweep list's leaf records (kAllLds, sc.sweep_leaves of them)
+  uint32_t sweep_base;    // the sweep list's records (kAllLds, sc.sweep_leaves of them)
   uint32_t scratch_base;  // uint32 offset of the per-block scratch
   uint32_t stack_base;    // uint32 offset of the block's stack slot 0 (lane 0's); lanes add threadIdx.x
   uint32_t* spill;        // stack entries >= STACK: the block's rows of a global [lane][word] spill
@@ -318,7 +318,7 @@ __host__ __device__ inline uint32_t scene_tri_records(const DeviceScene& sc) { r
 __host__ __device__ inline uint32_t lds_scene_float4s(int mode, const DeviceScene& sc) {
   return lds_scene_float4s(mode, node_float4s(sc.width), scene_nodes(sc), sc.lds_nodes, scene_tri_records(sc),
                            sc.num_triangles, sc.num_materials, sc.num_lights + 1) +
-         (mode == kAllLds ? 2 * sc.sweep_leaves : 0u);   // the sweep list's leaf records (sweep_nearest)
+         (mode == kAllLds ? 2 * sc.sweep_leaves : 0u);   // the sweep list's records (sweep_nearest)
 }
 
 // 16-B buffer load at a 32-bit byte offset from a wave-uniform descriptor
@@ -494,12 +494,13 @@ __device__ __forceinline__ LdsCtx stage_lds(const DeviceScene& sc, uint32_t scra
 //         the shadow query's root select, the sweep's phase-1 record loads
 //         (per record), and a back-to-back pair of clock reads (the cost of
 //         the measurement itself, to be subtracted per event)
+//   46-47 leaf-box sweep: third key rounds that test, lanes in them
 // ---------------------------------------------------------------------------
 #ifndef MRT_LANESTATS
 #define MRT_LANESTATS 0
 #endif
 #if MRT_LANESTATS
-constexpr int kLaneStats = 46;
+constexpr int kLaneStats = 48;
 __shared__ unsigned long long s_lanes[kBlock / 64][kLaneStats];
 __device__ unsigned long long g_lanes[kLaneStats];
 __device__ __forceinline__ void ls_add(int k, uint32_t v) {
@@ -786,18 +787,31 @@ __device__ __forceinline__ bool traverse(const DeviceScene& sc, const LdsCtx& cx
 // (DESIGN §2.1i).  The while-while walk parks a lane's first leaf and pushes
 // the rest before any h.t exists, so its culling removes almost nothing in a
 // shallow tree and the wave runs as many leaf rounds as its unluckiest lane.
-// Phase 1 tests every leaf box of the sweep list (DeviceScene::sweep; the
+// Phase 1 tests every box of the sweep list (DeviceScene::sweep: one record
+// per pair of triangles, sweep_pairs.h; the
 // records are wave-uniform: scalar loads into SGPRs, no VGPR or LDS traffic)
-// with the walk's own slab arithmetic and keeps, per lane, the two nearest leaves by
-// box entry as packed keys (entry bits with the low five cleared | leaf id:
-// non-negative floats order as unsigned integers, and lowering an entry only
-// culls less) and the other hit leaves as a bit mask.  Phase 2 tests the
-// nearest leaf, the second if its entry is within h.t (1 + 2^-11), then the
+// with the walk's own slab arithmetic and keeps, per lane, the kSweepKeys nearest records by
+// box entry as packed keys (entry bits with the sign and the low five cleared |
+// record id: non-negative floats order as unsigned integers, an entry of -0 is
+// +0, and lowering an entry only culls less) and the other hit records as a
+// bit mask.  Phase 2 tests the nearest record's triangles, the next keys' while
+// their entries are within h.t (1 + 2^-11), then the
 // masked ones, lowest id first, each culled by its recomputed entry under the
-// same rule.  The leaves tested are among those whose boxes the ray hits, and
-// a leaf left out lies behind h.t by more than the walk's own slack, so the
+// same rule.  A masked record's key is no smaller than the last key's, so its
+// entry is no smaller than that key's lowered one: the first key that is
+// missing or culled ends the lane with no pop (§2.1l; h.t only shrinks).
+// The triangles tested are among those whose boxes the ray hits, and
+// a record left out lies behind h.t by more than the walk's own slack, so the
 // answer is the walk's: the minimum of (t, prim) over the box-hit leaves'
-// triangles, independent of the order (§3.1).
+// triangles, independent of the order and of the grouping (§3.1).
+#ifndef MRT_SWEEP_KEYS    // keys kept per lane: 2; 3 was built and measured slower (A/B builds)
+#define MRT_SWEEP_KEYS 2
+#endif
+#ifndef MRT_SWEEP_EARLY   // a culled or missing key ends the lane (0: it pops its whole mask; A/B builds)
+#define MRT_SWEEP_EARLY 1
+#endif
+constexpr int kSweepKeys = MRT_SWEEP_KEYS;
+static_assert(kSweepKeys == 2 || kSweepKeys == 3, "MRT_SWEEP_KEYS");
 __device__ __forceinline__ bool sweep_box(float4 lo, float4 hi, V3 o, const RayBox& rb, float tmin, float& tnear) {
 #if MRT_PRECISE
   const float ox = o.x, oy = o.y, oz = o.z, oix = 0.0f, oiy = 0.0f, oiz = 0.0f;
@@ -815,25 +829,27 @@ __device__ __forceinline__ bool sweep_box(float4 lo, float4 hi, V3 o, const RayB
   return tnear <= tfar;
 }
 
-typedef float SweepRec __attribute__((ext_vector_type(8)));           // one leaf record
+typedef float SweepRec __attribute__((ext_vector_type(8)));           // one record
 typedef const __attribute__((address_space(4))) SweepRec* SweepList;   // constant address space: scalar loads
 
+// the triangles of a record (ref = ka | kb << 16, kb == ka: one): one pair, no loop
 template <int MODE>
 __device__ __forceinline__ void sweep_leaf(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
                                            uint32_t ref, Hit& h) {
   LS_ADD(4, 1);
   LS_ADD(5, ls_lanes());
-  const uint32_t lr = ~ref;
-  leaf_tests<MODE>(sc, cx, o, d, tmin, lr >> kLeafCountBits, (lr & (kMaxLeafSize - 1)) + 1, h, false, 0u, nullptr);
+  const uint32_t ka = ref & 0xFFFFu, kb = ref >> 16;
+  tri_pair<MODE>(sc, cx, o, d, tmin, ka, kb, kb != ka, h, false, 0u, nullptr);
 }
 
 // CAP (the stream kernel's queue levels): a pass makes at most
 // `cap` pops of the rest mask and returns the mask it leaves; the caller puts
 // a lane with a non-zero mask back on its queue with h as it stands, and a
 // later pass continues it with `resume` = that mask and h = that partial hit.
-// A resumed lane rides through phase 1 (wave-uniform) and ignores its keys;
-// it spends the two key rounds on its next two pops, so every pass clears a
-// bit of every unfinished lane's mask even with cap = 0.  The tested leaves
+// A resumed lane rides through phase 1 (wave-uniform) and ignores its keys
+// (it never takes their early-out: its mask is what an earlier pass left);
+// it spends the key rounds on its next pops, so every pass clears a
+// bit of every unfinished lane's mask even with cap = 0.  The tested records
 // and the cull rule are those of one uncapped pass, so is the answer.
 template <int MODE, bool CAP = false>
 __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
@@ -842,7 +858,8 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
   LS_ADD(0, ls_lanes());
   LS_ADD(1, 1);
   constexpr uint32_t kNone = 0xFFFFFFFFu;
-  uint32_t k1 = kNone, k2 = kNone, rest = 0u;   // rest: in phase 1 every leaf hit, then those beyond the pair
+  uint32_t key_of[3] = {kNone, kNone, kNone};   // ascending; [2] unused with two keys
+  uint32_t rest = 0u;   // in phase 1 every record hit, then those beyond the keys
   const uint32_t n = sc.sweep_leaves;
   const SweepList list = (SweepList)(uintptr_t)sc.sweep;
   for (uint32_t i = 0; i < n; ++i) {
@@ -858,16 +875,25 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
     float te;
     const bool hit = sweep_box(make_float4(rec[0], rec[1], rec[2], rec[3]), make_float4(rec[4], rec[5], rec[6], rec[7]),
                                o, rb, tmin, te);
-    // one v_bfi: entry bits above the leaf id (an entry of -0 sorts last and is never culled: still exact)
-    const uint32_t key = hit ? ((fbits(te) & ~31u) | (i & 31u)) : kNone;
-    const uint32_t mid = max(k1, key);
-    k1 = min(k1, key);
-    k2 = min(k2, mid);
+    // one v_bfi: entry bits, sign cleared (-0 sorts first, as +0 does), above the record id
+    const uint32_t key = hit ? ((fbits(te) & 0x7FFFFFE0u) | (i & 31u)) : kNone;
+    const uint32_t mid = max(key_of[0], key);
+    key_of[0] = min(key_of[0], key);
+    if (kSweepKeys == 3) {
+      key_of[2] = min(key_of[2], max(key_of[1], mid));
+      key_of[1] = min(key_of[1], mid);
+    } else {
+      key_of[1] = min(key_of[1], mid);
+    }
     rest |= (hit ? 1u : 0u) << (i & 31u);
   }
-  // the pair's leaves leave the mask (a lone hit: k2 is kNone, whose id bits name leaf 31 — not set, or k1's own)
-  rest &= ~((1u << (k1 & 31u)) | (1u << (k2 & 31u)));
-  // the lowest masked leaf leaves the mask: its reference, and whether its recomputed entry passes the cull
+  // the keys' records leave the mask (a missing key is kNone, whose id bits name record 31 — not set, or an earlier key's own)
+  {
+    uint32_t keyed = (1u << (key_of[0] & 31u)) | (1u << (key_of[1] & 31u));
+    if (kSweepKeys == 3) keyed |= 1u << (key_of[2] & 31u);
+    rest &= ~keyed;
+  }
+  // the lowest masked record leaves the mask: its triangles, and whether its recomputed entry passes the cull
   auto pop = [&](uint32_t& ref) {
     const uint32_t id = (uint32_t)__ffs((int)rest) - 1u;
     rest &= rest - 1u;
@@ -876,24 +902,27 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
     ref = fbits(blo.w);
     return sweep_box(blo, bhi, o, rb, tmin, te) && te <= h.t * kCullScale;
   };
-  if (!CAP) {
-    if (k1 != kNone) sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(g_lds[cx.sweep_base + 2u * (k1 & 31u)].w), h);
-    if (k2 != kNone && bitsf(k2 & ~31u) <= h.t * kCullScale)
-      sweep_leaf<MODE>(sc, cx, o, d, tmin, fbits(g_lds[cx.sweep_base + 2u * (k2 & 31u)].w), h);
-  } else {
-    if (resume) rest = resume;
+  if (CAP && resume) rest = resume;
 #pragma unroll
-    for (int round = 0; round < 2; ++round) {   // the key rounds, shared with the resumed lanes' pops
-      const uint32_t k = round == 0 ? k1 : k2;
-      bool test = k != kNone && (round == 0 || bitsf(k & ~31u) <= h.t * kCullScale);
-      uint32_t ref = 0u;
-      if (resume) {
-        test = false;
-        if (rest) test = pop(ref);
-      } else if (test) {
-        ref = fbits(g_lds[cx.sweep_base + 2u * (k & 31u)].w);
+  for (int round = 0; round < kSweepKeys; ++round) {   // the key rounds, shared with the resumed lanes' pops
+    const uint32_t k = key_of[round];
+    // (a missing key's entry bits are a NaN: it fails the cull)
+    bool test = round == 0 ? k != kNone : bitsf(k & ~31u) <= h.t * kCullScale;
+    uint32_t ref = 0u;
+    if (CAP && resume) {
+      test = false;
+      if (rest) test = pop(ref);
+    } else if (test) {
+      ref = fbits(g_lds[cx.sweep_base + 2u * (k & 31u)].w);
+    } else if (MRT_SWEEP_EARLY) {
+      rest = 0u;   // every masked record lies behind this key
+    }
+    if (test) {
+      if (round == 2) {
+        LS_ADD(46, 1);
+        LS_ADD(47, ls_lanes());
       }
-      if (test) sweep_leaf<MODE>(sc, cx, o, d, tmin, ref, h);
+      sweep_leaf<MODE>(sc, cx, o, d, tmin, ref, h);
     }
   }
   for (uint32_t c = 0; rest && (!CAP || c < cap); ++c) {

@@ -148,12 +148,16 @@ struct DeviceScene {
   float conv_obb[4][16];             // [kMaxConvex]
   uint32_t conv_face_tris[4][8];
   // leaf-box sweep (kernels.hip sweep_nearest): nearest queries of a
-  // whole-scene-in-LDS tree with at most kSweepLeaves leaves test every leaf
-  // box instead of walking the tree.  sweep = float4 x 2 per leaf of the main
-  // tree, interior nodes in index order and their slots in slot order:
-  // (lo.xyz, bits(leaf ref)), (hi.xyz, 0) — the padded child box as it stands
-  // in the leaf's parent node; a leaf's id is its position in the list.
-  // sweep_leaves == 0: the queries walk.  Last, so that no other field moves.
+  // whole-scene-in-LDS tree with at most kSweepLeaves leaves test a list of
+  // boxes instead of walking the tree.  sweep = float4 x 2 per record, one
+  // record per group of at most two triangles (sweep_pairs.h: a two-triangle
+  // leaf, two single-triangle leaves paired, or half a pair of a larger leaf),
+  // in the order of the leaves (interior nodes in index order, their slots in
+  // slot order): (lo.xyz, bits(ka | kb << 16)), (hi.xyz, 0) — the union of the
+  // members' padded child boxes as they stand in their parent nodes, and the
+  // two leaf-ordered triangles (kb == ka: one); a record's id is its position
+  // in the list.  sweep_leaves = the number of records (<= kSweepLeaves),
+  // 0: the queries walk.  Last, so that no other field moves.
   // sweep_cap: rest pops of one pass in the stream kernel's queue levels
   // before a lane with leaves left is recycled (kernels.hip bounce_wave;
   // >= kSweepLeaves: never); it fills the struct's tail padding.

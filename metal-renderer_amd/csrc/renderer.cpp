@@ -38,6 +38,7 @@
 #include "occluders.h"
 #include "primary.h"
 #include "scene.h"
+#include "sweep_pairs.h"
 #include "diag_env.h"
 
 namespace {
@@ -120,7 +121,9 @@ struct mrt_scene {
   // leaf-box sweep (mrt_layout.h DeviceScene::sweep): the main tree's leaf
   // records, 8 floats each (empty for a tree over kSweepLeaves leaves or a
   // leaf root), and whether nearest queries use them
-  std::vector<float> sweep_list;
+  // sweep_pairs: the list the kernels get, derived from it (sweep_pairs.h:
+  // one record per group of at most two triangles)
+  std::vector<float> sweep_list, sweep_pairs;
   bool sweep_on = false;
   uint32_t sweep_cap = mrt::kSweepCap;   // DeviceScene::sweep_cap
   DevBuf sweep;
@@ -1170,7 +1173,12 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
                                                      nd[4 + c], nd[12 + c], nd[20 + c], 0.0f});
     }
   }
-  const uint32_t sweep_leaves = (uint32_t)(s->sweep_list.size() / 8);
+  // the kernels' list: triangle pairs (MRT_SWEEP_PAIRS=0: no two leaves share
+  // a record); a non-default leaf size can push it over the cap: the scene walks
+  bool pair_singles = true;
+  if (const char* v = mrt::diag_env("MRT_SWEEP_PAIRS")) pair_singles = std::atoi(v) != 0;
+  mrt::sweep_pair_records(s->sweep_list, pair_singles, s->sweep_pairs);
+  const uint32_t sweep_leaves = (uint32_t)(s->sweep_pairs.size() / 8);
   const uint32_t up_occ_nodes = occ_on ? (uint32_t)(up_nodes.size() / 32) - s->bvh.num_nodes : 0u;
   if (sweep_leaves >= 1 && sweep_leaves <= mrt::kSweepLeaves && s->bvh.width == 4) {
     mrt::DeviceScene probe{};   // the counts the staging mode is chosen by
@@ -1262,7 +1270,7 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
   d.sweep_leaves = 0;
   d.sweep_cap = s->sweep_cap;
   if (s->sweep_on) {
-    HIP_TRY(upload(s->sweep, s->sweep_list.data(), s->sweep_list.size() * 4));
+    HIP_TRY(upload(s->sweep, s->sweep_pairs.data(), s->sweep_pairs.size() * 4));
     d.sweep = s->sweep.as<float>();
     d.sweep_leaves = sweep_leaves;
   }
@@ -1286,6 +1294,21 @@ int mrt_debug_sweep_list(const mrt_scene* scene, float* records, uint32_t capaci
   if (records) std::memcpy(records, scene->sweep_list.data(), (size_t)std::min(n, capacity) * 32);
   *count = n;
   *enabled = scene->sweep_on ? 1u : 0u;
+  return MRT_OK;
+}
+
+int mrt_debug_sweep_pairs(const mrt_scene* scene, float* records, uint32_t* prims, uint32_t capacity,
+                          uint32_t* count) {
+  if (!scene || !count) return fail(MRT_ERR_INVALID, "mrt_debug_sweep_pairs: null argument");
+  const uint32_t n = (uint32_t)(scene->sweep_pairs.size() / 8), m = std::min(n, capacity);
+  if (records) std::memcpy(records, scene->sweep_pairs.data(), (size_t)m * 32);
+  if (prims)
+    for (uint32_t i = 0; i < m; ++i) {
+      const uint32_t w = fbits(scene->sweep_pairs[8 * (size_t)i + 3]);
+      prims[2 * i] = fbits(scene->bvh.tris[12 * (size_t)(w & 0xFFFFu) + 3]);
+      prims[2 * i + 1] = fbits(scene->bvh.tris[12 * (size_t)(w >> 16) + 3]);
+    }
+  *count = n;
   return MRT_OK;
 }
 

@@ -26,6 +26,11 @@
 //   4. by the sweep with a cap on a pass's rest pops, unfinished rays going
 //      back on their level's queue (recycling): caps 0-3 and
 //      unbounded, on rays that are the same for every cap.
+//   5. by the sweep over triangle-pair records (sweep_pairs.h):
+//      A. single-triangle leaves paired, B. a culled or missing key ends the
+//      lane with no pop, C. a third key — each variant on the same waves, and
+//      on an adversarial set (origins inside and on the faces of the record
+//      boxes, with every zero entry forced to -0).
 // The sweep's (found, t, prim) is compared with the walk's for every ray, and
 // so is every recycled ray's once it finishes; no queue may pass kStreamCap.
 //
@@ -42,6 +47,7 @@
 
 #include "bvh.h"
 #include "scene.h"
+#include "sweep_pairs.h"
 
 using namespace mrt;
 
@@ -230,6 +236,75 @@ void sweep_wave(const Ray* rays, int n, Hit* out, SweepStats& st) {
   }
 }
 
+// 5. sweep_nearest over a list in the pair encoding (lo.w = ka | kb << 16):
+// `keys` keys kept (2 or 3), `early`: the first culled or missing key clears
+// the lane's mask, `neg_zero`: every zero entry of phase 1 is taken as -0
+// (the key clears the sign, so it sorts first as +0 does)
+struct PairStats { double calls = 0, rays = 0, tests = 0, leaf_rounds = 0, rest_leaf_rounds = 0, cull_rounds = 0, key3_rounds = 0, mismatches = 0; };
+void pairs_wave(const std::vector<float>& list, int keys, bool early, bool neg_zero, const Ray* rays, int n, Hit* out,
+                PairStats& st) {
+  const uint32_t N = (uint32_t)(list.size() / 8), kNone = 0xFFFFFFFFu;
+  uint32_t key[kWave][3], rest[kWave];
+  float inv[kWave][3];
+  st.calls += 1;
+  st.rays += n;
+  for (int l = 0; l < n; ++l) {
+    key[l][0] = key[l][1] = key[l][2] = kNone; rest[l] = 0; out[l] = Hit();
+    for (int a = 0; a < 3; ++a) inv[l][a] = safe_inv(rays[l].d[a]);
+    for (uint32_t i = 0; i < N; ++i) {
+      float te;
+      const bool hit = box_entry(rays[l], inv[l], &list[8 * i], &list[8 * i + 4], te);
+      if (neg_zero && te == 0.0f) te = -0.0f;
+      const uint32_t k = hit ? ((fb(te) & 0x7FFFFFE0u) | i) : kNone;
+      const uint32_t mid = std::max(key[l][0], k);
+      key[l][0] = std::min(key[l][0], k);
+      if (keys == 3) key[l][2] = std::min(key[l][2], std::max(key[l][1], mid));
+      key[l][1] = std::min(key[l][1], mid);
+      if (hit) rest[l] |= 1u << i;
+    }
+    for (int k = 0; k < keys; ++k) rest[l] &= ~(1u << (key[l][k] & 31u));
+  }
+  auto test = [&](int l, uint32_t id) {
+    const uint32_t w = fb(list[8 * id + 3]), ka = w & 0xFFFFu, kb = w >> 16;
+    tri_test(rays[l], ka, out[l]);
+    if (kb != ka) tri_test(rays[l], kb, out[l]);
+    st.tests += 1;
+  };
+  for (int round = 0; round < keys; ++round) {
+    bool any = false;
+    for (int l = 0; l < n; ++l) {
+      const uint32_t k = key[l][round];
+      const bool pass = round == 0 ? k != kNone : bf(k & ~31u) <= out[l].t * kCull;
+      if (pass) { any = true; test(l, k & 31u); }
+      else if (early) rest[l] = 0;
+    }
+    st.leaf_rounds += any;
+    if (round == 2) st.key3_rounds += any;
+  }
+  for (;;) {
+    bool more = false, any = false;
+    for (int l = 0; l < n; ++l) if (rest[l]) {
+      more = true;
+      const uint32_t id = (uint32_t)__builtin_ctz(rest[l]);
+      rest[l] &= rest[l] - 1;
+      float te;
+      if (box_entry(rays[l], inv[l], &list[8 * id], &list[8 * id + 4], te) && te <= out[l].t * kCull) { any = true; test(l, id); }
+    }
+    if (!more) break;
+    st.cull_rounds += 1;
+    st.leaf_rounds += any;
+    st.rest_leaf_rounds += any;
+  }
+}
+std::vector<float> g_pairs, g_unpaired;   // sweep_pairs.h: the kernels' list, and one record per leaf in its encoding
+struct PairVariant { const char* name; const std::vector<float>* list; int keys; bool early; };
+const PairVariant kPairVariants[6] = {
+    {"today", &g_unpaired, 2, false},   {"A", &g_pairs, 2, false},         {"B alone", &g_unpaired, 2, true},
+    {"A + B", &g_pairs, 2, true},       {"A + B + C", &g_pairs, 3, true},  {"B + C without A", &g_unpaired, 3, true}};
+bool differs(const Hit& a, const Hit& b) {
+  return a.found != b.found || (a.found && (fb(a.t) != fb(b.t) || a.prim != b.prim));
+}
+
 // leaves in order of box entry, culled against the hit so far: tests per ray,
 // and the leaf boxes hit with no culling at all
 struct OrderStats { double rays = 0, waves = 0, tests = 0, wave_max = 0, boxes = 0; };
@@ -303,6 +378,7 @@ struct Totals {
   WalkStats walk, sorted;
   SweepStats sweep;
   OrderStats ordered;
+  PairStats pairs[6];
 };
 
 // one wave of bounce-`level` rays: every query shape on the same rays
@@ -316,6 +392,63 @@ void run_wave(const std::vector<Ray>& w, Totals& T, Hit* hits, bool stats_only_w
   sweep_wave(w.data(), n, tmp, T.sweep);
   for (int l = 0; l < n; ++l)
     T.sweep.mismatches += tmp[l].found != hits[l].found || (tmp[l].found && (fb(tmp[l].t) != fb(hits[l].t) || tmp[l].prim != hits[l].prim));
+  for (int v = 0; v < 6; ++v) {
+    const PairVariant& pv = kPairVariants[v];
+    pairs_wave(*pv.list, pv.keys, pv.early, false, w.data(), n, tmp, T.pairs[v]);
+    for (int l = 0; l < n; ++l) T.pairs[v].mismatches += differs(tmp[l], hits[l]);
+  }
+}
+
+// 5. the adversarial set: origins at the centre, at the face centres, inside
+// and on the faces of every record box, eight directions each; every variant,
+// with phase 1's zero entries as they come and forced to -0
+void adversarial(double& rays, double& mismatches) {
+  std::vector<Ray> set;
+  g_rng = 0xD1B54A32D192ED03ull;
+  auto dirs = [&](const float* o) {
+    for (int k = 0; k < 8; ++k) {
+      Ray r;
+      float len;
+      do {
+        for (int a = 0; a < 3; ++a) r.d[a] = 2.0f * rnd() - 1.0f;
+        len = std::sqrt(tdot(r.d, r.d));
+      } while (!(len > 1e-3f) || len > 1.0f);
+      for (int a = 0; a < 3; ++a) { r.o[a] = o[a]; r.d[a] /= len; }
+      if (k == 0) r.d[1] = r.d[2] = 0.0f, r.d[0] = 1.0f;   // along an axis: the other slabs' planes at infinity
+      set.push_back(r);
+    }
+  };
+  for (const std::vector<float>* list : {&g_pairs, &g_unpaired})
+    for (size_t i = 0; i < list->size() / 8; ++i) {
+      const float *lo = &(*list)[8 * i], *hi = lo + 4;
+      float o[3];
+      for (int a = 0; a < 3; ++a) o[a] = 0.5f * (lo[a] + hi[a]);
+      dirs(o);
+      for (int f = 0; f < 6; ++f) {   // face centres, then random points of the faces
+        for (int rep = 0; rep < 3; ++rep) {
+          for (int a = 0; a < 3; ++a) o[a] = rep == 0 ? 0.5f * (lo[a] + hi[a]) : lo[a] + (hi[a] - lo[a]) * rnd();
+          o[f / 2] = (f & 1) ? hi[f / 2] : lo[f / 2];
+          dirs(o);
+        }
+      }
+      for (int rep = 0; rep < 6; ++rep) {   // inside
+        for (int a = 0; a < 3; ++a) o[a] = lo[a] + (hi[a] - lo[a]) * rnd();
+        dirs(o);
+      }
+    }
+  WalkStats scratch;
+  Hit ref[kWave], tmp[kWave];
+  for (size_t at = 0; at < set.size(); at += kWave) {
+    const int n = (int)std::min<size_t>(kWave, set.size() - at);
+    walk_wave(&set[at], n, ref, scratch, false);
+    rays += n;
+    for (int v = 0; v < 6; ++v)
+      for (int nz = 0; nz < 2; ++nz) {
+        PairStats ps;
+        pairs_wave(*kPairVariants[v].list, kPairVariants[v].keys, kPairVariants[v].early, nz != 0, &set[at], n, tmp, ps);
+        for (int l = 0; l < n; ++l) mismatches += differs(tmp[l], ref[l]);
+      }
+  }
 }
 
 // the wave-local queue policy over `blocks` camera blocks; bins = 1 or 8 (octant)
@@ -536,6 +669,8 @@ int main(int argc, char** argv) {
       if ((int32_t)fb(nd[24 + c]) < 0)
         g_sweep.insert(g_sweep.end(), {nd[c], nd[8 + c], nd[16 + c], nd[24 + c], nd[4 + c], nd[12 + c], nd[20 + c], 0.0f});
   }
+  sweep_pair_records(g_sweep, true, g_pairs);
+  sweep_pair_records(g_sweep, false, g_unpaired);
   std::printf("%zu triangles, %u nodes, %u leaves, %d camera blocks\n", sc.references.size(), g_bvh.num_nodes,
               g_bvh.num_leaves, blocks);
   Totals T, B[2];
@@ -583,5 +718,23 @@ int main(int argc, char** argv) {
       max_queue = std::max(max_queue, r.max_queue);
     }
   std::printf("recycling vs walk: mismatches %.0f, longest queue %u of %d slots\n", bad, max_queue, kStreamCap);
+  // 5. triangle-pair records, the culled-key early-out, the third key
+  std::printf("5. triangle-pair records: %u leaves -> %zu records (per sweep call)\n", g_bvh.num_leaves, g_pairs.size() / 8);
+  double pair_bad = 0;
+  for (int v = 0; v < 6; ++v) {
+    const PairStats& ps = T.pairs[v];
+    std::printf("   %-16s %2zu records; leaf rounds %.2f (%.2f out of the rest mask), cull rounds %.2f, third key rounds %.2f; "
+                "%.3f pair tests/ray; mismatches %.0f of %.0f\n",
+                kPairVariants[v].name, kPairVariants[v].list->size() / 8, ps.leaf_rounds / ps.calls,
+                ps.rest_leaf_rounds / ps.calls, ps.cull_rounds / ps.calls, ps.key3_rounds / ps.calls, ps.tests / ps.rays,
+                ps.mismatches, ps.rays);
+    pair_bad += ps.mismatches;
+  }
+  double adv_rays = 0, adv_bad = 0;
+  adversarial(adv_rays, adv_bad);
+  std::printf("   adversarial: %.0f rays from inside and on the faces of the record boxes, every variant, zero entries as "
+              "they come and forced to -0: mismatches %.0f\n", adv_rays, adv_bad);
+  std::printf("pairs vs walk: rays %.0f mismatches %.0f ; adversarial rays %.0f mismatches %.0f\n", T.pairs[4].rays, pair_bad,
+              adv_rays, adv_bad);
   return s.mismatches == 0 && bad == 0 && max_queue <= (uint32_t)kStreamCap ? 0 : 2;
 }
