@@ -680,6 +680,15 @@ int mrt_debug_sweep_list(const mrt_scene* scene, float* records, uint32_t capaci
  * a record. */
 int mrt_debug_sweep_pairs(const mrt_scene* scene, float* records, uint32_t* prims, uint32_t capacity,
                           uint32_t* count);
+/* Test entry: phase 1's list of a scene whose nearest queries sweep (none, and
+ * *count = 0, for one that walks) — one record per record of
+ * mrt_debug_sweep_pairs, in its order, of which min(*count, capacity) are
+ * copied to `records` (may be NULL) as 8 floats each: (c.xyz, bits(id)),
+ * (e.xyz, bits(1 << id)), the centre and half-extent of the record's box with
+ * [c - e, c + e] containing [lo, hi] on every axis in exact arithmetic and e
+ * the smallest such float.  The fast build's phase 1 tests these (three fused
+ * multiply-adds per axis); phase 2 and the precise build keep lo / hi. */
+int mrt_debug_sweep_phase1(const mrt_scene* scene, float* records, uint32_t capacity, uint32_t* count);
 /* Test entry: the rest pops one pass of the stream kernel's queue levels makes
  * before it recycles a ray with leaves left to test (kernels.hip bounce_wave),
  * for a scene whose nearest queries sweep.  32: never, the default (every cap

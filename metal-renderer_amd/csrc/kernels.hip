@@ -832,6 +832,30 @@ __device__ __forceinline__ bool sweep_box(float4 lo, float4 hi, V3 o, const RayB
 typedef float SweepRec __attribute__((ext_vector_type(8)));           // one record
 typedef const __attribute__((address_space(4))) SweepRec* SweepList;   // constant address space: scalar loads
 
+#ifndef MRT_SWEEP_PRED     // phase 1 keeps its keys and mask in the lanes that hit only: 2 under v_cmpx with no branch
+#define MRT_SWEEP_PRED 2   // (the fast build's centre form with two keys; elsewhere as 1), 1 the compiler's
+#endif                     // exec-masked block, 0 selects in every lane (A/B builds)
+#ifndef MRT_SWEEP_CENTRE   // fast build: phase 1 tests centre / half-extent records (0: the lo / hi records; A/B builds)
+#define MRT_SWEEP_CENTRE 1
+#endif
+// Phase 1's slab test on a record of the centre list (sweep_pairs.h
+// sweep_phase1_records: c.xyz, bits(id), e.xyz, bits(1 << id), with
+// [c - e, c + e] containing the record's padded [lo, hi]): three fma per axis,
+// no min / max to order the planes — the half-extent times |inv| is the
+// distance from the centre's plane to either, whatever the ray's sign.  One
+// rounding more than sweep_box, inside the boxes' padding:
+// conservative, which is all phase 1 needs; pop() re-tests with sweep_box.
+#if !MRT_PRECISE   // (the precise build keeps the lo / hi records)
+__device__ __forceinline__ bool sweep_centre(SweepRec rec, const RayBox& rb, float tmin, float& tnear, float& tfar) {
+  const float ax = fmaf(rec[0], rb.inv.x, -rb.oinv.x), ay = fmaf(rec[1], rb.inv.y, -rb.oinv.y),
+              az = fmaf(rec[2], rb.inv.z, -rb.oinv.z);
+  const float ix = fabsf(rb.inv.x), iy = fabsf(rb.inv.y), iz = fabsf(rb.inv.z);
+  tnear = fmaxf(fmaxf(fmaf(-rec[4], ix, ax), fmaf(-rec[5], iy, ay)), fmaxf(fmaf(-rec[6], iz, az), tmin));
+  tfar = fminf(fminf(fmaf(rec[4], ix, ax), fmaf(rec[5], iy, ay)), fmaf(rec[6], iz, az));
+  return tnear <= tfar;
+}
+#endif
+
 // the triangles of a record (ref = ka | kb << 16, kb == ka: one): one pair, no loop
 template <int MODE>
 __device__ __forceinline__ void sweep_leaf(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
@@ -861,7 +885,18 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
   uint32_t key_of[3] = {kNone, kNone, kNone};   // ascending; [2] unused with two keys
   uint32_t rest = 0u;   // in phase 1 every record hit, then those beyond the keys
   const uint32_t n = sc.sweep_leaves;
+#if MRT_SWEEP_CENTRE && !MRT_PRECISE
+  // the centre list stands kSweepLeaves records behind the lo / hi one, in the same buffer
+  const SweepList list = (SweepList)(uintptr_t)sc.sweep + kSweepLeaves;
+#else
   const SweepList list = (SweepList)(uintptr_t)sc.sweep;
+#endif
+#if MRT_SWEEP_PRED
+  // the key's entry mask in a vector register: v_and_or takes one scalar
+  // operand, the record id (as a literal the mask costs an instruction of its own per record)
+  uint32_t key_mask = 0x7FFFFFE0u;
+  asm volatile("" : "+v"(key_mask));
+#endif
   for (uint32_t i = 0; i < n; ++i) {
     // (no record loaded ahead: the eight more scalar registers of a second
     // record cost the stream kernel scalar spills inside this loop, and the
@@ -873,8 +908,55 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
     LS_T1(42);
 #endif
     float te;
+#if MRT_SWEEP_CENTRE && !MRT_PRECISE
+    float tf;
+    [[maybe_unused]] const bool hit = sweep_centre(rec, rb, tmin, te, tf);
+    const uint32_t bit = fbits(rec[7]);   // 1 << i, from the record
+#else
     const bool hit = sweep_box(make_float4(rec[0], rec[1], rec[2], rec[3]), make_float4(rec[4], rec[5], rec[6], rec[7]),
                                o, rb, tmin, te);
+    const uint32_t bit = 1u << (i & 31u);
+#endif
+#if MRT_SWEEP_PRED == 2 && MRT_SWEEP_CENTRE && !MRT_PRECISE && MRT_SWEEP_KEYS == 2
+    // the same block with no branch: v_cmpx narrows exec to the lanes that hit,
+    // the five instructions run (in no lane, if none hit), exec comes back
+    {
+      uint32_t key, mid;
+      uint64_t saved;
+      asm volatile(
+          "s_mov_b64 %[sv], exec\n\t"
+          "v_cmpx_le_f32_e32 vcc, %[te], %[tf]\n\t"
+          "v_and_or_b32 %[key], %[te], %[mask], %[id]\n\t"
+          "v_or_b32_e32 %[rest], %[bit], %[rest]\n\t"
+          "v_max_u32_e32 %[mid], %[k0], %[key]\n\t"
+          "v_min_u32_e32 %[k0], %[k0], %[key]\n\t"
+          "v_min_u32_e32 %[k1], %[k1], %[mid]\n\t"
+          "s_mov_b64 exec, %[sv]"
+          : [sv] "=&s"(saved), [key] "=&v"(key), [mid] "=&v"(mid), [k0] "+v"(key_of[0]), [k1] "+v"(key_of[1]),
+            [rest] "+v"(rest)
+          : [te] "v"(te), [tf] "v"(tf), [mask] "v"(key_mask), [id] "s"(i), [bit] "s"(bit)
+          : "vcc");
+    }
+#elif MRT_SWEEP_PRED
+    // the bookkeeping runs in the lanes that hit only: the same keys and mask
+    // as the selects below give (a miss's kNone changes no key), in an
+    // exec-masked block of five VALU instead of eight in every lane
+    if (hit) {
+      // entry bits, sign cleared (-0 sorts first, as +0 does), above the record id
+      // (i < n <= kSweepLeaves = 32 is the id as it stands; one v_and_or with the mask from its register)
+      uint32_t key = (fbits(te) & key_mask) | i;
+      asm volatile("" : "+v"(key));   // (keeps the block: without it the compiler turns it back into selects)
+      const uint32_t mid = max(key_of[0], key);
+      key_of[0] = min(key_of[0], key);
+      if (kSweepKeys == 3) {
+        key_of[2] = min(key_of[2], max(key_of[1], mid));
+        key_of[1] = min(key_of[1], mid);
+      } else {
+        key_of[1] = min(key_of[1], mid);
+      }
+      rest |= bit;
+    }
+#else
     // one v_bfi: entry bits, sign cleared (-0 sorts first, as +0 does), above the record id
     const uint32_t key = hit ? ((fbits(te) & 0x7FFFFFE0u) | (i & 31u)) : kNone;
     const uint32_t mid = max(key_of[0], key);
@@ -885,7 +967,8 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
     } else {
       key_of[1] = min(key_of[1], mid);
     }
-    rest |= (hit ? 1u : 0u) << (i & 31u);
+    rest |= hit ? bit : 0u;
+#endif
   }
   // the keys' records leave the mask (a missing key is kNone, whose id bits name record 31 — not set, or an earlier key's own)
   {

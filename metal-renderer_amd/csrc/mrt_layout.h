@@ -158,6 +158,10 @@ struct DeviceScene {
   // two leaf-ordered triangles (kb == ka: one); a record's id is its position
   // in the list.  sweep_leaves = the number of records (<= kSweepLeaves),
   // 0: the queries walk.  Last, so that no other field moves.
+  // Phase 1's centre list (sweep_pairs.h sweep_phase1_records: (c.xyz,
+  // bits(id)), (e.xyz, bits(1 << id)) per record) stands in the same buffer,
+  // kSweepLeaves records behind the first list — a constant offset, so that
+  // the struct and with it every kernel's argument offsets stay as they are.
   // sweep_cap: rest pops of one pass in the stream kernel's queue levels
   // before a lane with leaves left is recycled (kernels.hip bounce_wave;
   // >= kSweepLeaves: never); it fills the struct's tail padding.

@@ -123,7 +123,9 @@ struct mrt_scene {
   // leaf root), and whether nearest queries use them
   // sweep_pairs: the list the kernels get, derived from it (sweep_pairs.h:
   // one record per group of at most two triangles)
-  std::vector<float> sweep_list, sweep_pairs;
+  // sweep_phase1: phase 1's centre / half-extent record of each of them
+  // (sweep_pairs.h sweep_phase1_records), for a scene that sweeps
+  std::vector<float> sweep_list, sweep_pairs, sweep_phase1;
   bool sweep_on = false;
   uint32_t sweep_cap = mrt::kSweepCap;   // DeviceScene::sweep_cap
   DevBuf sweep;
@@ -1194,6 +1196,7 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
     s->sweep_on = !mrt::fast::path_preferred(probe);
   }
   if (const char* v = mrt::diag_env("MRT_SWEEP")) s->sweep_on = s->sweep_on && std::atoi(v) != 0;
+  if (s->sweep_on) mrt::sweep_phase1_records(s->sweep_pairs, s->sweep_phase1);
   // rest pops per pass of the stream kernel's queue levels before a ray is
   // recycled (MRT_SWEEP_CAP: kSweepLeaves or more never recycles — the uncapped sweep)
   if (const char* v = mrt::diag_env("MRT_SWEEP_CAP"))
@@ -1270,7 +1273,11 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
   d.sweep_leaves = 0;
   d.sweep_cap = s->sweep_cap;
   if (s->sweep_on) {
-    HIP_TRY(upload(s->sweep, s->sweep_pairs.data(), s->sweep_pairs.size() * 4));
+    // both lists in one buffer: the records, then at kSweepLeaves records phase 1's centre list
+    std::vector<float> both(8 * (size_t)mrt::kSweepLeaves + s->sweep_phase1.size(), 0.0f);
+    std::copy(s->sweep_pairs.begin(), s->sweep_pairs.end(), both.begin());
+    std::copy(s->sweep_phase1.begin(), s->sweep_phase1.end(), both.begin() + 8 * (size_t)mrt::kSweepLeaves);
+    HIP_TRY(upload(s->sweep, both.data(), both.size() * 4));
     d.sweep = s->sweep.as<float>();
     d.sweep_leaves = sweep_leaves;
   }
@@ -1308,6 +1315,14 @@ int mrt_debug_sweep_pairs(const mrt_scene* scene, float* records, uint32_t* prim
       prims[2 * i] = fbits(scene->bvh.tris[12 * (size_t)(w & 0xFFFFu) + 3]);
       prims[2 * i + 1] = fbits(scene->bvh.tris[12 * (size_t)(w >> 16) + 3]);
     }
+  *count = n;
+  return MRT_OK;
+}
+
+int mrt_debug_sweep_phase1(const mrt_scene* scene, float* records, uint32_t capacity, uint32_t* count) {
+  if (!scene || !count) return fail(MRT_ERR_INVALID, "mrt_debug_sweep_phase1: null argument");
+  const uint32_t n = (uint32_t)(scene->sweep_phase1.size() / 8);
+  if (records) std::memcpy(records, scene->sweep_phase1.data(), (size_t)std::min(n, capacity) * 32);
   *count = n;
   return MRT_OK;
 }

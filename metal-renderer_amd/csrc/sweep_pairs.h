@@ -18,6 +18,7 @@
 // triangles.  Header-only: the library and tools/walk_model.cpp share it.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -86,6 +87,40 @@ inline void sweep_pair_records(const std::vector<float>& leaves, bool pair_singl
       continue;
     }
     for (uint32_t k = 0; k < cnt; k += 2) emit(lo, hi, f + k, f + std::min(k + 1, cnt - 1));
+  }
+}
+
+// Phase 1's list (kernels.hip sweep_centre): record i of
+// `pairs` as (c.xyz, bits(i), e.xyz, bits(1 << i)) — centre and half-extent
+// per axis with [c - e, c + e] containing [lo, hi] in exact arithmetic.  c is
+// the rounded midpoint and e the smallest float that is at least
+// max(c - lo, hi - c): the double differences are checked with their exact
+// rounding errors (two-sum) and e is stepped up with nextafter until it holds.
+// The fast build's phase 1 reads this list; phase 2 and the precise build
+// keep `pairs`.
+inline void sweep_phase1_records(const std::vector<float>& pairs, std::vector<float>& out) {
+  out.clear();
+  // a - b > e in exact arithmetic, for values of floats: a - b = s + err exactly (two-sum)
+  auto exceeds = [](double a, double b, double e) {
+    const double y = -b, s = a + y, a1 = s - y, y1 = s - a1, err = (a - a1) + (y - y1);
+    return s > e || (s == e && err > 0.0);
+  };
+  const size_t n = pairs.size() / 8;
+  for (size_t i = 0; i < n; ++i) {
+    const float *lo = &pairs[8 * i], *hi = lo + 4;
+    float c[3], e[3];
+    for (int a = 0; a < 3; ++a) {
+      c[a] = (float)(0.5 * ((double)lo[a] + (double)hi[a]));
+      e[a] = (float)std::max((double)c[a] - (double)lo[a], (double)hi[a] - (double)c[a]);
+      auto holds = [&](float x) { return !exceeds(c[a], lo[a], x) && !exceeds(hi[a], c[a], x); };
+      while (!holds(e[a])) e[a] = std::nextafter(e[a], INFINITY);
+      while (e[a] > 0.0f && holds(std::nextafter(e[a], 0.0f))) e[a] = std::nextafter(e[a], 0.0f);   // (the cast rounded up)
+    }
+    const uint32_t id = (uint32_t)i, bit = 1u << (i & 31u);
+    float idf, bitf;
+    std::memcpy(&idf, &id, 4);
+    std::memcpy(&bitf, &bit, 4);
+    out.insert(out.end(), {c[0], c[1], c[2], idf, e[0], e[1], e[2], bitf});
   }
 }
 

@@ -232,7 +232,7 @@ EXPORTED = [
     "mrt_renderer_exchange_flush", "mrt_renderer_tiles_read", "mrt_renderer_tiles_write",
     "mrt_image_load_exr", "mrt_renderer_load_reference", "mrt_renderer_display",
     "mrt_renderer_display_enqueue", "mrt_renderer_display_map",
-    "mrt_debug_lanes", "mrt_debug_sweep_list", "mrt_debug_sweep_pairs", "mrt_debug_sweep_cap", "mrt_debug_bvh_nodes", "mrt_debug_exchange_unpack", "mrt_debug_box_margin",
+    "mrt_debug_lanes", "mrt_debug_sweep_list", "mrt_debug_sweep_pairs", "mrt_debug_sweep_phase1", "mrt_debug_sweep_cap", "mrt_debug_bvh_nodes", "mrt_debug_exchange_unpack", "mrt_debug_box_margin",
     "mrt_debug_magic_div", "mrt_comm_set_timeout", "mrt_comm_check", "mrt_debug_comm_fail",
     "mrt_camera_default", "mrt_camera_look_at", "mrt_camera_check", "mrt_raygen_camera",
     "mrt_renderer_set_camera", "mrt_renderer_get_camera",
@@ -297,6 +297,7 @@ def lib() -> ctypes.CDLL:
         "mrt_debug_lanes": [vp, ctypes.c_size_t, c_int],
         "mrt_debug_sweep_list": [vp, vp, u32, vp, vp],
         "mrt_debug_sweep_pairs": [vp, vp, vp, u32, vp],
+        "mrt_debug_sweep_phase1": [vp, vp, u32, vp],
         "mrt_debug_sweep_cap": [vp, vp],
         "mrt_debug_bvh_nodes": [vp, vp, u32, vp],
         "mrt_debug_exchange_unpack": [vp, u32, vp, ctypes.c_size_t],
@@ -948,6 +949,18 @@ def debug_sweep_pairs(scene: "Scene"):
            "mrt_debug_sweep_pairs")
     n = min(count.value, len(out))
     return out[:n].copy(), prims[:n].copy()
+
+
+def debug_sweep_phase1(scene: "Scene"):
+    """Phase 1's list of a scene that sweeps (test entry): an (n, 8) uint32
+    view of the float records (c.xyz, id, e.xyz, 1 << id), one per record of
+    debug_sweep_pairs in its order; empty for a scene whose queries walk."""
+    import numpy as np
+    out = np.zeros((32, 8), np.uint32)
+    count = ctypes.c_uint32()
+    _check(lib().mrt_debug_sweep_phase1(scene.handle, ctypes.c_void_p(out.ctypes.data), len(out), ctypes.byref(count)),
+           "mrt_debug_sweep_phase1")
+    return out[:min(count.value, len(out))].copy()
 
 
 def debug_sweep_cap(scene: "Scene") -> int:

@@ -31,6 +31,11 @@
 //      lane with no pop, C. a third key — each variant on the same waves, and
 //      on an adversarial set (origins inside and on the faces of the record
 //      boxes, with every zero entry forced to -0).
+//   6. by the sweep with phase 1 on centre / half-extent records in the fast
+//      build's arithmetic, on part 5's rays and on the
+//      adversarial set extended by directions with components 0, -0, +-1e-20;
+//      no record holding a triangle the ray hits may be missed, and no key may
+//      lie beyond that triangle's cull bound.
 // The sweep's (found, t, prim) is compared with the walk's for every ray, and
 // so is every recycled ray's once it finishes; no queue may pass kStreamCap.
 //
@@ -305,6 +310,85 @@ bool differs(const Hit& a, const Hit& b) {
   return a.found != b.found || (a.found && (fb(a.t) != fb(b.t) || a.prim != b.prim));
 }
 
+// 6. phase 1 on the centre list (kernels.hip sweep_centre), in
+// the fast build's arithmetic: a = fma(c, inv, -o inv), near / far =
+// fma(-+e, |inv|, a) per axis.  Phase 2 is the product's (two keys, the
+// early-out, pops re-tested on lo / hi with the fast build's slab form).  Per
+// ray and record it also counts: records the lo / hi test hits (in either
+// build's arithmetic) and the centre test misses, those of them holding a
+// triangle the ray hits, and records whose lowered key lies beyond the cull
+// bound of a triangle of theirs the ray hits.
+std::vector<float> g_phase1;   // sweep_pairs.h sweep_phase1_records of g_pairs
+struct Phase1Stats { double rays = 0, boxes = 0, extra = 0, missed = 0, missed_with_hit = 0, late_keys = 0, mismatches = 0; };
+bool box_entry_fast(const Ray& r, const float* inv, const float* lo, const float* hi, float& tn) {
+  float n[3], f[3];
+  for (int a = 0; a < 3; ++a) {
+    const float oinv = r.o[a] * inv[a], t0 = std::fmaf(lo[a], inv[a], -oinv), t1 = std::fmaf(hi[a], inv[a], -oinv);
+    n[a] = std::fmin(t0, t1);
+    f[a] = std::fmax(t0, t1);
+  }
+  tn = std::fmax(std::fmax(n[0], n[1]), std::fmax(n[2], 0.0f));
+  return tn <= std::fmin(std::fmin(f[0], f[1]), f[2]);
+}
+bool centre_entry(const Ray& r, const float* inv, const float* c, const float* e, float& tn) {
+  float n[3], f[3];
+  for (int a = 0; a < 3; ++a) {
+    const float oinv = r.o[a] * inv[a], m = std::fmaf(c[a], inv[a], -oinv), ia = std::fabs(inv[a]);
+    n[a] = std::fmaf(-e[a], ia, m);
+    f[a] = std::fmaf(e[a], ia, m);
+  }
+  tn = std::fmax(std::fmax(n[0], n[1]), std::fmax(n[2], 0.0f));
+  return tn <= std::fmin(std::fmin(f[0], f[1]), f[2]);
+}
+void phase1_wave(bool neg_zero, const Ray* rays, int n, Hit* out, Phase1Stats& st) {
+  const std::vector<float>& list = g_pairs;
+  const uint32_t N = (uint32_t)(list.size() / 8), kNone = 0xFFFFFFFFu;
+  st.rays += n;
+  for (int l = 0; l < n; ++l) {
+    const Ray& r = rays[l];
+    uint32_t key[2] = {kNone, kNone}, rest = 0;
+    float inv[3];
+    out[l] = Hit();
+    for (int a = 0; a < 3; ++a) inv[a] = safe_inv(r.d[a]);
+    auto tris = [&](uint32_t id, Hit& h) {
+      const uint32_t w = fb(list[8 * id + 3]), ka = w & 0xFFFFu, kb = w >> 16;
+      tri_test(r, ka, h);
+      if (kb != ka) tri_test(r, kb, h);
+    };
+    for (uint32_t i = 0; i < N; ++i) {
+      float te, t_old;
+      const bool hit = centre_entry(r, inv, &g_phase1[8 * i], &g_phase1[8 * i + 4], te);
+      const bool old = box_entry(r, inv, &list[8 * i], &list[8 * i + 4], t_old) ||
+                       box_entry_fast(r, inv, &list[8 * i], &list[8 * i + 4], t_old);
+      if (neg_zero && te == 0.0f) te = -0.0f;
+      const uint32_t k = hit ? ((fb(te) & 0x7FFFFFE0u) | i) : kNone;
+      Hit own;   // the record's own triangles, with no other hit to cull them
+      tris(i, own);
+      st.boxes += old;
+      st.extra += hit && !old;
+      st.missed += old && !hit;
+      st.missed_with_hit += !hit && own.found;
+      st.late_keys += hit && own.found && !(bf(k & ~31u) <= own.t * kCull);
+      const uint32_t mid = std::max(key[0], k);
+      key[0] = std::min(key[0], k);
+      key[1] = std::min(key[1], mid);
+      if (hit) rest |= 1u << i;
+    }
+    rest &= ~((1u << (key[0] & 31u)) | (1u << (key[1] & 31u)));
+    for (int round = 0; round < 2; ++round) {
+      const uint32_t k = key[round];
+      if (round == 0 ? k != kNone : bf(k & ~31u) <= out[l].t * kCull) tris(k & 31u, out[l]);
+      else rest = 0;
+    }
+    while (rest) {
+      const uint32_t id = (uint32_t)__builtin_ctz(rest);
+      rest &= rest - 1;
+      float te;
+      if (box_entry_fast(r, inv, &list[8 * id], &list[8 * id + 4], te) && te <= out[l].t * kCull) tris(id, out[l]);
+    }
+  }
+}
+
 // leaves in order of box entry, culled against the hit so far: tests per ray,
 // and the leaf boxes hit with no culling at all
 struct OrderStats { double rays = 0, waves = 0, tests = 0, wave_max = 0, boxes = 0; };
@@ -379,6 +463,7 @@ struct Totals {
   SweepStats sweep;
   OrderStats ordered;
   PairStats pairs[6];
+  Phase1Stats phase1;
 };
 
 // one wave of bounce-`level` rays: every query shape on the same rays
@@ -397,12 +482,14 @@ void run_wave(const std::vector<Ray>& w, Totals& T, Hit* hits, bool stats_only_w
     pairs_wave(*pv.list, pv.keys, pv.early, false, w.data(), n, tmp, T.pairs[v]);
     for (int l = 0; l < n; ++l) T.pairs[v].mismatches += differs(tmp[l], hits[l]);
   }
+  phase1_wave(false, w.data(), n, tmp, T.phase1);
+  for (int l = 0; l < n; ++l) T.phase1.mismatches += differs(tmp[l], hits[l]);
 }
 
 // 5. the adversarial set: origins at the centre, at the face centres, inside
 // and on the faces of every record box, eight directions each; every variant,
 // with phase 1's zero entries as they come and forced to -0
-void adversarial(double& rays, double& mismatches) {
+std::vector<Ray> adversarial_set() {
   std::vector<Ray> set;
   g_rng = 0xD1B54A32D192ED03ull;
   auto dirs = [&](const float* o) {
@@ -436,6 +523,10 @@ void adversarial(double& rays, double& mismatches) {
         dirs(o);
       }
     }
+  return set;
+}
+void adversarial(double& rays, double& mismatches) {
+  const std::vector<Ray> set = adversarial_set();
   WalkStats scratch;
   Hit ref[kWave], tmp[kWave];
   for (size_t at = 0; at < set.size(); at += kWave) {
@@ -448,6 +539,41 @@ void adversarial(double& rays, double& mismatches) {
         pairs_wave(*kPairVariants[v].list, kPairVariants[v].keys, kPairVariants[v].early, nz != 0, &set[at], n, tmp, ps);
         for (int l = 0; l < n; ++l) mismatches += differs(tmp[l], ref[l]);
       }
+  }
+}
+
+// 6. the adversarial set of part 5, and each of its rays again with one or two
+// direction components replaced by 0, -0, 1e-20 or -1e-20 (safe_inv's +-1e20:
+// the axis' planes at +-infinity or, from an origin on a face, at 0 * 1e20),
+// phase 1's zero entries as they come and forced to -0
+void adversarial_phase1(Phase1Stats& st) {
+  std::vector<Ray> set = adversarial_set();
+  const size_t base = set.size();
+  const float tiny[4] = {0.0f, -0.0f, 1e-20f, -1e-20f};
+  for (size_t k = 0; k < base; ++k) {
+    Ray r = set[k];
+    const int a = (int)(k % 3), b = (int)((k / 3) % 3);
+    r.d[a] = tiny[(k / 9) % 4];
+    if (b != a) r.d[b] = tiny[(k / 36) % 4];   // two components (one when b == a)
+    float len = 0.0f;   // the other components: a unit vector again (along an axis if they were zero)
+    for (int c = 0; c < 3; ++c) if (c != a && c != b) len += r.d[c] * r.d[c];
+    len = std::sqrt(len);
+    for (int c = 0, first = 1; c < 3; ++c) if (c != a && c != b) { r.d[c] = len > 0.0f ? r.d[c] / len : (float)first; first = 0; }
+    set.push_back(r);
+  }
+  WalkStats scratch;
+  Hit ref[kWave], tmp[kWave];
+  for (size_t at = 0; at < set.size(); at += kWave) {
+    const int n = (int)std::min<size_t>(kWave, set.size() - at);
+    walk_wave(&set[at], n, ref, scratch, false);
+    for (int nz = 0; nz < 2; ++nz) {
+      Phase1Stats one;
+      phase1_wave(nz != 0, &set[at], n, tmp, one);
+      for (int l = 0; l < n; ++l) one.mismatches += differs(tmp[l], ref[l]);
+      if (nz == 0) { st.rays += one.rays; st.boxes += one.boxes; st.extra += one.extra; }
+      st.missed += one.missed; st.missed_with_hit += one.missed_with_hit; st.late_keys += one.late_keys;
+      st.mismatches += one.mismatches;
+    }
   }
 }
 
@@ -671,6 +797,7 @@ int main(int argc, char** argv) {
   }
   sweep_pair_records(g_sweep, true, g_pairs);
   sweep_pair_records(g_sweep, false, g_unpaired);
+  sweep_phase1_records(g_pairs, g_phase1);
   std::printf("%zu triangles, %u nodes, %u leaves, %d camera blocks\n", sc.references.size(), g_bvh.num_nodes,
               g_bvh.num_leaves, blocks);
   Totals T, B[2];
@@ -736,5 +863,20 @@ int main(int argc, char** argv) {
               "they come and forced to -0: mismatches %.0f\n", adv_rays, adv_bad);
   std::printf("pairs vs walk: rays %.0f mismatches %.0f ; adversarial rays %.0f mismatches %.0f\n", T.pairs[4].rays, pair_bad,
               adv_rays, adv_bad);
-  return s.mismatches == 0 && bad == 0 && max_queue <= (uint32_t)kStreamCap ? 0 : 2;
+  // 6. phase 1 on the centre list
+  const Phase1Stats& p1 = T.phase1;
+  Phase1Stats adv;
+  adversarial_phase1(adv);
+  std::printf("6. phase 1 on centre / half-extent records, fast-build arithmetic (per ray: lo / hi boxes hit %.2f, "
+              "hit by the centre test alone %.4f, by lo / hi alone %.0f in all)\n", p1.boxes / p1.rays, p1.extra / p1.rays,
+              p1.missed);
+  std::printf("   adversarial: %.0f rays (part 5's, and each again with one or two direction components 0, -0, +-1e-20): "
+              "lo / hi boxes hit %.2f per ray, by the centre test alone %.4f, by lo / hi alone %.0f in all (both zero "
+              "settings; rays in a padded face's own plane)\n", adv.rays, adv.boxes / adv.rays, adv.extra / adv.rays,
+              adv.missed);
+  std::printf("phase 1 vs walk: rays %.0f mismatches %.0f ; adversarial rays %.0f mismatches %.0f ; missed records %.0f "
+              "holding a hit triangle %.0f ; late keys %.0f\n", p1.rays, p1.mismatches, adv.rays, adv.mismatches,
+              p1.missed + adv.missed, p1.missed_with_hit + adv.missed_with_hit, p1.late_keys + adv.late_keys);
+  const bool p1_ok = p1.mismatches + adv.mismatches + p1.missed_with_hit + adv.missed_with_hit + p1.late_keys + adv.late_keys == 0;
+  return s.mismatches == 0 && bad == 0 && max_queue <= (uint32_t)kStreamCap && p1_ok ? 0 : 2;
 }
