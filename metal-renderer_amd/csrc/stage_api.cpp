@@ -1,0 +1,519 @@
+// stage_api.cpp — the stage-level C ABI of include/mrt.h (one call per pass of
+// the reference's frame: raygen, intersect, shade, resolve, accumulate) and the
+// entry points that need no renderer: camera helpers, guides, denoise, temporal
+// resolve and reproject, display, tile pack / unpack, events, the noise table.
+// The library's one error string lives here, behind mrt::host::fail.
+#include <atomic>
+#include <cmath>
+
+#include "host_internal.h"
+#include "denoise.h"
+#include "image.h"
+#include "noise.h"
+#include "temporal.h"
+
+using namespace mrt::host;
+
+namespace {
+
+thread_local std::string g_last_error;   // the one string: every unit's fail() writes it, mrt_last_error reads it
+std::atomic<uint32_t> g_denoise_path{mrt::kAtrousAuto};
+
+// `iterations` iterations from step 2^first_log2 on, with implementation `path`
+int denoise_run(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
+                uint32_t W, uint32_t H, const mrt_denoise_params* params, uint32_t iterations, uint32_t first_log2,
+                uint32_t path, void* stream) {
+  if (!image || !guide_n || !guide_p || !out || !scratch || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_denoise: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  auto overlap = [bytes](const void* a, const void* b) {
+    const char* p = (const char*)a;
+    const char* q = (const char*)b;
+    return p < q + bytes && q < p + bytes;
+  };
+  if (overlap(image, out) || overlap(image, scratch) || overlap(out, scratch))
+    return fail(MRT_ERR_INVALID, "mrt_denoise: image, out and scratch must not overlap");
+  if (overlap(guide_n, out) || overlap(guide_n, scratch) || overlap(guide_p, out) || overlap(guide_p, scratch))
+    return fail(MRT_ERR_INVALID, "mrt_denoise: the guide planes must not overlap out or scratch");
+  const int rc = mrt_denoise_params_check(params);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t N = iterations;
+  if (N == 0) {
+    HIP_TRY(hipMemcpyAsync(out, image, bytes, hipMemcpyDeviceToDevice, s));
+    return MRT_OK;
+  }
+  mrt::AtrousArgs a{};
+  a.guide_n = reinterpret_cast<const float4*>(guide_n);
+  a.guide_p = reinterpret_cast<const float4*>(guide_p);
+  a.width = W;
+  a.height = H;
+  a.inv_sigma_c2 = params->sigma_color > 0.0f ? (float)(1.0 / ((double)params->sigma_color * params->sigma_color)) : 0.0f;
+  a.sigma_plane = params->sigma_plane;
+  a.normal_log2_power = params->normal_log2_power;
+  const float* src = image;
+  for (uint32_t i = 0; i < N; ++i) {
+    float* dst = ((N - 1 - i) & 1u) ? scratch : out;   // the last iteration writes `out`
+    a.image = reinterpret_cast<const float4*>(src);
+    a.out = reinterpret_cast<float4*>(dst);
+    a.step = 1u << (i + first_log2);
+    HIP_TRY(mrt::launch_atrous(a, path, s));
+    src = dst;
+  }
+  return MRT_OK;
+}
+
+bool planes_overlap(const void* a, const void* b, size_t bytes) {
+  const char* p = (const char*)a;
+  const char* q = (const char*)b;
+  return p < q + bytes && q < p + bytes;
+}
+
+}  // namespace
+
+namespace mrt {
+namespace host {
+
+int fail(int code, const std::string& msg) {
+  g_last_error = msg;
+  return code;
+}
+
+mrt::CameraBlock camera_block(const mrt_camera& c) {
+  mrt::CameraBlock b{};
+  static_assert(sizeof(mrt_camera) == 60 && sizeof(mrt_camera) <= sizeof(mrt::CameraBlock), "mrt_camera");
+  std::memcpy(&b, &c, sizeof(mrt_camera));   // the same fields in the same order
+  return b;
+}
+
+bool camera_is_default(const mrt_camera& c) {
+  mrt_camera d;
+  (void)mrt_camera_default(&d);
+  return std::memcmp(&c, &d, sizeof(mrt_camera)) == 0;
+}
+
+// mrt_guides with the caller's stack spill (a renderer's own, so that its guide
+// pass shares nothing with the stage calls on the scene or another renderer)
+int guides_with_spill(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, float* guide_n,
+                      float* guide_p, uint32_t flags, uint32_t* spill, void* stream) {
+  if (!scene || !guide_n || !guide_p || guide_n == guide_p || W < 2 || H < 2 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_guides: bad argument");
+  mrt_camera c;
+  if (cam) {
+    const int rc = mrt_camera_check(cam);
+    if (rc) return rc;
+    c = *cam;
+  } else {
+    (void)mrt_camera_default(&c);
+  }
+  c.lens_radius = 0.0f;   // the guide ray goes through the pinhole
+  c.focus_distance = 0.0f;
+  mrt_camera d;
+  (void)mrt_camera_default(&d);
+  d.focus_distance = 0.0f;
+  const bool moved = std::memcmp(&c, &d, sizeof(mrt_camera)) != 0;
+  const mrt::CameraBlock cb = camera_block(c);
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_guides(scene->dev, W, H, moved ? &cb : nullptr, guide_n, guide_p, spill,
+                                              (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+}  // namespace host
+}  // namespace mrt
+
+extern "C" {
+
+const char* mrt_last_error(void) { return g_last_error.c_str(); }
+int mrt_abi_version(void) { return MRT_ABI_VERSION; }
+
+int mrt_device_count(void) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+  return n;
+}
+
+int mrt_shard_mask(uint32_t W, uint32_t H, uint32_t rank, uint32_t count, uint8_t* mask, uint64_t* owned) {
+  if (W == 0 || H == 0) return fail(MRT_ERR_INVALID, "empty image");
+  const uint32_t S = count ? count : 1;
+  if (rank >= S) return fail(MRT_ERR_INVALID, "shard_rank >= shard_count");
+  const uint32_t tx_n = (W + mrt::kTile - 1) / mrt::kTile, ty_n = (H + mrt::kTile - 1) / mrt::kTile;
+  uint64_t n = 0;
+  for (uint32_t y = 0; y < H; ++y)
+    for (uint32_t x = 0; x < W; ++x) {
+      const uint32_t t = (y / mrt::kTile) * tx_n + x / mrt::kTile;
+      const bool mine = (t % S) == rank;
+      if (mask) mask[(size_t)y * W + x] = mine ? 1 : 0;
+      n += mine;
+    }
+  (void)ty_n;
+  if (owned) *owned = n;
+  return MRT_OK;
+}
+
+int mrt_display(const float* image, const float* reference, float* out, uint32_t W, uint32_t H, uint32_t flags,
+                float compare_scale, void* stream) {
+  const uint32_t mode = (flags >> 8) & 0xFFu;
+  flags &= ~(MRT_DISPLAY_DENOISED | MRT_DISPLAY_RESOLVED);   // a renderer-level choice of the source (mrt_renderer_display)
+  if (!image || !out || W == 0 || H == 0 || mode > 4 || (mode && !reference) || (flags & ~0xFF03u))
+    return fail(MRT_ERR_INVALID, "mrt_display: bad argument");
+  HIP_TRY(mrt::fast::launch_display(reinterpret_cast<const float4*>(image), reinterpret_cast<const float4*>(reference),
+                                    reinterpret_cast<float4*>(out), W * H, flags, compare_scale, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+int mrt_tiles_packed_floats(uint32_t W, uint32_t H, uint32_t rank, uint32_t count, uint64_t* floats) {
+  const uint32_t S = count ? count : 1;
+  if (!floats || W == 0 || H == 0 || rank >= S) return fail(MRT_ERR_INVALID, "mrt_tiles_packed_floats: bad argument");
+  const uint32_t T = ((W + mrt::kTile - 1) / mrt::kTile) * ((H + mrt::kTile - 1) / mrt::kTile);
+  const uint64_t owned = rank < T ? (T - rank + S - 1) / S : 0;
+  *floats = owned * mrt::kTile * mrt::kTile * 4;
+  return MRT_OK;
+}
+
+int mrt_tiles_pack(const float* image, uint32_t W, uint32_t H, uint32_t rank, uint32_t count, float* packed,
+                   void* stream) {
+  const uint32_t S = count ? count : 1;
+  if (!image || !packed || W == 0 || H == 0 || rank >= S) return fail(MRT_ERR_INVALID, "mrt_tiles_pack: bad argument");
+  HIP_TRY(mrt::fast::launch_tiles_move(reinterpret_cast<const float4*>(image), reinterpret_cast<float4*>(packed), W, H,
+                                       rank, S, true, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+int mrt_tiles_unpack(const float* packed, uint32_t W, uint32_t H, uint32_t rank, uint32_t count, float* image,
+                     void* stream) {
+  const uint32_t S = count ? count : 1;
+  if (!image || !packed || W == 0 || H == 0 || rank >= S) return fail(MRT_ERR_INVALID, "mrt_tiles_unpack: bad argument");
+  HIP_TRY(mrt::fast::launch_tiles_move(reinterpret_cast<const float4*>(packed), reinterpret_cast<float4*>(image), W, H,
+                                       rank, S, false, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+int mrt_synchronize(void* stream) {
+  if (stream) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  else HIP_TRY(hipDeviceSynchronize());
+  return MRT_OK;
+}
+
+int mrt_event_record(void* stream, void** event) {
+  if (!event) return fail(MRT_ERR_INVALID, "null event");
+  if (!*event) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    *event = (void*)e;
+  }
+  HIP_TRY(hipEventRecord((hipEvent_t)*event, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+int mrt_event_synchronize(void* event) {
+  if (!event) return fail(MRT_ERR_INVALID, "null event");
+  HIP_TRY(hipEventSynchronize((hipEvent_t)event));
+  return MRT_OK;
+}
+
+int mrt_event_destroy(void* event) {
+  if (event) HIP_TRY(hipEventDestroy((hipEvent_t)event));
+  return MRT_OK;
+}
+
+int mrt_debug_stamps(uint64_t* out8, int reset) {
+  if (!out8) return fail(MRT_ERR_INVALID, "null output");
+  HIP_TRY(mrt::fast::read_stamps(reinterpret_cast<unsigned long long*>(out8), reset != 0));
+  return MRT_OK;
+}
+
+int mrt_debug_wave_times(uint64_t* out, size_t n) {
+  if (!out) return fail(MRT_ERR_INVALID, "null output");
+  HIP_TRY(mrt::fast::read_wave_times(reinterpret_cast<unsigned long long*>(out), n));
+  return MRT_OK;
+}
+
+int mrt_debug_lanes(uint64_t* out, size_t n, int reset) {
+  if (!out) return fail(MRT_ERR_INVALID, "null output");
+  HIP_TRY(mrt::fast::read_lane_stats(reinterpret_cast<unsigned long long*>(out), n, reset != 0));
+  return MRT_OK;
+}
+
+int mrt_noise_table(uint64_t seed, int64_t frame, float* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "null output");
+  mrt::make_noise_table(seed, frame, out);
+  return MRT_OK;
+}
+
+int mrt_debug_magic_div(uint32_t d, const uint32_t* n, uint32_t count, uint32_t* q) {
+  if (d == 0 || (count && (!n || !q))) return fail(MRT_ERR_INVALID, "mrt_debug_magic_div: bad argument");
+  const mrt::MagicDiv m = mrt::magic_div(d);
+  for (uint32_t i = 0; i < count; ++i) q[i] = mrt::mdiv_host(n[i], m);
+  return MRT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// stage-level ABI
+// ---------------------------------------------------------------------------
+int mrt_raygen(const mrt_scene* scene, uint32_t W, uint32_t H, const float* noise, void* rays, uint32_t flags,
+               void* stream) {
+  if (!scene || !noise || !rays || W < 2 || H < 2) return fail(MRT_ERR_INVALID, "mrt_raygen: bad argument");
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_raygen(W, H, noise, (mrt::RefRay*)rays, nullptr, (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+// ---- camera (include/mrt.h) -------------------------------------------------
+int mrt_camera_default(mrt_camera* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_camera_default: null camera");
+  // rayGenerator's camera (mrt_layout.h kCameraX/Y/Z), looking down -z
+  *out = mrt_camera{{mrt::kCameraX, mrt::kCameraY, mrt::kCameraZ}, {1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f},
+                    {0.0f, 0.0f, -1.0f}, 1.0f, 0.0f, 0.0f};
+  return MRT_OK;
+}
+
+int mrt_camera_check(const mrt_camera* cam) {
+  if (!cam) return fail(MRT_ERR_INVALID, "camera: null");
+  const float* f = cam->origin;   // 15 consecutive floats
+  for (int i = 0; i < 15; ++i)
+    if (!std::isfinite(f[i])) return fail(MRT_ERR_INVALID, "camera: a field is not finite");
+  auto dotd = [](const float* a, const float* b) {
+    return (double)a[0] * b[0] + (double)a[1] * b[1] + (double)a[2] * b[2];
+  };
+  const float* ax[3] = {cam->right, cam->up, cam->forward};
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j)
+      if (std::fabs(dotd(ax[i], ax[j]) - (i == j ? 1.0 : 0.0)) > 1e-4)
+        return fail(MRT_ERR_INVALID, "camera: right, up, forward are not orthonormal to 1e-4");
+  const double cx[3] = {(double)cam->right[1] * cam->up[2] - (double)cam->right[2] * cam->up[1],
+                        (double)cam->right[2] * cam->up[0] - (double)cam->right[0] * cam->up[2],
+                        (double)cam->right[0] * cam->up[1] - (double)cam->right[1] * cam->up[0]};
+  if (!(cx[0] * cam->forward[0] + cx[1] * cam->forward[1] + cx[2] * cam->forward[2] < 0.0))
+    return fail(MRT_ERR_INVALID, "camera: the basis is not right-handed (right x up must be -forward)");
+  if (!(cam->tan_half_fov > 0.0f)) return fail(MRT_ERR_INVALID, "camera: tan_half_fov must be positive");
+  if (cam->lens_radius < 0.0f) return fail(MRT_ERR_INVALID, "camera: lens_radius must not be negative");
+  if (cam->lens_radius > 0.0f && !(cam->focus_distance > 0.0f))
+    return fail(MRT_ERR_INVALID, "camera: a lens needs a positive focus_distance");
+  return MRT_OK;
+}
+
+int mrt_camera_look_at(const float eye[3], const float target[3], const float up[3], float fov_x_degrees,
+                       mrt_camera* out) {
+  if (!eye || !target || !up || !out) return fail(MRT_ERR_INVALID, "mrt_camera_look_at: null argument");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(eye[i]) || !std::isfinite(target[i]) || !std::isfinite(up[i]))
+      return fail(MRT_ERR_INVALID, "mrt_camera_look_at: an argument is not finite");
+  if (!(fov_x_degrees > 0.0f && fov_x_degrees < 180.0f))
+    return fail(MRT_ERR_INVALID, "mrt_camera_look_at: fov_x_degrees must lie in (0, 180)");
+  double f[3] = {(double)target[0] - eye[0], (double)target[1] - eye[1], (double)target[2] - eye[2]};
+  const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+  if (!(fl > 0.0)) return fail(MRT_ERR_INVALID, "mrt_camera_look_at: eye and target coincide");
+  for (double& v : f) v /= fl;
+  const double ul = std::sqrt((double)up[0] * up[0] + (double)up[1] * up[1] + (double)up[2] * up[2]);
+  double r[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
+  const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  if (!(ul > 0.0) || !(rl > 1e-6 * ul))
+    return fail(MRT_ERR_INVALID, "mrt_camera_look_at: up is zero or parallel to the view direction");
+  for (double& v : r) v /= rl;
+  const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
+  mrt_camera c{};
+  for (int i = 0; i < 3; ++i) {
+    c.origin[i] = eye[i];
+    c.right[i] = (float)r[i];
+    c.up[i] = (float)u[i];
+    c.forward[i] = (float)f[i];
+  }
+  c.tan_half_fov = (float)std::tan((double)fov_x_degrees * (3.14159265358979323846 / 360.0));
+  c.lens_radius = 0.0f;
+  c.focus_distance = 0.0f;
+  const int rc = mrt_camera_check(&c);   // (e.g. a field of view whose tangent overflows a float)
+  if (rc) return rc;
+  *out = c;
+  return MRT_OK;
+}
+
+int mrt_raygen_camera(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, const float* noise,
+                      void* rays, uint32_t flags, void* stream) {
+  if (!scene || !cam || !noise || !rays || W < 2 || H < 2)
+    return fail(MRT_ERR_INVALID, "mrt_raygen_camera: bad argument");
+  const int rc = mrt_camera_check(cam);
+  if (rc) return rc;
+  const mrt::CameraBlock cb = camera_block(*cam);
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_raygen(W, H, noise, (mrt::RefRay*)rays, camera_is_default(*cam) ? nullptr : &cb,
+                                              (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+// ---- denoised output (include/mrt.h) ---------------------------------------
+int mrt_guides(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, float* guide_n, float* guide_p,
+               uint32_t flags, void* stream) {
+  return guides_with_spill(scene, cam, W, H, guide_n, guide_p, flags,
+                           scene ? scene->isect_spill.as<uint32_t>() : nullptr, stream);
+}
+
+int mrt_denoise_params_default(uint64_t frames, mrt_denoise_params* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_denoise_params_default: null params");
+  out->iterations = frames <= 2 ? 3u : (frames <= 16 ? 2u : 1u);
+  out->sigma_color = (float)(2.0 / std::sqrt((double)std::max<uint64_t>(frames, 1)));
+  out->sigma_plane = 0.01f;
+  out->normal_log2_power = 6;
+  return MRT_OK;
+}
+
+int mrt_denoise_params_check(const mrt_denoise_params* p) {
+  if (!p) return fail(MRT_ERR_INVALID, "denoise params: null");
+  if (p->iterations > 8) return fail(MRT_ERR_INVALID, "denoise params: iterations must be at most 8");
+  if (!std::isfinite(p->sigma_color) || p->sigma_color < 0.0f)
+    return fail(MRT_ERR_INVALID, "denoise params: sigma_color must be finite and not negative");
+  if (!std::isfinite(p->sigma_plane) || !(p->sigma_plane > 0.0f))
+    return fail(MRT_ERR_INVALID, "denoise params: sigma_plane must be finite and positive");
+  if (p->normal_log2_power > 8) return fail(MRT_ERR_INVALID, "denoise params: normal_log2_power must be at most 8");
+  return MRT_OK;
+}
+
+int mrt_debug_denoise_path(uint32_t path) {
+  if (path > mrt::kAtrousStaged) return fail(MRT_ERR_INVALID, "mrt_debug_denoise_path: 0, 1 or 2");
+  g_denoise_path.store(path);
+  return MRT_OK;
+}
+
+int mrt_denoise(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
+                uint32_t W, uint32_t H, const mrt_denoise_params* params, void* stream) {
+  return denoise_run(image, guide_n, guide_p, out, scratch, W, H, params, params ? params->iterations : 0u, 0u,
+                     g_denoise_path.load(), stream);
+}
+
+int mrt_debug_denoise_step(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
+                           uint32_t W, uint32_t H, const mrt_denoise_params* params, uint32_t step_log2, uint32_t path,
+                           void* stream) {
+  if (step_log2 > 14 || path > mrt::kAtrousStaged)
+    return fail(MRT_ERR_INVALID, "mrt_debug_denoise_step: step at most 2^14, path 0, 1 or 2");
+  return denoise_run(image, guide_n, guide_p, out, scratch, W, H, params, 1u, step_log2, path, stream);
+}
+
+// ---- temporal history (include/mrt.h) --------------------------------------
+int mrt_reproject_params_default(mrt_reproject_params* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_reproject_params_default: null params");
+  out->plane_tolerance = 0.01f;
+  out->normal_cos_min = 0.9f;
+  out->max_history = 32.0f;
+  return MRT_OK;
+}
+
+int mrt_reproject_params_check(const mrt_reproject_params* p) {
+  if (!p) return fail(MRT_ERR_INVALID, "reproject params: null");
+  if (!std::isfinite(p->plane_tolerance) || !(p->plane_tolerance > 0.0f))
+    return fail(MRT_ERR_INVALID, "reproject params: plane_tolerance must be finite and positive");
+  if (!std::isfinite(p->normal_cos_min) || p->normal_cos_min < -1.0f || p->normal_cos_min > 1.0f)
+    return fail(MRT_ERR_INVALID, "reproject params: normal_cos_min must be in [-1, 1]");
+  if (!std::isfinite(p->max_history) || p->max_history < 0.0f)
+    return fail(MRT_ERR_INVALID, "reproject params: max_history must be finite and not negative");
+  return MRT_OK;
+}
+
+
+int mrt_temporal_resolve(const float* image, uint64_t frames, const float* history, float* out, uint32_t W, uint32_t H,
+                         void* stream) {
+  if (!image || !out || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_temporal_resolve: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  if (planes_overlap(image, out, bytes) || (history && planes_overlap(history, out, bytes)))
+    return fail(MRT_ERR_INVALID, "mrt_temporal_resolve: out must not overlap image or history");
+  mrt::ResolveArgs a{};
+  a.image = reinterpret_cast<const float4*>(image);
+  a.history = reinterpret_cast<const float4*>(history);
+  a.out = reinterpret_cast<float4*>(out);
+  a.count = W * H;
+  a.frames = (float)frames;
+  HIP_TRY(mrt::launch_temporal_resolve(a, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+int mrt_reproject(const float* prev, const float* prev_guide_n, const float* prev_guide_p, const mrt_camera* prev_cam,
+                  const float* cur_guide_n, const float* cur_guide_p, float* history_out, uint32_t W, uint32_t H,
+                  const mrt_reproject_params* params, void* stream) {
+  if (!prev || !prev_guide_n || !prev_guide_p || !cur_guide_n || !cur_guide_p || !history_out || !params || W < 2 ||
+      H < 2 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_reproject: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  for (const float* in : {prev, prev_guide_n, prev_guide_p, cur_guide_n, cur_guide_p})
+    if (planes_overlap(in, history_out, bytes))
+      return fail(MRT_ERR_INVALID, "mrt_reproject: history_out must not overlap an input");
+  int rc = mrt_reproject_params_check(params);
+  if (rc) return rc;
+  mrt_camera c;
+  if (prev_cam) {
+    rc = mrt_camera_check(prev_cam);
+    if (rc) return rc;
+    c = *prev_cam;
+  } else {
+    (void)mrt_camera_default(&c);
+  }
+  mrt::ReprojectArgs a{};
+  a.prev = reinterpret_cast<const float4*>(prev);
+  a.prev_n = reinterpret_cast<const float4*>(prev_guide_n);
+  a.prev_p = reinterpret_cast<const float4*>(prev_guide_p);
+  a.cur_n = reinterpret_cast<const float4*>(cur_guide_n);
+  a.cur_p = reinterpret_cast<const float4*>(cur_guide_p);
+  a.out = reinterpret_cast<float4*>(history_out);
+  a.width = W;
+  a.height = H;
+  for (int k = 0; k < 3; ++k) {
+    a.origin[k] = c.origin[k];
+    a.right[k] = c.right[k];
+    a.up[k] = c.up[k];
+    a.forward[k] = c.forward[k];
+  }
+  a.tan_half_fov = c.tan_half_fov;   // the lens is ignored, as the guide pass ignores it
+  a.plane_tolerance = params->plane_tolerance;
+  a.normal_cos_min = params->normal_cos_min;
+  a.max_history = params->max_history;
+  HIP_TRY(mrt::launch_reproject(a, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+int mrt_intersect(const mrt_scene* scene, const void* rays, uint32_t stride, uint32_t count, void* isect,
+                  uint32_t flags, void* stream) {
+  if (!scene || (!rays && count) || (!isect && count) || stride < 32 || (stride % 4))
+    return fail(MRT_ERR_INVALID, "mrt_intersect: bad argument");
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_intersect(scene->dev, rays, stride, count, (mrt::RefIntersection*)isect,
+                                                 scene->isect_spill.as<uint32_t>(), (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+int mrt_shade(const mrt_scene* scene, uint32_t W, uint32_t H, uint32_t frame_index, uint32_t L, const float* noise,
+              const void* isect, void* rays, void* srays, uint32_t flags, void* stream) {
+  if (!scene || !noise || !isect || !rays || !srays || W == 0 || H == 0 || L == 0)
+    return fail(MRT_ERR_INVALID, "mrt_shade: bad argument");
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_shade(scene->dev, W, H, frame_index, L, noise, (const mrt::RefIntersection*)isect,
+                                             (mrt::RefRay*)rays, (mrt::RefShadowRay*)srays,
+                                             (flags & MRT_FLAG_DEBUG_MATERIAL) ? mrt::kShadeDebugMaterial : 0u,
+                                             (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+int mrt_resolve_shadow(const mrt_scene* scene, uint32_t count, const void* isect, void* rays, const void* srays,
+                       uint32_t flags, void* stream) {
+  if (!scene || (count && (!isect || !rays || !srays))) return fail(MRT_ERR_INVALID, "mrt_resolve_shadow: bad argument");
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_resolve(count, (const mrt::RefIntersection*)isect, (mrt::RefRay*)rays,
+                                               (const mrt::RefShadowRay*)srays, (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+int mrt_accumulate(const mrt_scene* scene, uint32_t W, uint32_t H, uint32_t frame_index, const void* rays,
+                   float* image, uint32_t flags, void* stream) {
+  if (!scene || !rays || !image || W == 0 || H == 0) return fail(MRT_ERR_INVALID, "mrt_accumulate: bad argument");
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_accumulate(W, H, frame_index, (const mrt::RefRay*)rays, image,
+                                                  !(flags & MRT_FLAG_NO_ACCUMULATE), (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+int mrt_image_load_exr(const char* path, float* rgba, size_t capacity, uint32_t* width, uint32_t* height) {
+  if (!path || !width || !height) return fail(MRT_ERR_INVALID, "mrt_image_load_exr: null argument");
+  std::vector<float> img;
+  uint32_t W = 0, H = 0;
+  std::string err;
+  if (!mrt::load_exr(path, img, W, H, err)) return fail(MRT_ERR_IO, err);
+  *width = W;
+  *height = H;
+  if (!rgba) return MRT_OK;
+  if (capacity < img.size()) return fail(MRT_ERR_INVALID, "mrt_image_load_exr: buffer too small");
+  std::memcpy(rgba, img.data(), img.size() * 4);
+  return MRT_OK;
+}
+
+}  // extern "C"

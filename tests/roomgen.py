@@ -45,7 +45,7 @@ DETECTING = [n for n, (c, _) in CASES.items() if c > 0]
 def seeds(name):
     """The two seeds the tests use per case.  float's seed 1 is left to a test
     of its own: there the occluder tree comes out deeper than the main tree,
-    so the library drops it (renderer.cpp) and no shortcut is detected."""
+    so the library drops it (scene_api.cpp build_occluder_tree) and no shortcut is detected."""
     return (2, 3) if name == "float" else (1, 2)
 
 MTL = """newmtl white

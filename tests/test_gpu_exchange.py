@@ -97,7 +97,7 @@ def test_host_tiles_roundtrip(gpu, mrt_mod):
 
 @pytest.mark.parametrize("n", [2, 3, 8])
 def test_rank0_unpacks_gathered_slabs(gpu, mrt_mod, n):
-    """Rank 0's unpack of an N-rank ncclGather (renderer.cpp exchange_unpack:
+    """Rank 0's unpack of an N-rank ncclGather (exchange.cpp exchange_unpack:
     slab k at k * slab_floats, tile k*count + k-th of rank k) on one device:
     the receive buffer is filled with N synthetic packed slabs through the
     test entry mrt_debug_exchange_unpack, and the image must equal rank 0's
