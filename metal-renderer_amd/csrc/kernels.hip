@@ -2024,6 +2024,9 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
   if (WAVEQ && MRT_STREAM_WAITS) wait_vmem();
   if (active && (!hit_ok || last)) a.radiance[gslot] = make_float4(s.R.x, s.R.y, s.R.z, 0.0f);
   const bool alive = hit_ok && !last;
+  // (WAVEQ: testing the survivor of the bounce before the last against the
+  // lights here, so that the last level holds only rays a light accepts, was
+  // built, changed no bit and measured C2 -3.4 %: removed)
   // re-sort by material between bounces: survivors that left a diffuse
   // surface (class 0) fill the block's segment from the front, the others
   // (mirror / plastic / dielectric: specular and refracted rays) from the
@@ -2220,9 +2223,9 @@ __global__ __launch_bounds__(kBlock, MRT_BOUNCE_WAVES) void bounce_kernel(Device
 // No wave ever waits for another, so any grid and any residency is safe.
 // ---------------------------------------------------------------------------
 template <int STACK, int MODE, bool CAM = false>
-// Waves per SIMD the stream kernel's registers allow: 6 (80 VGPRs, 6 values
-// spilled to scratch, reloaded outside the traversal loops: tools/
-// scratch_sites.py) under the max-ILP scheduler of its unit (Makefile):
+// Waves per SIMD the stream kernel's registers allow: 6 (80 VGPRs, 5 values
+// spilled to scratch — 6 until §2.1n — reloaded outside the traversal loops:
+// tools/scratch_sites.py) under the max-ILP scheduler of its unit (Makefile):
 // C2 +1.7…+3.4 %, L = 5 +4…6 % over 5 waves (96 VGPRs, no spill); 7 / 8
 // waves (23 / 37 spills) lose 6 / 27 %, and 6 waves under the default
 // scheduler only tie (r5, alternating in one call); re-swept at the r6
@@ -2234,18 +2237,24 @@ template <int STACK, int MODE, bool CAM = false>
 #define MRT_STREAM_SPARE 1
 #endif
 __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(DeviceScene sc, BounceArgs a) {
-  __shared__ uint32_t s_cnt[kBlock / 64][kStreamMaxL];    // rays queued per level (wave-private rows)
-  __shared__ uint32_t s_alive[kBlock / 64][kStreamMaxL];  // survivors per bounce (stats)
+  // per wave (private rows): [0] rays queued per level, [1] survivors per
+  // bounce (stats).  One array, so that the one row address `cnt` serves
+  // both: as two arrays the kernel spilled 6 values, as one 5 (16 scratch
+  // instructions -> 10), C2 +1.0 %.  A by-product of register allocation,
+  // which nothing guards: re-check with tools/kres.py after a change here or
+  // a compiler update
+  __shared__ uint32_t s_rows[kBlock / 64][2][kStreamMaxL];
   __shared__ uint32_t s_closed;
   span_begin(a);
   LS_INIT();
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t L = a.max_path_length;
   const LdsCtx cx = stage_lds<MODE>(sc, 0, a.stack_spill);
-  for (uint32_t i = lane; i < L; i += 64u) { s_cnt[wave][i] = 0; s_alive[wave][i] = 0; }
+  for (uint32_t i = lane; i < L; i += 64u) { s_rows[wave][0][i] = 0; s_rows[wave][1][i] = 0; }
   if (tid == 0) s_closed = 0;
   __syncthreads();
-  uint32_t* cnt = s_cnt[wave];
+  uint32_t* cnt = s_rows[wave][0];
+  uint32_t* alive_cnt = cnt + kStreamMaxL;   // s_rows[wave][1]
   const uint32_t N0 = a.num_slots * a.batch;
   const uint32_t rlen = ((N0 + kGrabRanges - 1) / kGrabRanges + kGrab - 1) / kGrab * kGrab;
   uint32_t cur_range = blockIdx.x % kGrabRanges, ranges_left = kGrabRanges;
@@ -2333,7 +2342,7 @@ __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(Device
                                                                  a.in_q, a.in_q, nullptr, out, 0u, st, recycled);
     if (lvl + 1u < L && lane == 0) {
       cnt[lvl + 1u] += wrote;
-      s_alive[wave][lvl] += wrote;
+      alive_cnt[lvl] += wrote;
     }
     // at most the n lanes that left the level return to it: it stays within
     // kStreamCap, and every pass clears a mask bit of each, so they finish
@@ -2341,7 +2350,7 @@ __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(Device
   }
   // stats: survivors of bounce b = rays alive at the start of bounce b + 1
   for (uint32_t b = lane; b + 1 < L; b += 64u)
-    if (s_alive[wave][b]) atomicAdd(a.bounce_counts + b, s_alive[wave][b]);
+    if (alive_cnt[b]) atomicAdd(a.bounce_counts + b, alive_cnt[b]);
   LS_FLUSH();
   span_end(a);
 }
