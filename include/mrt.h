@@ -123,7 +123,7 @@ typedef struct mrt_scene_info {
    * tree lies on one of convex_solids parallelepiped solids (e.g. the Cornell
    * box's blocks): shadow rays through that tree are decided per solid by a
    * segment test against its three slabs pushed out by convex_delta, and the
-   * leaf test of the face the segment enters, before any walk (kernels.hip
+   * leaf test of the face the segment enters, before any walk (dev_shadow.h
    * convex_occlusion).  convex_obb[c] = three unit axis normals (9 floats),
    * then each axis's padded slab (lo, hi); convex_face_tris[c][2a + side]
    * (side 0: the lo face, 1: the hi face) = its two primitive ids, 16 bits
@@ -655,7 +655,7 @@ int mrt_debug_wave_times(uint64_t* out, size_t n);
  * the last reset — per traversal loop the wave iterations and the active
  * lanes in them (tools/lane_stats.py names the slots).  Zeros otherwise. */
 int mrt_debug_lanes(uint64_t* out, size_t n, int reset);
-/* Test entry: the scene's leaf-box sweep list (kernels.hip sweep_nearest) —
+/* Test entry: the scene's leaf-box sweep list (dev_sweep.h sweep_nearest) —
  * *count leaf records of the main tree, of which min(*count, capacity) are
  * copied to `records` (may be NULL) as 8 floats each: (lo.xyz, bits(leaf
  * ref)), (hi.xyz, 0), the leaf's child box as its parent node holds it, in
@@ -690,7 +690,7 @@ int mrt_debug_sweep_pairs(const mrt_scene* scene, float* records, uint32_t* prim
  * multiply-adds per axis); phase 2 and the precise build keep lo / hi. */
 int mrt_debug_sweep_phase1(const mrt_scene* scene, float* records, uint32_t capacity, uint32_t* count);
 /* Test entry: the rest pops one pass of the stream kernel's queue levels makes
- * before it recycles a ray with leaves left to test (kernels.hip bounce_wave),
+ * before it recycles a ray with leaves left to test (kern_bounce.h bounce_wave),
  * for a scene whose nearest queries sweep.  32: never, the default (every cap
  * measured slower); MRT_SWEEP_CAP=<n> under MRT_DIAG=1 sets another. */
 int mrt_debug_sweep_cap(const mrt_scene* scene, uint32_t* cap);
@@ -717,7 +717,7 @@ int mrt_debug_exchange_unpack(mrt_renderer* r, uint32_t nranks, const float* gat
  * smallest t those bounds allow, within 2^-10 of t_hit (what a differently
  * rounding triangle test may report instead).  +inf if the ray
  * misses one of those boxes altogether, -inf for none.  The kernels cull a
- * child only when its entry lies beyond h.t * (1 + 2^-11) (kernels.hip
+ * child only when its entry lies beyond h.t * (1 + 2^-11) (dev_traverse.h
  * kCullScale): every value below 2^-11 is a hit no visiting order can lose
  * (DESIGN.md §3.1). */
 int mrt_debug_box_margin(const mrt_scene* scene, const void* rays, uint32_t stride, uint32_t count,

@@ -8,7 +8,7 @@ namespace mrt {
 
 struct AtrousArgs {
   const float4* image;     // c^i: rgb + alpha
-  const float4* guide_n;   // (normal, bits(word)) of kernels.hip guide_kernel
+  const float4* guide_n;   // (normal, bits(word)) of kern_stage.h guide_kernel
   const float4* guide_p;   // (position, t)
   float4* out;             // c^(i+1)
   uint32_t width, height;

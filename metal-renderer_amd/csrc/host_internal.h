@@ -59,7 +59,7 @@ struct DevBuf {
 // traversal-stack spill of the stage intersect and guide kernels (trees deeper
 // than their kMaxStack-entry LDS stack): one row of max_stack words per lane of
 // their persistent grid — the row stride the kernels address it with
-// (kernels.hip LdsCtx::spill_lane; a lane uses the first max_stack - 32 words)
+// (dev_lds.h LdsCtx::spill_lane; a lane uses the first max_stack - 32 words)
 inline hipError_t alloc_isect_spill(DevBuf& b, uint32_t max_stack) {
   if (max_stack <= (uint32_t)mrt::kMaxStack) return b.alloc(0);
   return b.alloc((size_t)max_stack * mrt::kIntersectSpillGrid * 256 * 4);

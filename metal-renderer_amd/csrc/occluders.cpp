@@ -4,7 +4,7 @@
 // Float-error margin.  Let T be a culled triangle, P its plane, and let the
 // shadow origin p and every light vertex (hence the light point q, a convex
 // combination) lie inside P by at least d.  The segment [p, q] does not meet
-// P; the leaf test (kernels.hip tri_bary) could still report t in [0, t_q]
+// P; the leaf test (dev_math.h tri_bary) could still report t in [0, t_q]
 // only through rounding.  Its t = (s . (e1 x e2)) / (d . (e2 x e1)) with
 // s = p - v0: the numerator is off by about 5u |s||e1||e2| (u = 2^-24) against
 // a true value d_p * |e1 x e2|, the denominator by 5u |e1||e2| against
@@ -14,7 +14,7 @@
 // d_q / d_p from q) beyond the true t_q for every direction; a grazing
 // direction gives |t| > 6 S > t_q.  Triangles with c > 16 (slivers) are kept.
 //
-// The light's own t_q (the target test, kernels.hip tri_test) is computed
+// The light's own t_q (the target test, dev_math.h tri_test) is computed
 // too: by the same analysis its error is about 10 u S c_L / |cos_L| (c_L the
 // light triangle's c, cos_L the ray's cosine to the light's plane), which
 // grows without bound for rays grazing the light plane (the reference only

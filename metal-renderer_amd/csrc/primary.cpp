@@ -2,7 +2,7 @@
 //
 // Conservative by construction, in double precision:
 //   * the block's rectangle on the image plane covers every direction
-//     camera_ray (kernels.hip, = rayGenerator, renderer/Shaders.metal:75-103)
+//     camera_ray (dev_shade.h, = rayGenerator, renderer/Shaders.metal:75-103)
 //     can produce for its pixels: pixel centre +- the noise jitter
 //     (ns * 2 - 1) / (W - 1) in x and (ns * 2 - 1) / (H - 1) in y, ns in [0, 1);
 //   * a triangle is listed when its perspective projection, grown by a margin

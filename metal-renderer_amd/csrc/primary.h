@@ -4,7 +4,7 @@
 // origin (0, 1, 2.35), image plane z = -1 in front of it); a pinhole camera
 // set with mrt_renderer_set_camera is the same construction in its own basis.
 // Bounce 0 sends one ray per pixel through it.  Every camera ray of an 8x8 pixel block —
-// one 64-lane wave of bounce 0 (kernels.hip slot_pixel) — points into a small
+// one 64-lane wave of bounce 0 (dev_shade.h slot_pixel) — points into a small
 // rectangle of the image plane, so the only triangles such a ray can hit are
 // those whose perspective projection overlaps that rectangle.  For each block
 // we list them (leaf-order indices into DeviceScene::tris); bounce 0 then

@@ -5,7 +5,7 @@
 //
 // mrt_renderer_draw_n mirrors performRaytracing: (renderer/Renderer.mm:500-585)
 // frame by frame, restructured for MI355X as a wavefront of fused bounce
-// launches (kernels.hip::bounce_kernel):
+// launches (kern_bounce.h::bounce_kernel):
 //   reference per frame: rayGenerator, L x {MPS intersect, intersectionHandler,
 //                        MPS intersect (shadow), lightSamplingHandler},
 //                        accumulateImage                       = 2 + 4L passes
@@ -229,7 +229,7 @@ int alloc_frame_buffers(mrt_renderer* r) {
     const size_t qslots = r->stream_mode ? mrt::stream_slots(r->desc.max_path_length, r->grid) : slots;
     // (stream mode: queue[1] is unused but for its plane 0, the partial hits
     // of recycled rays — 16 B a slot, as the other planes — where the scene's
-    // nearest queries sweep under a cap, kernels.hip bounce_wave)
+    // nearest queries sweep under a cap, kern_bounce.h bounce_wave)
     const mrt::DeviceScene& dev = r->scene->dev;
     const bool partial = r->stream_mode && dev.sweep_leaves && dev.sweep_cap < mrt::kSweepLeaves;
     for (int q = 0; q < 2; ++q)
@@ -237,7 +237,7 @@ int alloc_frame_buffers(mrt_renderer* r) {
         HIP_TRY(fs.queue[q][p].alloc(r->path_mode || (r->stream_mode && q == 1 && !(partial && p == 0)) ? 0 : qslots * 16));
     HIP_TRY(fs.radiance.alloc(owned_slots * r->batch * 16));
     const uint32_t need = r->scene->dev.max_stack;
-    // spill rows of max_stack words per lane (kernels.hip LdsCtx::spill_lane)
+    // spill rows of max_stack words per lane (dev_lds.h LdsCtx::spill_lane)
     if (need > r->stack_entries && !fs.spill.p) HIP_TRY(fs.spill.alloc((size_t)need * r->grid * 256 * 4));
   }
   if (r->own_image) {

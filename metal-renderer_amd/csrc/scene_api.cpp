@@ -191,7 +191,7 @@ int build_occluder_tree(SceneBuild& b) {
   }
   // with few light triangles the occluder tree leaves them out: every shadow
   // ray enters the light's own leaf box, and the kernels test the other
-  // light triangles in one wave-uniform loop instead (kernels.hip
+  // light triangles in one wave-uniform loop instead (dev_shadow.h
   // lights_occlude; MRT_OCC_LIGHTS=0 keeps them in the tree)
   b.occ_lights = b.occ_on && h.light_count <= mrt::kOccLightsMax;
   if (const char* v = mrt::diag_env("MRT_OCC_LIGHTS")) b.occ_lights = b.occ_lights && std::atoi(v) != 0;
@@ -266,7 +266,7 @@ void find_convex_solids(SceneBuild& b) {
   for (uint32_t t = 0; t < b.T; ++t) {
     const uint32_t code = conv.prim_face[t];   // c * 8 + face + 1, 0: not on a solid
     b.prims[(size_t)t * 24 + 11] = bitsf(code);
-    // the face's outward unit normal in n0.w, n1.w, n2.w (kernels.hip convex_occlusion's own-face test)
+    // the face's outward unit normal in n0.w, n1.w, n2.w (dev_shadow.h convex_occlusion's own-face test)
     if (code)
       for (int c = 0; c < 3; ++c) b.prims[(size_t)t * 24 + 15 + 4 * c] = conv.face_normal[(code - 1) / 8][3 * ((code - 1) % 8) + c];
   }
@@ -368,7 +368,7 @@ int upload_scene(SceneBuild& b) {
   const mrt::OccluderSet& occ = b.occ;
   const uint32_t T = b.T;
   // the kernels address nodes and leaf triangles with 32-bit buffer offsets
-  // (kernels.hip buf_ld4): each array below 4 GiB (~33 M nodes, ~89 M
+  // (dev_lds.h buf_ld4): each array below 4 GiB (~33 M nodes, ~89 M
   // triangles; a scene beyond that needs the flat-address build)
   if ((uint64_t)b.up_nodes.size() * 4 >= (1ull << 32) || (uint64_t)b.up_tris.size() * 4 >= (1ull << 32) ||
       (uint64_t)s->bvh.nodes.size() * 4 >= (1ull << 32) || (uint64_t)T * 48 >= (1ull << 32))
@@ -751,7 +751,7 @@ int mrt_debug_box_margin(const mrt_scene* scene, const void* rays, uint32_t stri
     if (!(is[i].distance >= 0.0f) || is[i].triangleIndex >= T || prim_up[is[i].triangleIndex].node == kNone) continue;
     const float tmin = f[3];
     float inv[3], oinv[3];
-    for (int a = 0; a < 3; ++a) {   // kernels.hip make_raybox (the fast build's reciprocal correctly rounded here)
+    for (int a = 0; a < 3; ++a) {   // dev_math.h make_raybox (the fast build's reciprocal correctly rounded here)
       const float d = f[4 + a], dd = std::fabs(d) > 1e-20f ? d : std::copysign(1e-20f, d);
       inv[a] = 1.0f / dd;
       oinv[a] = f[a] * inv[a];

@@ -1,4 +1,4 @@
-// sweep_pairs.h — the leaf-box sweep's device list (kernels.hip sweep_nearest,
+// sweep_pairs.h — the leaf-box sweep's device list (dev_sweep.h sweep_nearest,
 // DESIGN §2.1l), derived from the per-leaf list mrt_scene_create builds: one
 // record per group of at most two triangles, since the leaf test computes two
 // triangles at a time whatever the leaf holds.
@@ -90,7 +90,7 @@ inline void sweep_pair_records(const std::vector<float>& leaves, bool pair_singl
   }
 }
 
-// Phase 1's list (kernels.hip sweep_centre): record i of
+// Phase 1's list (dev_sweep.h sweep_centre): record i of
 // `pairs` as (c.xyz, bits(i), e.xyz, bits(1 << i)) — centre and half-extent
 // per axis with [c - e, c + e] containing [lo, hi] in exact arithmetic.  c is
 // the rounded midpoint and e the smallest float that is at least

@@ -17,7 +17,7 @@ struct ResolveArgs {
 
 struct ReprojectArgs {
   const float4* prev;      // counted image seen through the previous camera
-  const float4* prev_n;    // its guide planes (kernels.hip guide_kernel)
+  const float4* prev_n;    // its guide planes (kern_stage.h guide_kernel)
   const float4* prev_p;
   const float4* cur_n;     // the current camera's guide planes
   const float4* cur_p;

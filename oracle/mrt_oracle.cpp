@@ -486,7 +486,7 @@ static void build_cpu_bvh(const Scene& sc) {
 static inline float safe_inv(float d) { return 1.0f / (std::fabs(d) > 1e-20f ? d : std::copysign(1e-20f, d)); }
 
 // Culling rule of the CPU BVH's traversal.  It must not share the kernels'
-// error mode (their children are culled beyond h.t * (1 + 2^-11), kernels.hip
+// error mode (their children are culled beyond h.t * (1 + 2^-11), dev_traverse.h
 // kCullScale), or a triangle the kernels miss by the same
 // rounding would be missed here too and the comparison would pass:
 //   kCullWide — boxes culled only beyond bt * (1 + 2^-6): strictly more

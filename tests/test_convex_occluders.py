@@ -1,4 +1,4 @@
-"""CPU: the convex-occluder shadow decision (kernels.hip convex_occlusion,
+"""CPU: the convex-occluder shadow decision (dev_shadow.h convex_occlusion,
 occluders.h ConvexSet) against the brute-force leaf test, in float32.
 
 On C2's scene every triangle of the light-free occluder tree lies on one of
@@ -74,7 +74,7 @@ def _recip(x, fma):
 
 
 def _tri_bary(o, d, v0, v1, v2, fma):
-    """kernels.hip tri_bary (+ the leaf test's validity), float32."""
+    """dev_math.h tri_bary (+ the leaf test's validity), float32."""
     e1, e2 = (v1 - v0).astype(F), (v2 - v0).astype(F)
     p = _cross(d, e2, fma)
     det = _dot(e1, p, fma)
@@ -90,7 +90,7 @@ def _tri_bary(o, d, v0, v1, v2, fma):
 
 
 def _classify(o, d, tT, own, own_n, info, prims, target, fma, count=None):
-    """kernels.hip convex_occlusion, float32: 1 occluded, 0 clear by the slabs
+    """dev_shadow.h convex_occlusion, float32: 1 occluded, 0 clear by the slabs
     or the own face, -1 left to the exhaustive test of a solid (not occluded).
     count, if given, collects how many (ray, solid) tests had no entry face
     (the segment starts inside the padded solid): all of them, and those

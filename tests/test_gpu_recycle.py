@@ -1,4 +1,4 @@
-"""GPU: the stream kernel's capped sweep with recycled rays (kernels.hip
+"""GPU: the stream kernel's capped sweep with recycled rays (kern_bounce.h
 bounce_wave / sweep_nearest) changes no result.  A ray's answer
 is the minimum of (t, prim) over the same tested leaves under the same cull
 rule whatever pass tests them, so on the Cornell box (64 x 48 and a ragged

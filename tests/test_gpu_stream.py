@@ -1,4 +1,4 @@
-"""GPU: the wave-local streaming wavefront (kernels.hip::stream_kernel) —
+"""GPU: the wave-local streaming wavefront (kern_stream.h::stream_kernel) —
 every bounce of a frame batch in one launch, each wave running 64 rays of one
 bounce at a time from its own per-level queues — renders exactly what one
 launch per bounce (bounce_kernel, MRT_STREAM=0) renders.

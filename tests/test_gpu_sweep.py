@@ -1,4 +1,4 @@
-"""GPU: the leaf-box sweep (kernels.hip sweep_nearest) returns
+"""GPU: the leaf-box sweep (dev_sweep.h sweep_nearest) returns
 the walk's answer for every nearest query — on the Cornell box (64 x 48 and a
 ragged 97 x 61, L = 1 ... 5) and on generated rooms (96 x 64, L = 4), 3 frames:
 

@@ -1,5 +1,5 @@
 """GPU: the sweep over triangle-pair records with the culled-key early-out and
-the third key (kernels.hip sweep_nearest) returns the walk's
+the third key (dev_sweep.h sweep_nearest) returns the walk's
 answer — on the Cornell box (64 x 48 and a ragged 97 x 61, L = 3, 4, 5: a
 shorter path has no swept bounce) and on generated rooms (96 x 64, L = 4),
 3 frames, in both builds:

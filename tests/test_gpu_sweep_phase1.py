@@ -1,6 +1,6 @@
 """GPU: phase 1 of the nearest sweep with its bookkeeping in the lanes that
 hit only and, in the fast build, the centre / half-extent slab test on a list
-of its own (kernels.hip sweep_nearest / sweep_centre) changes no
+of its own (dev_sweep.h sweep_nearest / sweep_centre) changes no
 pixel.  Fresh scene and renderer per render, 3 frames, both builds:
 
 a. the sweep is bitwise equal, image and active-ray count, to MRT_SWEEP=0 (the

@@ -277,7 +277,7 @@ def test_exr_reader_formats(mrt_mod, tmp_path, comp, ptype):
 
 @pytest.mark.parametrize("L", [2, 4, 8])
 def test_stream_kernel_level_bound(L):
-    """kernels.hip::stream_kernel keeps a wave's queue per bounce level in
+    """kern_stream.h::stream_kernel keeps a wave's queue per bounce level in
     kStreamCap = 128 slots.  Its schedule — run the deepest level holding
     >= 64 rays, else up to 64 camera rays, else (camera rays exhausted) the
     deepest non-empty level; survivors append to the next level — must never

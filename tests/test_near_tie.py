@@ -1,7 +1,7 @@
 """The traversal's culling slack against the near tie of DESIGN.md §3.1.
 
 The kernels cull a BVH4 child only when its slab entry lies beyond the current
-hit's t by more than 2^-11 of it (kernels.hip kCullScale).  The committed
+hit's t by more than 2^-11 of it (dev_traverse.h kCullScale).  The committed
 regression ray (tests/golden/near_tie_ray.json) is the one that made a C5
 pixel differ between identical renders before that slack: the fast build's
 triangle test put prim 7787 at a t 1.85e-5 (relative) before 7787's own

@@ -6,7 +6,7 @@ light triangle.  The product leaves the triangles of culled supporting planes
 (walls, floor, ceiling) out of a second BVH that shadow rays from origins
 inside those planes traverse.  These tests restate the plane choice and check
 the claim it rests on with the kernels' own float32 ray-triangle arithmetic
-(kernels.hip tri_bary, with and without FMA contraction): from an origin
+(dev_math.h tri_bary, with and without FMA contraction): from an origin
 inside every culled plane by the margin, no culled triangle reports a hit in
 [0, t_light] — including origins at the margin and shadow rays grazing the
 ceiling the light hangs under.  (The GPU tests check the renders: precise
@@ -52,7 +52,7 @@ def _fma(a, b, c):
 
 
 def _tri_t(o, d, v0, e1, e2, fma):
-    """kernels.hip tri_bary in float32: (t, inside).  fma: False (IEEE), True
+    """dev_math.h tri_bary in float32: (t, inside).  fma: False (IEEE), True
     (FMA contraction) or "rcp" (FMA contraction and the fast build's approximate
     reciprocal, test_convex_occluders._recip)."""
     f32 = np.float32

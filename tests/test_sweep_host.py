@@ -1,4 +1,4 @@
-"""CPU: the leaf-box sweep list (kernels.hip sweep_nearest) as
+"""CPU: the leaf-box sweep list (dev_sweep.h sweep_nearest) as
 the host builds it — on the Cornell box and on generated rooms the list holds
 every leaf of the main tree exactly once, each with the bits of the child box
 its parent node holds, and the sweep is chosen exactly for trees of at most 32

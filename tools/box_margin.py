@@ -2,7 +2,7 @@
 """Measure the culling slack the kernels' traversal needs.
 
 The kernels cull a BVH child only when its slab entry lies beyond the current
-hit's t by more than 2^-11 of it (kernels.hip kCullScale).  A hit is safe from
+hit's t by more than 2^-11 of it (dev_traverse.h kCullScale).  A hit is safe from
 every visiting order iff each box on the path from the root to its leaf is
 entered no later than t_hit * (1 + 2^-11).  This tool traces the oracle's own
 rays of one full-size frame through the oracle's stages (renderer/Shaders.metal

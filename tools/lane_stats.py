@@ -31,7 +31,7 @@ NAMES = ["near_lanes", "near_calls", "near_int_iters", "near_int_lanes", "near_l
          "q01_wait_cycles", "q01_waits", "q23_wait_cycles", "q23_waits", "list_wait_cycles", "list_waits",
          "root_wait_cycles", "root_waits", "sweep_rec_wait_cycles", "sweep_rec_waits",
          "clock_pair_cycles", "clock_pairs",
-         # leaf-box sweep: third key rounds in which a lane tests, lanes testing in them
+         # slots 46-47 read zero: the sweep's third key is no longer built; the slots keep their numbers
          "sweep_key3_rounds", "sweep_key3_lanes"]
 # (cycles slot, events slot, output name) of the timed waits
 WAITS = [("q01_wait_cycles", "q01_waits", "q01"), ("q23_wait_cycles", "q23_waits", "q23"),
@@ -86,9 +86,6 @@ def main():
         if c.get("sweep_cull_rounds"):   # leaf-box sweep: the masked leaves' pop-and-cull rounds
             out["sweep_cull_rounds_per_call"] = round(c["sweep_cull_rounds"] / max(1, c["near_calls"]), 3)
             out["sweep_cull_util"] = util(c["sweep_cull_lanes"], c["sweep_cull_rounds"])
-        if c.get("sweep_key3_rounds"):   # the third key's round (every sweep call runs key 1's; key 2's is not counted apart)
-            out["sweep_key3_rounds_per_call"] = round(c["sweep_key3_rounds"] / max(1, c["near_calls"]), 3)
-            out["sweep_key3_util"] = util(c["sweep_key3_lanes"], c["sweep_key3_rounds"])
         if c.get("recycled_lanes"):   # capped sweep: against tools/walk_model's table
             # near_lanes counts a recycled ray once per pass: finished rays = lanes - recycled
             out["recycled_share_of_rays"] = round(c["recycled_lanes"] / max(1, c["near_lanes"] - c["recycled_lanes"]), 4)

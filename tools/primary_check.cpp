@@ -1,7 +1,7 @@
 // primary_check — CPU check that the camera-ray candidate lists (csrc/primary.cpp)
 // are conservative: for every pixel of a W x H frame and `jitters` noise
 // samples per pixel (plus the jitter extremes), the camera ray is formed with
-// camera_ray's float arithmetic (kernels.hip, = rayGenerator,
+// camera_ray's float arithmetic (dev_shade.h, = rayGenerator,
 // renderer/Shaders.metal:75-103) and its nearest hit found by brute force over
 // every triangle with the kernels' Moller-Trumbore arithmetic (tri_bary, IEEE
 // float, no contraction); a listed block must contain the winning triangle.
@@ -77,7 +77,7 @@ bool tri_bary(V o, V d, V v0, V e1, V e2, float& t) {
 
 const CameraBlock* g_cam = nullptr;   // a moved pinhole camera (arguments 8-20); null = the reference's
 
-// kernels.hip camera_ray with a camera block (pinhole): c = (u s, v s, -1),
+// dev_shade.h camera_ray with a camera block (pinhole): c = (u s, v s, -1),
 // w = normalize(c), d = (right w.x + up w.y) + forward (-w.z)
 template <bool F>
 void moved_camera_ray(const CameraBlock& c, float u, float v, V& o, V& d) {
@@ -119,7 +119,7 @@ void camera_ray(uint32_t x, uint32_t y, uint32_t W, uint32_t H, float nsx, float
     moved_camera_ray<F>(*g_cam, u, v, o, d);
     return;
   }
-  o = {kCameraX, kCameraY, kCameraZ};   // mrt_layout.h, shared with kernels.hip camera_ray
+  o = {kCameraX, kCameraY, kCameraZ};   // mrt_layout.h, shared with dev_shade.h camera_ray
   if (F) {   // m_div(a, b) = a * rcp(b), contracted where the compiler can
     const float rw = approx(1.0f / float(W)), rw1 = approx(1.0f / wm1), rh1 = approx(1.0f / hm1);
     const float aspect = float(H) * rw;

@@ -1,6 +1,6 @@
 // walk_model — CPU model of the stream kernel's nearest-hit queries on a small
 // all-in-LDS scene (C2: the Cornell box), to count what a 64-lane wave spends
-// in the while-while walk (kernels.hip traverse) and what other query shapes
+// in the while-while walk (dev_traverse.h traverse) and what other query shapes
 // would spend on the same rays in the same waves.
 //
 // Builds the product tree (scene.cpp, bvh.cpp, the options mrt_scene_create
@@ -80,7 +80,7 @@ void tcross(const float* a, const float* b, float* c) {
   c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// kernels.hip tri_bary + tri_pair's acceptance (nearest; ties -> lowest primitive)
+// dev_math.h tri_bary + tri_pair's acceptance (nearest; ties -> lowest primitive)
 void tri_test(const Ray& r, uint32_t k, Hit& h) {
   const float* T = &g_bvh.tris[12 * (size_t)k];
   float p[3], s[3], q[3];
@@ -310,7 +310,7 @@ bool differs(const Hit& a, const Hit& b) {
   return a.found != b.found || (a.found && (fb(a.t) != fb(b.t) || a.prim != b.prim));
 }
 
-// 6. phase 1 on the centre list (kernels.hip sweep_centre), in
+// 6. phase 1 on the centre list (dev_sweep.h sweep_centre), in
 // the fast build's arithmetic: a = fma(c, inv, -o inv), near / far =
 // fma(-+e, |inv|, a) per axis.  Phase 2 is the product's (two keys, the
 // early-out, pops re-tested on lo / hi with the fast build's slab form).  Per
