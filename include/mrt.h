@@ -71,6 +71,9 @@ typedef enum mrt_status {
 #define MRT_FLAG_DEBUG_MATERIAL 16u   /* DEBUG_MATERIAL 1 (Shaders.metal:7,142-147): at each hit the path radiance
                                          is set to fresnel(n, -wI, 1.0, 1.5) before emission and NEE add to it.
                                          Renderer and mrt_shade. */
+#define MRT_FLAG_MOMENTS 32u          /* the renderer accumulates the luminance moments of its frames beside the
+                                         image ("variance-guided denoising" below).  Renderer flag; not with
+                                         MRT_FLAG_NO_ACCUMULATE, not with shard_count > 1. */
 
 typedef struct mrt_scene mrt_scene;
 typedef struct mrt_renderer mrt_renderer;
@@ -197,6 +200,12 @@ int mrt_resolve_shadow(const mrt_scene* scene, uint32_t count, const void* inter
                        const void* shadow_rays, uint32_t flags, void* stream);
 int mrt_accumulate(const mrt_scene* scene, uint32_t width, uint32_t height, uint32_t frame_index,
                    const void* rays, float* image_rgba, uint32_t flags, void* stream);
+/* mrt_accumulate's counterpart for the luminance moments ("variance-guided
+ * denoising" below): with l = lum(ray.radiance), moments[p] =
+ * accumulate(moments[p], (l, l*l, 0), frame_index).  The rays are only read.
+ * flags: MRT_FLAG_PRECISE. */
+int mrt_moments(const mrt_scene* scene, uint32_t width, uint32_t height, uint32_t frame_index, const void* rays,
+                float* moments_rgba, uint32_t flags, void* stream);
 
 /* ---- camera ---------------------------------------------------------------
  * The reference's rayGenerator has one fixed camera; this is the same
@@ -346,6 +355,77 @@ int mrt_reproject(const float* prev, const float* prev_guide_n, const float* pre
                   const mrt_camera* prev_cam /* NULL = default */, const float* cur_guide_n, const float* cur_guide_p,
                   float* history_out, uint32_t width, uint32_t height, const mrt_reproject_params* params,
                   void* stream);
+
+/* ---- variance-guided denoising ----------------------------------------------
+ * The spatial half of SVGF (Schied et al., HPG 2017): a
+ * per-pixel variance estimate from accumulated luminance moments, and an
+ * A-Trous filter whose colour term it steers, so that one parameter set serves
+ * every frame count.  Not in the reference.  Device pointers throughout.
+ *
+ * lum(c) = (0.2126 r + 0.7152 g) + 0.0722 b.  A MOMENTS IMAGE is W*H float4
+ * (mean l, mean l*l, 0, 1): for every frame f, where the image gets
+ * accumulate(stored, c, f) the moments image gets accumulate(stored_m,
+ * (l, l*l, 0), f) with l = lum(c) — the same recurrence in the same frame
+ * order; f == 0 overwrites.  In the precise build l and l*l are rounded after
+ * each operation, in the order written; the fast build may contract.  As a
+ * counted image (temporal history above) its fourth channel is n, and it
+ * resolves and reprojects through mrt_temporal_resolve and mrt_reproject, which
+ * are linear in the first three channels. */
+typedef struct mrt_svgf_params {
+  uint32_t iterations;         /* 0..8 */
+  float sigma_luminance;       /* > 0 */
+  float sigma_plane;           /* > 0 */
+  uint32_t normal_log2_power;  /* e, 0..8 */
+  uint32_t min_frames;         /* >= 2: counts from which a pixel's own moments are trusted */
+} mrt_svgf_params;
+/* Host only.  iterations = 5, sigma_luminance = 4, sigma_plane = 0.01,
+ * normal_log2_power = 6, min_frames = 4. */
+int mrt_svgf_params_default(mrt_svgf_params* out);
+/* Host only.  MRT_ERR_INVALID (with a message naming the field) for a field
+ * outside the ranges above, a non-finite one included. */
+int mrt_svgf_params_check(const mrt_svgf_params* p);
+/* variance[p] (W*H floats) estimates the variance of the pixel's MEAN from the
+ * counted moments (mu1, mu2, ., n) = moments[p]; params->iterations and
+ * sigma_luminance are not used.
+ *   p not filterable (word_p >= 0x80000000): 0.
+ *   p is USABLE when mu1 and mu2 are finite and n > 0.
+ *   p usable and n >= min_frames: the temporal estimate max(0, mu2 - mu1^2) / (n - 1).
+ *   Otherwise the spatial estimate over the 7x7 window, (dx, dy) in {-3..3}^2,
+ *   dy outer and dx inner, the centre included: a tap q counts iff it is inside
+ *   the image, filterable, word_q == word_p and usable, with weight
+ *     w = D^(2^e) exp(-|n_p.(x_q - x_p)| / (sigma_plane t_p)) n_q,
+ *   D = max(0, n_p.n_q) as in mrt_denoise; a1 = sum w mu1_q / sum w,
+ *   a2 = sum w mu2_q / sum w, and the result is
+ *   max(0, a2 - a1^2) / max(n_p, 1), or 0 if sum w is not > 0.
+ *   A result that is negative or not finite (sums that overflow) is replaced by 0:
+ *   the output is never negative and never non-finite.
+ * The inputs are only read.  params == NULL, or `variance` overlapping an
+ * input, is MRT_ERR_INVALID. */
+int mrt_variance(const float* moments, const float* guide_n, const float* guide_p, float* variance, uint32_t width,
+                 uint32_t height, const mrt_svgf_params* params, void* stream);
+/* mrt_denoise's definition — the same k, steps s = 2^i, tap order and tap
+ * conditions, a pixel that is not filterable keeps its value, alpha copied
+ * from `image` — with two changes.  v^0 = `variance` (W*H floats).
+ *   The colour weight is replaced by
+ *     exp(-|lum(c^i_q) - lum(c^i_p)| / (sigma_luminance sqrt(g_p) + 1e-6))   (1 if c^i_p is not finite),
+ *   g_p = the average of v^i over the 3x3 pixels around p (offsets of ONE
+ *   pixel, not s) with weights (1/4, 1/2, 1/4)^2, over the taps inside the
+ *   image, renormalised by the weights of those taps.
+ *   The variance is filtered with the colour: c^(i+1)_p = sum w c^i_q / sum w,
+ *   v^(i+1)_p = sum w^2 v^i_q / (sum w)^2 (evaluated as (sum w^2 v / sum w) /
+ *   sum w); both stay as they are if the sum is 0, and a pixel that is not
+ *   filterable keeps its v.
+ * variance_out (W*H floats, may be NULL) receives v^iterations.  iterations = 0
+ * copies image to out and variance to variance_out.  A non-finite or negative
+ * input variance is outside the contract.  The iterations ping-pong between
+ * `out` and `scratch` (W*H*4 floats each; between iterations their fourth
+ * channel carries v).  Any overlap among out, scratch, variance_out and any
+ * other buffer, and params == NULL, is MRT_ERR_INVALID.
+ * mrt_debug_denoise_path selects between the two implementations of an
+ * iteration here as it does for mrt_denoise. */
+int mrt_denoise_variance(const float* image, const float* variance, const float* guide_n, const float* guide_p,
+                         float* out, float* scratch, float* variance_out /* may be NULL */, uint32_t width,
+                         uint32_t height, const mrt_svgf_params* params, void* stream);
 
 /* ---- renderer (B-1) ------------------------------------------------------ */
 typedef struct mrt_renderer_desc {
@@ -505,8 +585,38 @@ int mrt_renderer_save_resolved(mrt_renderer* r, const char* path);   /* .pfm / .
 /* mrt_renderer_resolve, then mrt_denoise of the resolved buffer into the
  * renderer's denoised buffer (read_denoised, MRT_DISPLAY_DENOISED).  params
  * NULL = mrt_denoise_params_default(max(frames accumulated, 1)), which ignores
- * the history's length: conservative; a host that knows better passes its own. */
+ * the history's length: conservative; a host that knows better passes its own,
+ * or uses mrt_renderer_denoise_variance, whose filter widths follow the variance. */
 int mrt_renderer_denoise_resolved(mrt_renderer* r, const mrt_denoise_params* params);
+/* Variance-guided denoising on a renderer created with MRT_FLAG_MOMENTS (the
+ * section of that name above).  Such a renderer owns a moments image (16 B per
+ * pixel, allocated at create, re-made by resize) that every draw updates with
+ * the image, from the one read of the frames' radiance; mrt_renderer_reset
+ * restarts it as it restarts the image.  mrt_renderer_move_camera also carries
+ * the moments: moments_prev = resolve(moments, frames, moments history if
+ * valid) and moments history = reproject(moments_prev, ...) with the guide
+ * planes, camera and parameters of the colour history (two more 16-B-per-pixel
+ * buffers, allocated at the first move); its validity is the colour
+ * history's.  Without the flag nothing of this exists, and every call below
+ * that needs it is MRT_ERR_STATE.
+ * mrt_renderer_read_moments synchronises as read_image does;
+ * mrt_renderer_moments returns the device pointer. */
+int mrt_renderer_read_moments(mrt_renderer* r, float* rgba, size_t count);
+int mrt_renderer_moments(mrt_renderer* r, float** device_moments);
+/* On the main stream, without a host wait: the guide planes if they are not
+ * current; resolved = resolve(image, frames, history if valid) (as
+ * mrt_renderer_resolve: read_resolved gives it); M = resolve(moments, frames,
+ * moments history if valid); mrt_variance(M) into a plane the renderer owns;
+ * mrt_denoise_variance(resolved, variance, ...) into the denoised buffer
+ * (read_denoised, save_denoised, MRT_DISPLAY_DENOISED).  params NULL =
+ * mrt_svgf_params_default.  The buffers are allocated at the first call and
+ * re-made by resize.  MRT_ERR_STATE without MRT_FLAG_MOMENTS, and when no frame
+ * has been accumulated and there is no valid history. */
+int mrt_renderer_denoise_variance(mrt_renderer* r, const mrt_svgf_params* params);
+/* The variance plane (W*H floats) the last mrt_renderer_denoise_variance fed to
+ * the filter; synchronises.  MRT_ERR_STATE before one has run at the current
+ * size.  The hook for adaptive sampling. */
+int mrt_renderer_read_variance(mrt_renderer* r, float* plane, size_t count);
 int mrt_renderer_stats(const mrt_renderer* r, mrt_stats* stats);
 int mrt_renderer_destroy(mrt_renderer* r);
 
@@ -737,6 +847,13 @@ int mrt_debug_denoise_path(uint32_t path);
 int mrt_debug_denoise_step(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
                            uint32_t width, uint32_t height, const mrt_denoise_params* params, uint32_t step_log2,
                            uint32_t path, void* stream);
+/* Measurement entry (tools/variance_time.py): ONE iteration of
+ * mrt_denoise_variance at step 2^step_log2 (<= 14) with implementation `path`,
+ * as a first iteration (v from `variance`) that is not the last (out.w = v');
+ * params->iterations is not used.  Touches no process-wide state. */
+int mrt_debug_denoise_variance_step(const float* image, const float* variance, const float* guide_n,
+                                    const float* guide_p, float* out, uint32_t width, uint32_t height,
+                                    const mrt_svgf_params* params, uint32_t step_log2, uint32_t path, void* stream);
 /* Number of HIP devices visible (0 when none; never fails). */
 int mrt_device_count(void);
 

@@ -29,6 +29,7 @@
  *                   [--eye x,y,z] [--target x,y,z] [--up x,y,z] [--fov DEGREES]
  *                   [--aperture LENS_RADIUS] [--focus DISTANCE]
  *                   [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]
+ *                   [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]
  *                   [--orbit-steps K --orbit-degrees D]
  * --orbit-steps K --orbit-degrees D (single rank only): after the first --spp
  * frames, K times: the eye turns about the vertical axis through the target
@@ -43,6 +44,11 @@
  * the whole image, denoises) mrt_renderer_denoise with the defaults for --spp
  * frames, and --out receives the denoised image (mrt_renderer_save_denoised);
  * the two other options override a default and imply --denoise.
+ * --denoise-variance (single rank only, not with --denoise): the renderer
+ * accumulates luminance moments (MRT_FLAG_MOMENTS) and --out receives the image
+ * of mrt_renderer_denoise_variance, run after the last draw (with --orbit-steps
+ * after the last move's draw); --svgf-iterations and --svgf-sigma-luminance
+ * override a default of mrt_svgf_params_default and imply it.
  * The camera options go through mrt_camera_look_at / mrt_renderer_set_camera
  * (fov: full horizontal angle; --aperture > 0: a thin lens, focused at --focus
  * or else on the target); without any of them the reference's camera renders.
@@ -78,6 +84,10 @@ typedef struct {
   int denoise, denoise_iterations_set, denoise_sigma_set;
   uint32_t denoise_iterations;
   float denoise_sigma_color;
+  /* variance-guided denoising (mrt_renderer_denoise_variance) */
+  int denoise_variance, svgf_iterations_set, svgf_sigma_set;
+  uint32_t svgf_iterations;
+  float svgf_sigma_luminance;
   /* orbit with temporal history (mrt_renderer_move_camera) */
   uint32_t orbit_steps;
   int orbit_degrees_set;
@@ -104,6 +114,7 @@ static void usage(void) {
           "                  [--eye x,y,z] [--target x,y,z] [--up x,y,z] [--fov DEGREES]\n"
           "                  [--aperture LENS_RADIUS] [--focus DISTANCE]\n"
           "                  [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]\n"
+          "                  [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]\n"
           "                  [--orbit-steps K --orbit-degrees D]\n"
           "  --orbit-steps K --orbit-degrees D (one rank): after the first --spp frames, K times: turn the eye by D\n"
           "  degrees about the world's vertical (y) axis through the target, whatever --up says, move the camera\n"
@@ -159,7 +170,10 @@ static int parse(int argc, char** argv, options* o) {
     else if (VAL("--denoise-sigma-color")) { o->denoise_sigma_color = strtof(v, NULL); o->denoise = o->denoise_sigma_set = 1; }
     else if (VAL("--orbit-steps")) o->orbit_steps = (uint32_t)strtoul(v, NULL, 0);
     else if (VAL("--orbit-degrees")) { o->orbit_degrees = strtof(v, NULL); o->orbit_degrees_set = 1; }
+    else if (VAL("--svgf-iterations")) { o->svgf_iterations = (uint32_t)strtoul(v, NULL, 0); o->denoise_variance = o->svgf_iterations_set = 1; }
+    else if (VAL("--svgf-sigma-luminance")) { o->svgf_sigma_luminance = strtof(v, NULL); o->denoise_variance = o->svgf_sigma_set = 1; }
     else if (strcmp(a, "--denoise") == 0) o->denoise = 1;
+    else if (strcmp(a, "--denoise-variance") == 0) o->denoise_variance = 1;
     else if (strcmp(a, "--precise") == 0) o->flags |= MRT_FLAG_PRECISE;
     else if (strcmp(a, "--static-noise") == 0) o->flags |= MRT_FLAG_STATIC_NOISE;
     else if (strcmp(a, "--no-accumulate") == 0) o->flags |= MRT_FLAG_NO_ACCUMULATE;
@@ -182,6 +196,15 @@ static int parse(int argc, char** argv, options* o) {
     fprintf(stderr, "mrt_render: --orbit-steps is single rank only (a sharded renderer keeps no temporal history)\n");
     return -1;
   }
+  if (o->denoise_variance && o->denoise) {
+    fprintf(stderr, "mrt_render: --denoise-variance and --denoise exclude each other\n");
+    return -1;
+  }
+  if (o->denoise_variance && o->gpus > 1) {
+    fprintf(stderr, "mrt_render: --denoise-variance is single rank only (a sharded renderer keeps no moments)\n");
+    return -1;
+  }
+  if (o->denoise_variance) o->flags |= MRT_FLAG_MOMENTS;
   return 0;
 }
 
@@ -325,7 +348,14 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
   mrt_stats st;
   if (mrt_renderer_stats(r, &st)) return die("mrt_renderer_stats");
   if (rank == 0) {
-    if (o->denoise) {
+    if (o->denoise_variance) {
+      mrt_svgf_params vp;
+      if (mrt_svgf_params_default(&vp)) return die("mrt_svgf_params_default");
+      if (o->svgf_iterations_set) vp.iterations = o->svgf_iterations;
+      if (o->svgf_sigma_set) vp.sigma_luminance = o->svgf_sigma_luminance;
+      if (mrt_renderer_denoise_variance(r, &vp)) return die("mrt_renderer_denoise_variance");
+      if (mrt_renderer_save_denoised(r, o->out)) return die("mrt_renderer_save_denoised");
+    } else if (o->denoise) {
       mrt_denoise_params dp;
       if (mrt_denoise_params_default(st.frame_index, &dp)) return die("mrt_denoise_params_default");
       if (o->denoise_iterations_set) dp.iterations = o->denoise_iterations;

@@ -330,6 +330,13 @@ struct mrt_renderer {
   mrt::host::DevBuf prev_guide_n, prev_guide_p, temporal_prev, history, resolved;
   bool history_valid = false;      // `history` holds the reprojection into the camera in force
   bool resolved_current = false;   // a resolve has run at the current size
+  // variance-guided denoising (MRT_FLAG_MOMENTS): the moments image lives with
+  // the image (create, resize); its scratch and history are allocated at the
+  // first move, the resolved moments and the variance plane at the first
+  // mrt_renderer_denoise_variance; all re-made by resize.  The moments
+  // history's validity is history_valid.
+  mrt::host::DevBuf moments, moments_prev, moments_history, moments_resolved, variance;
+  bool variance_current = false;   // a denoise_variance has run at the current size
   struct DisplaySlot {          // mrt_renderer_display_enqueue / _map: pinned copies of the blit
     float* host = nullptr;
     size_t floats = 0;

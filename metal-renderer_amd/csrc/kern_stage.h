@@ -18,7 +18,27 @@ namespace mrt { namespace MRT_NS { namespace {
 // its drain (the 2-stream period was launch + ~0.33 ms on C2).  One call,
 // alternating: C2 10755 / 10762 -> 11024 / 11033 Mpaths/s (+2.5 %), C2 L=5
 // +2.0 %, C2 1/8 share 10340 -> 10733 (+3.7 %), C4 +0.5 %.
+// MOMENTS (MRT_FLAG_MOMENTS): the luminance moments image gets the same
+// recurrence over (l, l*l, 0), l = lum(c), from the same read of the radiance
+// rows — two more running means in registers.  With two frames' loads in
+// flight instead of four it stays within the 32 VGPRs without scratch (27;
+// with four the compiler takes 38) (include/mrt.h "variance-guided denoising").
 constexpr uint32_t kAccLoads = 4;
+__device__ __forceinline__ float luminance(V3 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }
+// accumulate_value of (l, l*l) into the two running means
+__device__ __forceinline__ void accumulate_moments(float& m1, float& m2, V3 c, uint32_t f) {
+  const float l = luminance(c);
+  const float l2 = l * l;
+  if (f > 0) {
+    const float factor = m_div(float(f), float(f + 1));
+    m1 = mixf(l, m1, factor);
+    m2 = mixf(l2, m2, factor);
+  } else {
+    m1 = l;
+    m2 = l2;
+  }
+}
+template <bool MOMENTS>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_vgpr(32))) void accumulate_frame_kernel(AccumArgs a) {
   if (a.counters && blockIdx.x == 0) {   // the draw's render launches have completed (stream order)
     for (uint32_t i = threadIdx.x; i < a.copy_words; i += kBlock) a.host_counters[i] = a.counters[i];
@@ -43,20 +63,37 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_vgpr(32))) void a
       continue;
     }
     float4 cur = a.frame_index > 0 ? a.image[pix] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float m1 = 0.0f, m2 = 0.0f;
+    if constexpr (MOMENTS) {
+      if (a.frame_index > 0) {
+        const float4 m = a.moments[pix];
+        m1 = m.x;
+        m2 = m.y;
+      }
+    }
+    constexpr uint32_t kLoads = MOMENTS ? kAccLoads / 2 : kAccLoads;
     uint32_t j = 0;
-    for (; j + kAccLoads <= a.batch; j += kAccLoads) {
-      float4 c[kAccLoads];
+    for (; j + kLoads <= a.batch; j += kLoads) {
+      float4 c[kLoads];
 #pragma unroll
-      for (uint32_t k = 0; k < kAccLoads; ++k) {
+      for (uint32_t k = 0; k < kLoads; ++k) {
         typedef float v4f __attribute__((ext_vector_type(4)));
         const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(rad + (size_t)(j + k) * a.num_slots));
         c[k] = make_float4(v.x, v.y, v.z, v.w);
       }
 #pragma unroll
-      for (uint32_t k = 0; k < kAccLoads; ++k) cur = accumulate_value(cur, mk(c[k]), a.frame_index + j + k);
+      for (uint32_t k = 0; k < kLoads; ++k) {
+        cur = accumulate_value(cur, mk(c[k]), a.frame_index + j + k);
+        if constexpr (MOMENTS) accumulate_moments(m1, m2, mk(c[k]), a.frame_index + j + k);
+      }
     }
-    for (; j < a.batch; ++j) cur = accumulate_value(cur, mk(rad[(size_t)j * a.num_slots]), a.frame_index + j);
+    for (; j < a.batch; ++j) {
+      const V3 c = mk(rad[(size_t)j * a.num_slots]);
+      cur = accumulate_value(cur, c, a.frame_index + j);
+      if constexpr (MOMENTS) accumulate_moments(m1, m2, c, a.frame_index + j);
+    }
     a.image[pix] = cur;
+    if constexpr (MOMENTS) a.moments[pix] = make_float4(m1, m2, 0.0f, 1.0f);
   }
 }
 
@@ -196,6 +233,15 @@ __global__ __launch_bounds__(kBlock) void accumulate_kernel(uint32_t W, uint32_t
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= W * H) return;
   accumulate_pixel(image, i, mk(rays[i].radiance[0], rays[i].radiance[1], rays[i].radiance[2]), accumulate ? f : 0u);
+}
+
+// mrt_moments: accumulate_kernel over (l, l*l, 0), l = lum(radiance)
+__global__ __launch_bounds__(kBlock) void moments_kernel(uint32_t W, uint32_t H, uint32_t f, const RefRay* rays,
+                                                         float4* moments) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= W * H) return;
+  const float l = luminance(mk(rays[i].radiance[0], rays[i].radiance[1], rays[i].radiance[2]));
+  accumulate_pixel(moments, i, mk(l, l * l, 0.0f), f);
 }
 
 }  // namespace

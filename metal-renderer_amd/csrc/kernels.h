@@ -170,6 +170,9 @@ struct AccumArgs {
   uint32_t* counters;
   uint32_t* host_counters;
   uint32_t copy_words, span_word, span_words, zero_words;
+  // MRT_FLAG_MOMENTS: the luminance moments image (mean l, mean l^2, 0, 1), updated with the
+  // image from the one read of the radiance rows; null = none.  Last, so that no other argument moves.
+  float4* moments;
 };
 
 constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_shade flags
@@ -193,6 +196,9 @@ constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_sha
                             const RefShadowRay* srays, hipStream_t s);                                    \
   hipError_t launch_accumulate(uint32_t W, uint32_t H, uint32_t frame_index, const RefRay* rays,          \
                                float* image, bool accumulate, hipStream_t s);                             \
+  /* mrt_moments: the luminance moments of the rays' radiance, accumulated as launch_accumulate does */   \
+  hipError_t launch_moments(uint32_t W, uint32_t H, uint32_t frame_index, const RefRay* rays,             \
+                            float* moments, hipStream_t s);                                               \
   /* persistent grid size of the fused bounce kernel for this scene */                                    \
   hipError_t bounce_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t blocks_per_cu,          \
                          uint32_t* grid);                                                                \

@@ -322,7 +322,15 @@ hipError_t launch_accumulate(uint32_t W, uint32_t H, uint32_t frame_index, const
 
 hipError_t launch_accumulate_frame(const AccumArgs& a, hipStream_t s) {
   const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(blocks_for(a.num_slots), 4096));
-  accumulate_frame_kernel<<<dim3(blocks), dim3(kBlock), 0, s>>>(a);
+  if (a.moments) accumulate_frame_kernel<true><<<dim3(blocks), dim3(kBlock), 0, s>>>(a);
+  else accumulate_frame_kernel<false><<<dim3(blocks), dim3(kBlock), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_moments(uint32_t W, uint32_t H, uint32_t frame_index, const RefRay* rays, float* moments,
+                          hipStream_t s) {
+  moments_kernel<<<dim3(blocks_for(W * H)), dim3(kBlock), 0, s>>>(W, H, frame_index, rays,
+                     reinterpret_cast<float4*>(moments));
   return hipGetLastError();
 }
 

@@ -246,6 +246,10 @@ int alloc_frame_buffers(mrt_renderer* r) {
     HIP_TRY(hipMalloc(&r->image, (size_t)W * H * 16));
   }
   HIP_TRY(hipMemsetAsync(r->image, 0, (size_t)W * H * 16, r->stream));
+  if (r->desc.flags & MRT_FLAG_MOMENTS) {
+    HIP_TRY(r->moments.alloc((size_t)W * H * 16));
+    HIP_TRY(hipMemsetAsync(r->moments.p, 0, (size_t)W * H * 16, r->stream));
+  }
   r->image_foreign = false;
   r->frame_index = 0;
   r->stats = mrt_stats{};
@@ -378,6 +382,7 @@ mrt::AccumArgs accum_args(const mrt_renderer* r, const DrawRecord& d, const Batc
   acc.radiance = fs.radiance.as<float4>();
   acc.image = reinterpret_cast<float4*>(r->image);
   acc.accumulate = (r->desc.flags & MRT_FLAG_NO_ACCUMULATE) ? 0u : 1u;
+  acc.moments = r->moments.as<float4>();   // (null without MRT_FLAG_MOMENTS)
   if (fold) {
     acc.counters = d.counters.as<uint32_t>();
     acc.host_counters = static_cast<uint32_t*>(d.host_dev);
@@ -533,6 +538,15 @@ int resolve_into(mrt_renderer* r, DevBuf& out) {
                               out.as<float>(), r->desc.width, r->desc.height, r->stream);
 }
 
+// the same for the moments image and its history (MRT_FLAG_MOMENTS)
+int resolve_moments_into(mrt_renderer* r, DevBuf& out) {
+  const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
+  if (out.bytes != bytes || !out.p) HIP_TRY(out.alloc(bytes));
+  return mrt_temporal_resolve(r->moments.as<float>(), r->frame_index,
+                              r->history_valid ? r->moments_history.as<float>() : nullptr, out.as<float>(),
+                              r->desc.width, r->desc.height, r->stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -551,8 +565,12 @@ int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out) {
   const uint32_t S = std::max<uint32_t>(1, desc->shard_count);
   if (desc->shard_rank >= S) return fail(MRT_ERR_INVALID, "shard_rank >= shard_count");
   constexpr uint32_t kKnownFlags = MRT_FLAG_PRECISE | MRT_FLAG_PROFILE | MRT_FLAG_STATIC_NOISE |
-                                   MRT_FLAG_NO_ACCUMULATE | MRT_FLAG_DEBUG_MATERIAL;
+                                   MRT_FLAG_NO_ACCUMULATE | MRT_FLAG_DEBUG_MATERIAL | MRT_FLAG_MOMENTS;
   if (desc->flags & ~kKnownFlags) return fail(MRT_ERR_INVALID, "unknown renderer flags");
+  if ((desc->flags & MRT_FLAG_MOMENTS) && (desc->flags & MRT_FLAG_NO_ACCUMULATE))
+    return fail(MRT_ERR_INVALID, "MRT_FLAG_MOMENTS needs an accumulated image (not with MRT_FLAG_NO_ACCUMULATE)");
+  if ((desc->flags & MRT_FLAG_MOMENTS) && S > 1)
+    return fail(MRT_ERR_INVALID, "MRT_FLAG_MOMENTS: a sharded moments image is not supported (shard_count > 1)");
   std::unique_ptr<mrt_renderer> r(new mrt_renderer());
   r->scene = desc->scene;
   r->desc = *desc;
@@ -676,6 +694,7 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   r->x.slab_floats = 0;    // the exchange buffers are re-sized for the new image at the next exchange
   r->guides_current = r->denoised_current = false;
   r->history_valid = r->resolved_current = false;
+  r->variance_current = false;
   if (r->denoised.p) {     // a renderer that has denoised keeps its buffers, at the new size
     const size_t bytes = (size_t)width * height * 16;
     HIP_TRY(r->guide_n.alloc(bytes));
@@ -686,8 +705,9 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   {   // likewise the temporal history's buffers, each where it exists
     const size_t bytes = (size_t)width * height * 16;
     for (DevBuf* b : {&r->guide_n, &r->guide_p, &r->prev_guide_n, &r->prev_guide_p, &r->temporal_prev, &r->history,
-                      &r->resolved})
+                      &r->resolved, &r->moments_prev, &r->moments_history, &r->moments_resolved})
       if (b->p && b->bytes != bytes) HIP_TRY(b->alloc(bytes));
+    if (r->variance.p && r->variance.bytes != bytes / 4) HIP_TRY(r->variance.alloc(bytes / 4));
   }
   return alloc_frame_buffers(r);
 }
@@ -967,12 +987,20 @@ int mrt_renderer_move_camera(mrt_renderer* r, const mrt_camera* cam, const mrt_r
   HIP_TRY(hipSetDevice(r->scene->device));
   for (DevBuf* b : {&r->prev_guide_n, &r->prev_guide_p, &r->temporal_prev, &r->history})   // the first move only
     if (b->bytes != bytes || !b->p) HIP_TRY(b->alloc(bytes));
+  const bool moments = (r->desc.flags & MRT_FLAG_MOMENTS) != 0;
+  if (moments)
+    for (DevBuf* b : {&r->moments_prev, &r->moments_history})
+      if (b->bytes != bytes || !b->p) HIP_TRY(b->alloc(bytes));
   // what the old camera saw: its guide planes, and everything accumulated
   // through it (a scratch image: the history itself is replaced last)
   rc = ensure_guides(r);
   if (rc) return rc;
   rc = resolve_into(r, r->temporal_prev);
   if (rc) return rc;
+  if (moments) {   // the moments travel with the colour, through the same two kernels
+    rc = resolve_moments_into(r, r->moments_prev);
+    if (rc) return rc;
+  }
   // the new camera, as mrt_renderer_set_camera installs it: failing here
   // leaves the previous camera in force, nothing reset, the history as it was
   const mrt_camera old = r->camera;
@@ -996,6 +1024,12 @@ int mrt_renderer_move_camera(mrt_renderer* r, const mrt_camera* cam, const mrt_r
   rc = mrt_reproject(r->temporal_prev.as<float>(), r->prev_guide_n.as<float>(), r->prev_guide_p.as<float>(), &old,
                      r->guide_n.as<float>(), r->guide_p.as<float>(), r->history.as<float>(), W, H, &p, r->stream);
   if (rc) return rc;
+  if (moments) {
+    rc = mrt_reproject(r->moments_prev.as<float>(), r->prev_guide_n.as<float>(), r->prev_guide_p.as<float>(), &old,
+                       r->guide_n.as<float>(), r->guide_p.as<float>(), r->moments_history.as<float>(), W, H, &p,
+                       r->stream);
+    if (rc) return rc;
+  }
   r->history_valid = true;
   return MRT_OK;
 }
@@ -1045,6 +1079,80 @@ int mrt_renderer_denoise_resolved(mrt_renderer* r, const mrt_denoise_params* par
                    r->denoise_scratch.as<float>(), W, H, &p, r->stream);
   if (rc) return rc;
   r->denoised_current = true;
+  return MRT_OK;
+}
+
+// ---- variance-guided denoising (include/mrt.h: mrt_renderer_denoise_variance) ----
+int mrt_renderer_read_moments(mrt_renderer* r, float* rgba, size_t count) {
+  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
+  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
+  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
+  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
+    return fail(MRT_ERR_STATE, "mrt_renderer_read_moments: the renderer was created without MRT_FLAG_MOMENTS");
+  const int rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(rgba, r->moments.p, need * 4, hipMemcpyDeviceToHost));
+  return MRT_OK;
+}
+
+int mrt_renderer_moments(mrt_renderer* r, float** device_moments) {
+  if (!r || !device_moments) return fail(MRT_ERR_INVALID, "null argument");
+  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
+    return fail(MRT_ERR_STATE, "mrt_renderer_moments: the renderer was created without MRT_FLAG_MOMENTS");
+  *device_moments = r->moments.as<float>();
+  return MRT_OK;
+}
+
+int mrt_renderer_denoise_variance(mrt_renderer* r, const mrt_svgf_params* params) {
+  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
+  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
+    return fail(MRT_ERR_STATE, "mrt_renderer_denoise_variance: the renderer was created without MRT_FLAG_MOMENTS");
+  if (r->frame_index == 0 && !r->history_valid)
+    return fail(MRT_ERR_STATE, "mrt_renderer_denoise_variance: no frame accumulated and no valid history");
+  mrt_svgf_params p;
+  if (params) p = *params;
+  else (void)mrt_svgf_params_default(&p);
+  int rc = mrt_svgf_params_check(&p);
+  if (rc) return rc;
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  const size_t bytes = (size_t)W * H * 16;
+  HIP_TRY(hipSetDevice(r->scene->device));
+  for (DevBuf* b : {&r->denoised, &r->denoise_scratch})
+    if (b->bytes != bytes || !b->p) {
+      r->denoised_current = false;
+      HIP_TRY(b->alloc(bytes));
+    }
+  if (r->variance.bytes != bytes / 4 || !r->variance.p) {
+    r->variance_current = false;
+    HIP_TRY(r->variance.alloc(bytes / 4));
+  }
+  rc = ensure_guides(r);
+  if (rc) return rc;
+  rc = mrt_renderer_resolve(r);
+  if (rc) return rc;
+  rc = resolve_moments_into(r, r->moments_resolved);
+  if (rc) return rc;
+  rc = mrt_variance(r->moments_resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
+                    r->variance.as<float>(), W, H, &p, r->stream);
+  if (rc) return rc;
+  r->variance_current = true;
+  rc = mrt_denoise_variance(r->resolved.as<float>(), r->variance.as<float>(), r->guide_n.as<float>(),
+                            r->guide_p.as<float>(), r->denoised.as<float>(), r->denoise_scratch.as<float>(), nullptr, W,
+                            H, &p, r->stream);
+  if (rc) return rc;
+  r->denoised_current = true;
+  return MRT_OK;
+}
+
+int mrt_renderer_read_variance(mrt_renderer* r, float* plane, size_t count) {
+  if (!r || !plane) return fail(MRT_ERR_INVALID, "null argument");
+  const size_t need = (size_t)r->desc.width * r->desc.height;
+  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
+  if (!r->variance_current)
+    return fail(MRT_ERR_STATE, "no mrt_renderer_denoise_variance has run at the renderer's current size");
+  const int rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(plane, r->variance.p, need * 4, hipMemcpyDeviceToHost));
   return MRT_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "image.h"
 #include "noise.h"
 #include "temporal.h"
+#include "variance.h"
 
 using namespace mrt::host;
 
@@ -67,6 +68,63 @@ bool planes_overlap(const void* a, const void* b, size_t bytes) {
   const char* p = (const char*)a;
   const char* q = (const char*)b;
   return p < q + bytes && q < p + bytes;
+}
+
+// mrt_denoise_variance: `iterations` iterations from step 2^first_log2 on with
+// implementation `path`; last: the final one writes the image's alpha and
+// variance_out (else the variance stays in out's fourth channel)
+int svgf_run(const float* image, const float* variance, const float* guide_n, const float* guide_p, float* out,
+             float* scratch, float* variance_out, uint32_t W, uint32_t H, const mrt_svgf_params* params,
+             uint32_t iterations, uint32_t first_log2, uint32_t path, bool last, void* stream) {
+  // (scratch may be null for a single iteration, which writes `out` alone: the measurement entry)
+  if (!image || !variance || !guide_n || !guide_p || !out || (!scratch && iterations != 1) || !params || W == 0 ||
+      H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_denoise_variance: bad argument");
+  const size_t bytes = (size_t)W * H * 16, plane = (size_t)W * H * 4;
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const char* p = (const char*)a;
+    const char* q = (const char*)b;
+    return p < q + nb && q < p + na;
+  };
+  // no written buffer may overlap any other buffer
+  const struct { const void* p; size_t n; bool written; } b[] = {
+      {image, bytes, false}, {variance, plane, false}, {guide_n, bytes, false}, {guide_p, bytes, false},
+      {out, bytes, true},    {scratch, bytes, true},   {variance_out, plane, true}};
+  for (size_t i = 0; i < 7; ++i)
+    for (size_t j = i + 1; j < 7; ++j)
+      if ((b[i].written || b[j].written) && b[i].p && b[j].p && overlap(b[i].p, b[i].n, b[j].p, b[j].n))
+        return fail(MRT_ERR_INVALID, "mrt_denoise_variance: out, scratch and variance_out must not overlap any buffer");
+  const int rc = mrt_svgf_params_check(params);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t N = iterations;
+  if (N == 0) {
+    HIP_TRY(hipMemcpyAsync(out, image, bytes, hipMemcpyDeviceToDevice, s));
+    if (variance_out) HIP_TRY(hipMemcpyAsync(variance_out, variance, plane, hipMemcpyDeviceToDevice, s));
+    return MRT_OK;
+  }
+  mrt::SvgfArgs a{};
+  a.guide_n = reinterpret_cast<const float4*>(guide_n);
+  a.guide_p = reinterpret_cast<const float4*>(guide_p);
+  a.width = W;
+  a.height = H;
+  a.sigma_luminance = params->sigma_luminance;
+  a.sigma_plane = params->sigma_plane;
+  a.normal_log2_power = params->normal_log2_power;
+  const float* src = image;
+  for (uint32_t i = 0; i < N; ++i) {
+    float* dst = ((N - 1 - i) & 1u) ? scratch : out;   // the last iteration writes `out`
+    const bool final = last && i + 1 == N;
+    a.src = reinterpret_cast<const float4*>(src);
+    a.var_in = i == 0 ? variance : nullptr;
+    a.dst = reinterpret_cast<float4*>(dst);
+    a.alpha = final ? reinterpret_cast<const float4*>(image) : nullptr;
+    a.var_out = final ? variance_out : nullptr;
+    a.step = 1u << (i + first_log2);
+    HIP_TRY(mrt::launch_svgf_atrous(a, path, s));
+    src = dst;
+  }
+  return MRT_OK;
 }
 
 }  // namespace
@@ -385,6 +443,72 @@ int mrt_debug_denoise_step(const float* image, const float* guide_n, const float
   return denoise_run(image, guide_n, guide_p, out, scratch, W, H, params, 1u, step_log2, path, stream);
 }
 
+// ---- variance-guided denoising (include/mrt.h) ------------------------------
+int mrt_svgf_params_default(mrt_svgf_params* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_svgf_params_default: null params");
+  out->iterations = 5;
+  out->sigma_luminance = 4.0f;
+  out->sigma_plane = 0.01f;
+  out->normal_log2_power = 6;
+  out->min_frames = 4;
+  return MRT_OK;
+}
+
+int mrt_svgf_params_check(const mrt_svgf_params* p) {
+  if (!p) return fail(MRT_ERR_INVALID, "svgf params: null");
+  if (p->iterations > 8) return fail(MRT_ERR_INVALID, "svgf params: iterations must be at most 8");
+  if (!std::isfinite(p->sigma_luminance) || !(p->sigma_luminance > 0.0f))
+    return fail(MRT_ERR_INVALID, "svgf params: sigma_luminance must be finite and positive");
+  if (!std::isfinite(p->sigma_plane) || !(p->sigma_plane > 0.0f))
+    return fail(MRT_ERR_INVALID, "svgf params: sigma_plane must be finite and positive");
+  if (p->normal_log2_power > 8) return fail(MRT_ERR_INVALID, "svgf params: normal_log2_power must be at most 8");
+  if (p->min_frames < 2) return fail(MRT_ERR_INVALID, "svgf params: min_frames must be at least 2");
+  return MRT_OK;
+}
+
+int mrt_variance(const float* moments, const float* guide_n, const float* guide_p, float* variance, uint32_t W,
+                 uint32_t H, const mrt_svgf_params* params, void* stream) {
+  if (!moments || !guide_n || !guide_p || !variance || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_variance: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  for (const float* in : {moments, guide_n, guide_p}) {
+    const char* p = (const char*)in;
+    const char* q = (const char*)variance;
+    if (p < q + bytes / 4 && q < p + bytes)
+      return fail(MRT_ERR_INVALID, "mrt_variance: variance must not overlap an input");
+  }
+  const int rc = mrt_svgf_params_check(params);
+  if (rc) return rc;
+  mrt::VarianceArgs a{};
+  a.moments = reinterpret_cast<const float4*>(moments);
+  a.guide_n = reinterpret_cast<const float4*>(guide_n);
+  a.guide_p = reinterpret_cast<const float4*>(guide_p);
+  a.variance = variance;
+  a.width = W;
+  a.height = H;
+  a.sigma_plane = params->sigma_plane;
+  a.normal_log2_power = params->normal_log2_power;
+  a.min_frames = (float)params->min_frames;
+  HIP_TRY(mrt::launch_variance(a, (hipStream_t)stream));
+  return MRT_OK;
+}
+
+int mrt_denoise_variance(const float* image, const float* variance, const float* guide_n, const float* guide_p,
+                         float* out, float* scratch, float* variance_out, uint32_t W, uint32_t H,
+                         const mrt_svgf_params* params, void* stream) {
+  if (!scratch) return fail(MRT_ERR_INVALID, "mrt_denoise_variance: bad argument");
+  return svgf_run(image, variance, guide_n, guide_p, out, scratch, variance_out, W, H, params,
+                  params ? params->iterations : 0u, 0u, g_denoise_path.load(), true, stream);
+}
+
+int mrt_debug_denoise_variance_step(const float* image, const float* variance, const float* guide_n,
+                                    const float* guide_p, float* out, uint32_t W, uint32_t H,
+                                    const mrt_svgf_params* params, uint32_t step_log2, uint32_t path, void* stream) {
+  if (step_log2 > 14 || path > mrt::kAtrousStaged)
+    return fail(MRT_ERR_INVALID, "mrt_debug_denoise_variance_step: step at most 2^14, path 0, 1 or 2");
+  return svgf_run(image, variance, guide_n, guide_p, out, nullptr, nullptr, W, H, params, 1u, step_log2, path, false, stream);
+}
+
 // ---- temporal history (include/mrt.h) --------------------------------------
 int mrt_reproject_params_default(mrt_reproject_params* out) {
   if (!out) return fail(MRT_ERR_INVALID, "mrt_reproject_params_default: null params");
@@ -499,6 +623,14 @@ int mrt_accumulate(const mrt_scene* scene, uint32_t W, uint32_t H, uint32_t fram
   if (!scene || !rays || !image || W == 0 || H == 0) return fail(MRT_ERR_INVALID, "mrt_accumulate: bad argument");
   HIP_TRY(MRT_BUILD_CALL(flags, launch_accumulate(W, H, frame_index, (const mrt::RefRay*)rays, image,
                                                   !(flags & MRT_FLAG_NO_ACCUMULATE), (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+int mrt_moments(const mrt_scene* scene, uint32_t W, uint32_t H, uint32_t frame_index, const void* rays,
+                float* moments, uint32_t flags, void* stream) {
+  if (!scene || !rays || !moments || W == 0 || H == 0) return fail(MRT_ERR_INVALID, "mrt_moments: bad argument");
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_moments(W, H, frame_index, (const mrt::RefRay*)rays, moments,
+                                               (hipStream_t)stream)));
   return MRT_OK;
 }
 

@@ -41,6 +41,7 @@ FLAG_PROFILE = 2
 FLAG_STATIC_NOISE = 4       # ANIMATE_NOISE 0
 FLAG_NO_ACCUMULATE = 8      # ACCUMULATE_IMAGE false
 FLAG_DEBUG_MATERIAL = 16    # DEBUG_MATERIAL 1
+FLAG_MOMENTS = 32           # luminance moments accumulated beside the image (variance-guided denoising)
 COMM_ID_BYTES = 128
 EXCHANGE_GATHER, EXCHANGE_REDUCE, EXCHANGE_OVERLAP = 1, 2, 0x100
 DEFAULT_SEED = 0x6D6574616C2D7274  # "metal-rt"
@@ -217,6 +218,27 @@ class ReprojectParams(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SvgfParams(ctypes.Structure):
+    """mrt_svgf_params (include/mrt.h): the variance estimate's and the
+    variance-guided filter's parameters."""
+    _fields_ = [
+        ("iterations", ctypes.c_uint32), ("sigma_luminance", ctypes.c_float), ("sigma_plane", ctypes.c_float),
+        ("normal_log2_power", ctypes.c_uint32), ("min_frames", ctypes.c_uint32),
+    ]
+
+    @classmethod
+    def default(cls) -> "SvgfParams":
+        p = cls()
+        _check(lib().mrt_svgf_params_default(ctypes.byref(p)), "mrt_svgf_params_default")
+        return p
+
+    def check(self) -> None:
+        _check(lib().mrt_svgf_params_check(ctypes.byref(self)), "mrt_svgf_params_check")
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 EXPORTED = [
     "mrt_scene_create", "mrt_scene_info_get", "mrt_scene_export", "mrt_scene_destroy", "mrt_scene_check_bvh",
     "mrt_raygen", "mrt_intersect", "mrt_shade", "mrt_resolve_shadow", "mrt_accumulate",
@@ -242,6 +264,9 @@ EXPORTED = [
     "mrt_reproject_params_default", "mrt_reproject_params_check", "mrt_temporal_resolve", "mrt_reproject",
     "mrt_renderer_move_camera", "mrt_renderer_resolve", "mrt_renderer_read_resolved", "mrt_renderer_save_resolved",
     "mrt_renderer_denoise_resolved",
+    "mrt_moments", "mrt_svgf_params_default", "mrt_svgf_params_check", "mrt_variance", "mrt_denoise_variance",
+    "mrt_renderer_read_moments", "mrt_renderer_moments", "mrt_renderer_denoise_variance",
+    "mrt_renderer_read_variance", "mrt_debug_denoise_variance_step",
 ]
 
 _lib = None
@@ -354,6 +379,16 @@ def lib() -> ctypes.CDLL:
         "mrt_renderer_read_resolved": [vp, vp, ctypes.c_size_t],
         "mrt_renderer_save_resolved": [vp, ctypes.c_char_p],
         "mrt_renderer_denoise_resolved": [vp, ctypes.POINTER(DenoiseParams)],
+        "mrt_moments": [vp, u32, u32, u32, vp, vp, u32, vp],
+        "mrt_svgf_params_default": [ctypes.POINTER(SvgfParams)],
+        "mrt_svgf_params_check": [ctypes.POINTER(SvgfParams)],
+        "mrt_variance": [vp, vp, vp, vp, u32, u32, ctypes.POINTER(SvgfParams), vp],
+        "mrt_denoise_variance": [vp, vp, vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(SvgfParams), vp],
+        "mrt_renderer_read_moments": [vp, vp, ctypes.c_size_t],
+        "mrt_renderer_moments": [vp, ctypes.POINTER(vp)],
+        "mrt_renderer_denoise_variance": [vp, ctypes.POINTER(SvgfParams)],
+        "mrt_renderer_read_variance": [vp, vp, ctypes.c_size_t],
+        "mrt_debug_denoise_variance_step": [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(SvgfParams), u32, u32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -499,15 +534,17 @@ class Renderer:
     def __init__(self, scene: Scene, width: int, height: int, max_path_length: int = 8, *,
                  seed: int = DEFAULT_SEED, shard_rank: int = 0, shard_count: int = 1, precise: bool = False,
                  profile: bool = False, stream: int | None = None, image_ptr: int | None = None,
-                 animate_noise: bool = True, accumulate_image: bool = True, debug_material: bool = False):
+                 animate_noise: bool = True, accumulate_image: bool = True, debug_material: bool = False,
+                 moments: bool = False):
         """animate_noise / accumulate_image / debug_material: the reference's
         ANIMATE_NOISE, ACCUMULATE_IMAGE and DEBUG_MATERIAL switches (defaults =
-        the reference's defaults)."""
+        the reference's defaults).  moments: accumulate the luminance moments
+        beside the image (FLAG_MOMENTS), for denoise_variance."""
         self._h = None
         self.scene = scene  # keep alive
         flags = ((FLAG_PRECISE if precise else 0) | (FLAG_PROFILE if profile else 0) |
                  (0 if animate_noise else FLAG_STATIC_NOISE) | (0 if accumulate_image else FLAG_NO_ACCUMULATE) |
-                 (FLAG_DEBUG_MATERIAL if debug_material else 0))
+                 (FLAG_DEBUG_MATERIAL if debug_material else 0) | (FLAG_MOMENTS if moments else 0))
         d = RendererDesc(scene.handle, width, height, max_path_length, seed, shard_rank, shard_count, flags,
                          stream, image_ptr)
         h = ctypes.c_void_p()
@@ -627,6 +664,35 @@ class Renderer:
         denoised buffer; params None = DenoiseParams.default(max(frames, 1))."""
         _check(lib().mrt_renderer_denoise_resolved(self._h, ctypes.byref(params) if params is not None else None),
                "mrt_renderer_denoise_resolved")
+
+    # ---- variance-guided denoising (include/mrt.h: mrt_renderer_denoise_variance) ----
+    def read_moments(self):
+        """[H, W, 4] float32 moments image (mean l, mean l*l, 0, 1), row 0 = bottom."""
+        import numpy as np
+        img = np.zeros((self.height, self.width, 4), np.float32)
+        _check(lib().mrt_renderer_read_moments(self._h, ctypes.c_void_p(img.ctypes.data), img.size),
+               "mrt_renderer_read_moments")
+        return img
+
+    def moments_ptr(self) -> int:
+        p = ctypes.c_void_p()
+        _check(lib().mrt_renderer_moments(self._h, ctypes.byref(p)), "mrt_renderer_moments")
+        return p.value
+
+    def denoise_variance(self, params: "SvgfParams | None" = None) -> None:
+        """resolve(), the variance estimate from the resolved moments, then the
+        variance-guided filter of the resolved buffer into the denoised buffer
+        (no host wait); params None = SvgfParams.default()."""
+        _check(lib().mrt_renderer_denoise_variance(self._h, ctypes.byref(params) if params is not None else None),
+               "mrt_renderer_denoise_variance")
+
+    def read_variance(self):
+        """[H, W] float32: the variance plane the last denoise_variance fed to the filter."""
+        import numpy as np
+        v = np.zeros((self.height, self.width), np.float32)
+        _check(lib().mrt_renderer_read_variance(self._h, ctypes.c_void_p(v.ctypes.data), v.size),
+               "mrt_renderer_read_variance")
+        return v
 
     # ---- multi-GPU exchange (include/mrt.h: mrt_renderer_exchange) ----
     def exchange(self, comm: "Comm", mode: int = EXCHANGE_GATHER) -> None:
@@ -757,6 +823,45 @@ def accumulate(scene: Scene, width, height, frame_index, rays_ptr, image_ptr, pr
     flags = _flags(precise) | (0 if accumulate_image else FLAG_NO_ACCUMULATE)
     _check(lib().mrt_accumulate(scene.handle, width, height, frame_index, rays_ptr, image_ptr, flags,
                                 stream), "mrt_accumulate")
+    if sync:
+        synchronize(stream)
+
+
+def moments(scene: Scene, width, height, frame_index, rays_ptr, moments_ptr, precise=True, stream=None, sync=True):
+    """accumulate's counterpart for the luminance moments (mrt_moments)."""
+    _check(lib().mrt_moments(scene.handle, width, height, frame_index, rays_ptr, moments_ptr, _flags(precise), stream),
+           "mrt_moments")
+    if sync:
+        synchronize(stream)
+
+
+def variance(moments_ptr: int, n_ptr: int, p_ptr: int, variance_ptr: int, width: int, height: int,
+             params: "SvgfParams | None", stream=None, sync=True) -> None:
+    """The per-pixel variance estimate from counted moments (mrt_variance): W*H floats."""
+    _check(lib().mrt_variance(moments_ptr, n_ptr, p_ptr, variance_ptr, width, height,
+                              ctypes.byref(params) if params is not None else None, stream), "mrt_variance")
+    if sync:
+        synchronize(stream)
+
+
+def denoise_variance(image_ptr: int, variance_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, scratch_ptr: int,
+                     variance_out_ptr: "int | None", width: int, height: int, params: "SvgfParams | None", stream=None,
+                     sync=True) -> None:
+    """The variance-guided A-Trous filter (mrt_denoise_variance) on device buffers."""
+    _check(lib().mrt_denoise_variance(image_ptr, variance_ptr, n_ptr, p_ptr, out_ptr, scratch_ptr, variance_out_ptr,
+                                      width, height, ctypes.byref(params) if params is not None else None, stream),
+           "mrt_denoise_variance")
+    if sync:
+        synchronize(stream)
+
+
+def debug_denoise_variance_step(image_ptr: int, variance_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, width: int,
+                                height: int, params: SvgfParams, step_log2: int, path: int, stream=None,
+                                sync=True) -> None:
+    """Measurement entry: one iteration at step 2^step_log2 with implementation `path`."""
+    _check(lib().mrt_debug_denoise_variance_step(image_ptr, variance_ptr, n_ptr, p_ptr, out_ptr, width, height,
+                                                 ctypes.byref(params), step_log2, path, stream),
+           "mrt_debug_denoise_variance_step")
     if sync:
         synchronize(stream)
 
