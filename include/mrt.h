@@ -427,6 +427,53 @@ int mrt_denoise_variance(const float* image, const float* variance, const float*
                          float* out, float* scratch, float* variance_out /* may be NULL */, uint32_t width,
                          uint32_t height, const mrt_svgf_params* params, void* stream);
 
+/* ---- adaptive sampling ------------------------------------------------------
+ * Spend further samples where the variance plane says the error is: a priority
+ * per 64x64 tile, the tiles of highest priority, and draws of an arbitrary
+ * list of tiles into counted images beside the accumulation image
+ * (mrt_renderer_refine below).  Not in the reference.  The
+ * tile is the unit: tile t of a W x H frame, row-major over
+ * ceil(W/64) x ceil(H/64) tiles, covers the pixels x in [64 (t % tiles_x), +64),
+ * y in [64 (t / tiles_x), +64) that are inside the image.  Device pointers
+ * throughout; flags: MRT_FLAG_PRECISE. */
+typedef struct mrt_adaptive_params {
+  float luminance_floor;   /* > 0: eps of the priority */
+} mrt_adaptive_params;
+/* Host only.  luminance_floor = 0.01. */
+int mrt_adaptive_params_default(mrt_adaptive_params* out);
+/* Host only.  MRT_ERR_INVALID (with a message) for a luminance_floor that is
+ * not finite or not positive. */
+int mrt_adaptive_params_check(const mrt_adaptive_params* p);
+/* Merge two counted images (temporal history above) of W*H float4.  Per pixel,
+ * with ha = a.w and hb = b.w:
+ *   hb == 0, or a component of b.rgb not finite:            out = a, bitwise
+ *   otherwise ha == 0, or a component of a.rgb not finite:  out = b, bitwise
+ *   otherwise  out.rgb = (ha a.rgb + hb b.rgb) / (ha + hb), out.w = ha + hb,
+ *   evaluated as written (the precise build rounds after every operation; the
+ *   fast build may contract and divides through a reciprocal).
+ * out == a (the same pointer) is allowed; any other overlap of out with an
+ * input is MRT_ERR_INVALID. */
+int mrt_counted_merge(const float* a, const float* b, float* out, uint32_t width, uint32_t height, uint32_t flags,
+                      void* stream);
+/* priority[t] (one float per tile) = the sum of v_p / (l_p l_p + eps^2) over the
+ * tile's pixels p that are inside the image, filterable (word_p < 0x80000000 in
+ * guide_n) and have a finite image[p].rgb; l_p = lum(image[p].rgb), v_p =
+ * variance[p] (W*H floats, as mrt_variance writes it), eps =
+ * params->luminance_floor.  A tile without such a pixel has priority 0.  The
+ * summation order is not defined.  v is the variance of the pixel's MEAN and a
+ * frame of a tile costs the same everywhere, so the sum is the relative squared
+ * error that a further sample of the tile buys.  The inputs are only read.
+ * params == NULL, or `priority` overlapping an input, is MRT_ERR_INVALID. */
+int mrt_tile_priority(const float* image, const float* variance, const float* guide_n, float* priority,
+                      uint32_t width, uint32_t height, const mrt_adaptive_params* params, uint32_t flags,
+                      void* stream);
+/* list[r] (uint32, r < count) = the tile of rank r under (priority descending,
+ * tile index ascending) among `tiles` priorities; a priority that is not finite
+ * or is negative counts as 0.  Exact given the priorities, and the same in both
+ * builds.  count == 0, count > tiles, tiles > 16384 (an 8192 x 8192 frame), or
+ * list overlapping priority, is MRT_ERR_INVALID. */
+int mrt_tile_select(const float* priority, uint32_t tiles, uint32_t count, uint32_t* list, void* stream);
+
 /* ---- renderer (B-1) ------------------------------------------------------ */
 typedef struct mrt_renderer_desc {
   const mrt_scene* scene;          /* not owned; must outlive the renderer */
@@ -614,9 +661,76 @@ int mrt_renderer_moments(mrt_renderer* r, float** device_moments);
  * has been accumulated and there is no valid history. */
 int mrt_renderer_denoise_variance(mrt_renderer* r, const mrt_svgf_params* params);
 /* The variance plane (W*H floats) the last mrt_renderer_denoise_variance fed to
- * the filter; synchronises.  MRT_ERR_STATE before one has run at the current
- * size.  The hook for adaptive sampling. */
+ * the filter (or the last mrt_renderer_refine chose its tiles by, whichever ran
+ * later); synchronises.  MRT_ERR_STATE before one has run at the current size. */
 int mrt_renderer_read_variance(mrt_renderer* r, float* plane, size_t count);
+/* Adaptive sampling on a renderer (the section of that name above): extra
+ * frames of chosen tiles, accumulated into two counted images the renderer
+ * owns beside its image — E, the extra image (r, g, b, n), and EM, the extra
+ * moments (mean l, mean l*l, 0, n), n = the extra samples behind the pixel.
+ * The accumulation image, the moments image and mrt_stats.frame_index, .paths
+ * and .draws are never touched by these calls: after any of them the image is
+ * bitwise that of a renderer that never made them, and stays so through later
+ * draws.  Needs MRT_FLAG_MOMENTS: MRT_ERR_STATE without it (so on every
+ * sharded renderer), with MRT_FLAG_STATIC_NOISE, and on a renderer forced to
+ * the per-bounce kernel (a diagnostic setting), which has no tile-list
+ * instantiation.  E, EM, the list and the priorities (32 B per pixel and 8 B
+ * per tile) are allocated at the first call and re-made by resize: a renderer
+ * that never calls them allocates nothing.  Everything is enqueued without a
+ * host wait; the render streams wait for the list through an event.
+ *
+ * Noise: extra samples read a second noise schedule, seeded
+ * desc.seed ^ MRT_REFINE_SEED_XOR, at an extra-frame counter e of their own
+ * that advances by `frames` per call whatever the list and is never reset, so
+ * no draw and no other refine ever repeats their paths.  A listed tile's extra
+ * frame is exactly the frame e of a renderer created with that seed: for each
+ * extra frame in order, with c its radiance at pixel p and n = (uint32_t)E[p].w,
+ *   E[p].rgb = accumulate(E[p].rgb, c, n), E[p].w = n + 1    (n == 0 overwrites)
+ * and EM[p] the same over (l, l*l, 0), l = lum(c).
+ *
+ * While E holds samples every resolve merges them: resolved =
+ * mrt_counted_merge(resolve(image, frames, history), E) and likewise the
+ * resolved moments with EM — in mrt_renderer_resolve, _denoise_resolved and
+ * _denoise_variance (whose mrt_variance therefore sees the n they add: a refined
+ * tile's priority falls by itself) and in mrt_renderer_move_camera, which
+ * carries the merged images into the history and then clears E and EM.
+ * mrt_renderer_reset, _set_camera and _resize clear them as well.
+ *
+ * The diagnostic counters of mrt_stats (active_ray_bounces, kernel_launches,
+ * span_ms, spans, kernel_ms, timed_launches, last_draw_ms, mpaths_per_s,
+ * draws_overlapped, inflight_waits) include the refine launches. */
+#define MRT_REFINE_SEED_XOR 0x9E3779B97F4A7C15ull
+/* `frames` (>= 1) extra frames of the `count` tiles in the host array `tiles`:
+ * distinct, each < tiles_x * tiles_y, 1 <= count.  A bad list or frames == 0 is
+ * MRT_ERR_INVALID and changes nothing.  The list is copied before the call
+ * returns. */
+int mrt_renderer_draw_tiles(mrt_renderer* r, const uint32_t* tiles, uint32_t count, uint32_t frames);
+/* One adaptive pass, in stream order: the guide planes if they are not current;
+ * the merged resolved image and moments as above; mrt_variance with
+ * mrt_svgf_params_default; mrt_tile_priority (params NULL =
+ * mrt_adaptive_params_default); mrt_tile_select of tile_count tiles into a
+ * device list; `frames` extra frames of those tiles as mrt_renderer_draw_tiles
+ * draws them.  MRT_ERR_STATE when no frame has been accumulated and there is no
+ * valid history; frames == 0, tile_count == 0 or tile_count above the frame's
+ * tile count is MRT_ERR_INVALID. */
+int mrt_renderer_refine(mrt_renderer* r, uint32_t frames, uint32_t tile_count, const mrt_adaptive_params* params);
+/* E and EM (W*H*4 floats), the priorities of the last refine (one float per
+ * tile) and the list of the last refine or draw_tiles (*count entries, at most
+ * `capacity`).  All synchronise.  MRT_ERR_STATE before the first refine or
+ * draw_tiles at the current size (the priorities: before the first refine). */
+int mrt_renderer_read_extra(mrt_renderer* r, float* rgba, size_t count);
+int mrt_renderer_read_extra_moments(mrt_renderer* r, float* rgba, size_t count);
+int mrt_renderer_read_tile_priority(mrt_renderer* r, float* priority, size_t count);
+int mrt_renderer_read_tile_list(mrt_renderer* r, uint32_t* tiles, size_t capacity, uint32_t* count);
+typedef struct mrt_refine_stats {   /* cumulative since create; never reset */
+  uint64_t passes;         /* refine and draw_tiles calls that enqueued frames */
+  uint64_t extra_frames;   /* the extra-frame counter e */
+  uint64_t tile_frames;    /* sum over those calls of tiles x frames */
+  uint64_t paths;          /* pixel paths traced by them (pixels of the listed tiles inside the image x frames);
+                              a refine's list is chosen on the device, so its pixels are counted when its
+                              list is next read back: mrt_renderer_refine_stats synchronises */
+} mrt_refine_stats;
+int mrt_renderer_refine_stats(mrt_renderer* r, mrt_refine_stats* stats);
 int mrt_renderer_stats(const mrt_renderer* r, mrt_stats* stats);
 int mrt_renderer_destroy(mrt_renderer* r);
 

@@ -31,6 +31,15 @@
  *                   [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]
  *                   [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]
  *                   [--orbit-steps K --orbit-degrees D]
+ *                   [--refine-passes P --refine-frames F --refine-tiles K]
+ * --refine-passes P (single rank only; --refine-frames F, default 1, and
+ * --refine-tiles K, default a quarter of the frame's 64x64 tiles, imply it with
+ * P = 1): adaptive sampling.  The renderer accumulates luminance moments, and
+ * after the draws (with --orbit-steps after the last move's draw) P times
+ * mrt_renderer_refine(F, K): F extra frames of the K tiles of highest
+ * priority.  --out then receives an image that holds the extra samples: that of
+ * --denoise-variance, or of --denoise (mrt_renderer_denoise_resolved), or else
+ * the resolved image.
  * --orbit-steps K --orbit-degrees D (single rank only): after the first --spp
  * frames, K times: the eye turns about the vertical axis through the target
  * by D degrees (step k stands at k D from the first eye; the axis is the
@@ -89,6 +98,9 @@ typedef struct {
   uint32_t svgf_iterations;
   float svgf_sigma_luminance;
   /* orbit with temporal history (mrt_renderer_move_camera) */
+  /* adaptive sampling (mrt_renderer_refine) */
+  uint32_t refine_passes, refine_frames, refine_tiles;
+  int refine_set;
   uint32_t orbit_steps;
   int orbit_degrees_set;
   float orbit_degrees;
@@ -116,10 +128,13 @@ static void usage(void) {
           "                  [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]\n"
           "                  [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]\n"
           "                  [--orbit-steps K --orbit-degrees D]\n"
+          "                  [--refine-passes P --refine-frames F --refine-tiles K]\n"
           "  --orbit-steps K --orbit-degrees D (one rank): after the first --spp frames, K times: turn the eye by D\n"
           "  degrees about the world's vertical (y) axis through the target, whatever --up says, move the camera\n"
           "  keeping the accumulated history, draw --spp frames; --out gets the resolved image.  --orbit-degrees\n"
-          "  alone is an error.\n");
+          "  alone is an error.\n"
+          "  --refine-passes P --refine-frames F --refine-tiles K (one rank): after the draws, P times F extra frames\n"
+          "  of the K 64x64 tiles whose variance says they need them most; --out gets an image that holds them.\n");
 }
 
 /* --scene cornellbox -> <dir of this executable>/../scenes/cornellbox.obj */
@@ -170,6 +185,9 @@ static int parse(int argc, char** argv, options* o) {
     else if (VAL("--denoise-sigma-color")) { o->denoise_sigma_color = strtof(v, NULL); o->denoise = o->denoise_sigma_set = 1; }
     else if (VAL("--orbit-steps")) o->orbit_steps = (uint32_t)strtoul(v, NULL, 0);
     else if (VAL("--orbit-degrees")) { o->orbit_degrees = strtof(v, NULL); o->orbit_degrees_set = 1; }
+    else if (VAL("--refine-passes")) { o->refine_passes = (uint32_t)strtoul(v, NULL, 0); o->refine_set = 1; }
+    else if (VAL("--refine-frames")) { o->refine_frames = (uint32_t)strtoul(v, NULL, 0); o->refine_set = 1; }
+    else if (VAL("--refine-tiles")) { o->refine_tiles = (uint32_t)strtoul(v, NULL, 0); o->refine_set = 1; }
     else if (VAL("--svgf-iterations")) { o->svgf_iterations = (uint32_t)strtoul(v, NULL, 0); o->denoise_variance = o->svgf_iterations_set = 1; }
     else if (VAL("--svgf-sigma-luminance")) { o->svgf_sigma_luminance = strtof(v, NULL); o->denoise_variance = o->svgf_sigma_set = 1; }
     else if (strcmp(a, "--denoise") == 0) o->denoise = 1;
@@ -204,7 +222,19 @@ static int parse(int argc, char** argv, options* o) {
     fprintf(stderr, "mrt_render: --denoise-variance is single rank only (a sharded renderer keeps no moments)\n");
     return -1;
   }
-  if (o->denoise_variance) o->flags |= MRT_FLAG_MOMENTS;
+  if (o->refine_set) {
+    if (o->gpus > 1) {
+      fprintf(stderr, "mrt_render: --refine-passes is single rank only (a sharded renderer keeps no moments)\n");
+      return -1;
+    }
+    if (!o->refine_passes) o->refine_passes = 1;
+    if (!o->refine_frames) o->refine_frames = 1;
+    if (!o->refine_tiles) {
+      const uint32_t tiles = ((o->width + 63) / 64) * ((o->height + 63) / 64);
+      o->refine_tiles = tiles / 4 ? tiles / 4 : 1;
+    }
+  }
+  if (o->denoise_variance || o->refine_set) o->flags |= MRT_FLAG_MOMENTS;
   return 0;
 }
 
@@ -320,6 +350,8 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
     if (mrt_renderer_move_camera(r, &cam, NULL)) return die("mrt_renderer_move_camera");
     if (mrt_renderer_draw_n(r, o->spp)) return die("mrt_renderer_draw_n");
   }
+  for (uint32_t k = 0; k < o->refine_passes; ++k)   /* (single rank) nor does this */
+    if (mrt_renderer_refine(r, o->refine_frames, o->refine_tiles, NULL)) return die("mrt_renderer_refine");
   if (rccl) {
     if (mrt_renderer_exchange(r, comm, MRT_EXCHANGE_GATHER)) return die("mrt_renderer_exchange");
   } else if (N > 1) {
@@ -360,13 +392,13 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
       if (mrt_denoise_params_default(st.frame_index, &dp)) return die("mrt_denoise_params_default");
       if (o->denoise_iterations_set) dp.iterations = o->denoise_iterations;
       if (o->denoise_sigma_set) dp.sigma_color = o->denoise_sigma_color;
-      if (o->orbit_steps) {
+      if (o->orbit_steps || o->refine_set) {
         if (mrt_renderer_denoise_resolved(r, &dp)) return die("mrt_renderer_denoise_resolved");
       } else if (mrt_renderer_denoise(r, &dp)) {
         return die("mrt_renderer_denoise");
       }
       if (mrt_renderer_save_denoised(r, o->out)) return die("mrt_renderer_save_denoised");
-    } else if (o->orbit_steps) {
+    } else if (o->orbit_steps || o->refine_set) {
       if (mrt_renderer_resolve(r)) return die("mrt_renderer_resolve");
       if (mrt_renderer_save_resolved(r, o->out)) return die("mrt_renderer_save_resolved");
     } else if (mrt_renderer_save_image(r, o->out)) {

@@ -250,6 +250,29 @@ __device__ __forceinline__ void slot_pixel_a(uint32_t s, const BounceArgs& a, ui
   y = ty * kTile + (blk >> 3) * 8u + (q >> 3);
 }
 
+// LIST: the kernel instantiation that renders the tiles of a.tile_list
+// (adaptive sampling, include/mrt.h): owned tile k = s >> 12 is tile
+// tile_list[k].  With LIST = false this is slot_pixel_a and the kernels are
+// the code they were before a launch could carry a list (as CAM above).
+// UNIFORM: the caller's lanes hold slots of one tile (a wave of camera rays:
+// 64 consecutive slots from a multiple of 64), so the list entry is one scalar
+// load; otherwise (a lane's own path, any tile) a load per lane of a list
+// that is at most 64 KB and stays in the CU's cache.
+template <bool LIST, bool UNIFORM = false>
+__device__ __forceinline__ void slot_pixel_l(uint32_t s, const BounceArgs& a, uint32_t& x, uint32_t& y) {
+  if constexpr (!LIST) {
+    slot_pixel_a(s, a, x, y);
+  } else {
+    const uint32_t p = s & 4095u;
+    const uint32_t k = UNIFORM ? __builtin_amdgcn_readfirstlane(s >> 12) : s >> 12;
+    const uint32_t t = a.tile_list[k];
+    const uint32_t ty = mdiv(t, a.div_tiles, a.tiles_x), tx = t - ty * a.tiles_x;
+    const uint32_t blk = p >> 6, q = p & 63u;
+    x = tx * kTile + (blk & 7u) * 8u + (q & 7u);
+    y = ty * kTile + (blk >> 3) * 8u + (q >> 3);
+  }
+}
+
 // noise table of frame (batch frame fj) - back, back in {0, 1, 2}
 __device__ __forceinline__ const float4* noise_table(const BounceArgs& a, uint32_t fj, uint32_t back) {
   return a.noise_window + (a.noise_offset + fj - back) * (kNoiseDim * kNoiseDim);

@@ -119,8 +119,29 @@ struct DrawRecord {
   // folding accumulate (which zeroes them behind the draw); a draw that
   // returned early after its first launch leaves them dirty
   bool clean = false;
+  // what the draw rendered per frame: the renderer's owned pixels, or (a refine
+  // draw: listed > 0) the tiles of list_host — the pinned staging a draw_tiles
+  // list is uploaded from and a refine's device-chosen list is copied back to,
+  // behind the draw; its pixels are counted when the draw is read back
+  uint64_t pixels = 0;
+  uint32_t listed = 0;
+  uint32_t* list_host = nullptr;
+  size_t list_cap = 0;                      // entries
 };
 constexpr int kDrawRing = 3;
+
+// What a draw renders and where it goes (renderer.cpp draw_frames): the frames
+// [f0, f0 + n) of a noise schedule, over the renderer's owned tiles into the
+// accumulation image (mrt_renderer_draw_n) or over a tile list into the counted
+// extra images (mrt_renderer_draw_tiles / _refine)
+struct DrawSource {
+  mrt::NoiseSchedule* noise = nullptr;
+  uint64_t f0 = 0;
+  uint32_t tiles = 0;                       // listed tiles; 0 = the owned tiles
+  const uint32_t* host_list = nullptr;      // listed: to upload (null: the device list is already chosen)
+  float* image = nullptr;                   // accumulation image, or E
+  float* moments = nullptr;                 // moments image (may be null), or EM
+};
 
 // One in-flight frame: its queues, segment counts, per-pixel path radiance and
 // the stream its render launches run on.  Batches b and b+1 run on different
@@ -337,6 +358,18 @@ struct mrt_renderer {
   // history's validity is history_valid.
   mrt::host::DevBuf moments, moments_prev, moments_history, moments_resolved, variance;
   bool variance_current = false;   // a denoise_variance has run at the current size
+  // adaptive sampling (mrt_renderer_refine / _draw_tiles): everything is made at
+  // the first call and re-made by resize.  E and EM are counted images beside
+  // the image and the moments; the second noise schedule (seed ^
+  // MRT_REFINE_SEED_XOR) and the extra-frame counter are never reset.
+  mrt::host::DevBuf extra, extra_moments, tile_list, tile_priority;
+  std::unique_ptr<mrt::NoiseSchedule> refine_noise;
+  hipEvent_t list_ready = nullptr; // on the main stream: the list's upload or selection (render streams wait on it)
+  bool extras_current = false;     // E / EM exist at the current size (zero unless extras_valid)
+  bool extras_valid = false;       // E holds samples: resolves merge it
+  bool priority_current = false;   // a refine has run at the current size
+  uint32_t list_count = 0;         // entries of tile_list the last refine / draw_tiles drew
+  mrt_refine_stats refine_stats{};
   struct DisplaySlot {          // mrt_renderer_display_enqueue / _map: pinned copies of the blit
     float* host = nullptr;
     size_t floats = 0;

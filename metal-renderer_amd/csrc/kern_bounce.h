@@ -81,7 +81,8 @@ __device__ __forceinline__ void wait_vmem() {
 // partial-hit plane (a.out_q.plane[0], which the stream kernel has no other
 // use for), at the level's first slot of this pass + its rank among the
 // recycled lanes.  `recycled` returns their count; they are not survivors.
-template <int STACK, int MODE, bool WAVEQ = false, bool CAM = false>
+// LIST: the launch renders the tiles of a.tile_list (dev_shade.h slot_pixel_l).
+template <int STACK, int MODE, bool WAVEQ = false, bool CAM = false, bool LIST = false>
 __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const LdsCtx& cx, const BounceArgs& a,
                                                uint32_t bounce, bool active, uint32_t idx, uint32_t slot,
                                                const RayQueue& in_q, const RayQueue& out_q, uint32_t* cursor,
@@ -103,7 +104,7 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
       // straddle frames, so fj is wave-uniform)
       const uint32_t fj = a.batch == 1u ? 0u : __builtin_amdgcn_readfirstlane(mdiv(idx, a.div_slots, a.num_slots));
       uint32_t x, y;
-      slot_pixel_a(idx - fj * a.num_slots, a, x, y);
+      slot_pixel_l<LIST, true>(idx - fj * a.num_slots, a, x, y);
       active = (x < a.width) && (y < a.height);
       if (active) {
         tag = idx;
@@ -234,7 +235,7 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
   if (hit_ok) {
     const uint32_t fj = a.batch == 1u ? 0u : mdiv(gslot, a.div_slots, a.num_slots);   // frame in batch
     uint32_t x, y;
-    slot_pixel_a(gslot - fj * a.num_slots, a, x, y);
+    slot_pixel_l<LIST>(gslot - fj * a.num_slots, a, x, y);
     const uint32_t back = (bounce % 3u) == 0 ? 0u : ((bounce % 3u) == 1 ? 2u : 1u);   // uniform
     const float4 ns = noise_table(a, fj, back)[shade_noise_cell(x, y, bounce, a.frame_index + fj)];
     if (a.debug & 2u) {   // ablation: no shading, reflect back along the ray

@@ -113,7 +113,8 @@ __device__ __forceinline__ void begin_nearest(const DeviceScene& sc, Hit& h, Tra
   h.t = __builtin_inff(); h.u = h.v = 0.0f; h.prim = 0xFFFFFFFFu; h.found = false;
 }
 
-template <int STACK, int MODE, bool CAM = false>
+// LIST: the launch renders the tiles of a.tile_list (dev_shade.h slot_pixel_l)
+template <int STACK, int MODE, bool CAM = false, bool LIST = false>
 __global__ __launch_bounds__(kBlock, MRT_PATH_WAVES) void path_kernel(DeviceScene sc, BounceArgs a) {
   __shared__ uint32_t s_closed;
   __shared__ uint32_t s_count[64];   // rays alive at the start of bounce b + 1 (stats)
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(kBlock, MRT_PATH_WAVES) void path_kernel(DeviceScen
           sl = idx - fj * a.num_slots;
         }
         uint32_t x, y;
-        slot_pixel_a(sl, a, x, y);
+        slot_pixel_l<LIST>(sl, a, x, y);
         if ((x < a.width) && (y < a.height)) {
           const float4 ns = noise_table(a, fj, 0u)[(x % kNoiseDim) + (y % kNoiseDim) * kNoiseDim];
           camera_ray<CAM>(x, y, a.width, a.height, ns, noise_table(a, fj, 0u), a.camera, ro, rd);
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(kBlock, MRT_PATH_WAVES) void path_kernel(DeviceScen
       if (hit_ok) {
         const uint32_t fj = a.batch == 1u ? 0u : mdiv(gslot, a.div_slots, a.num_slots);
         uint32_t x, y;
-        slot_pixel_a(gslot - fj * a.num_slots, a, x, y);
+        slot_pixel_l<LIST>(gslot - fj * a.num_slots, a, x, y);
         const uint32_t back = (bounce % 3u) == 0 ? 0u : ((bounce % 3u) == 1 ? 2u : 1u);
         const float4 ns = noise_table(a, fj, back)[shade_noise_cell(x, y, bounce, a.frame_index + fj)];
         shade_hit<MODE>(sc, cx, h, s, ns, bounce, L, !last, sh, (a.flags & kShadeDebugMaterial) != 0);

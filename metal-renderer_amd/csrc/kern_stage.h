@@ -38,8 +38,9 @@ __device__ __forceinline__ void accumulate_moments(float& m1, float& m2, V3 c, u
     m2 = l2;
   }
 }
-template <bool MOMENTS>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_vgpr(32))) void accumulate_frame_kernel(AccumArgs a) {
+// the last accumulate of a draw (a.counters set): block 0 copies the draw's
+// statistics words to the host's pinned copy and zeroes the counters
+__device__ __forceinline__ void fold_draw_counters(const AccumArgs& a) {
   if (a.counters && blockIdx.x == 0) {   // the draw's render launches have completed (stream order)
     for (uint32_t i = threadIdx.x; i < a.copy_words; i += kBlock) a.host_counters[i] = a.counters[i];
     for (uint32_t i = threadIdx.x; i < a.span_words; i += kBlock)
@@ -48,6 +49,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_vgpr(32))) void a
     for (uint32_t i = threadIdx.x; i < a.zero_words; i += kBlock) a.counters[i] = 0u;
     __threadfence_system();
   }
+}
+template <bool MOMENTS>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_num_vgpr(32))) void accumulate_frame_kernel(AccumArgs a) {
+  fold_draw_counters(a);
   for (uint32_t idx = blockIdx.x * kBlock + threadIdx.x; idx < a.num_slots; idx += gridDim.x * kBlock) {
     uint32_t x, y;
     slot_pixel(idx, a.shard_rank, a.shard_count, a.tiles_x, x, y);

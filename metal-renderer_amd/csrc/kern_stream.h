@@ -24,7 +24,7 @@ namespace mrt { namespace MRT_NS { namespace {
 // the camera rays are gone a wave runs its partial levels, deepest first.
 // No wave ever waits for another, so any grid and any residency is safe.
 // ---------------------------------------------------------------------------
-template <int STACK, int MODE, bool CAM = false>
+template <int STACK, int MODE, bool CAM = false, bool LIST = false>
 __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(DeviceScene sc, BounceArgs a) {
   // per wave (private rows): [0] rays queued per level, [1] survivors per
   // bounce (stats).  One array, so that the one row address `cnt` serves
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(Device
       LS_T1(44);
     }
     uint32_t recycled;   // lanes back on level lvl with leaves left to test: never camera rays
-    const uint32_t wrote = bounce_wave<STACK, MODE, true, CAM>(sc, cx, a, camera ? 0u : lvl, active, idx, slot,
+    const uint32_t wrote = bounce_wave<STACK, MODE, true, CAM, LIST>(sc, cx, a, camera ? 0u : lvl, active, idx, slot,
                                                                  a.in_q, a.in_q, nullptr, out, 0u, st, recycled);
     if (lvl + 1u < L && lane == 0) {
       cnt[lvl + 1u] += wrote;

@@ -149,8 +149,14 @@ struct BounceArgs {
   MagicDiv div_tiles, div_slots, div_batch;
   // null = the reference's camera, and then the kernels' instantiation
   // without a camera block is launched (kernels.hip camera_ray<CAM>);
-  // `primary` was built for this camera.  Last, so that no other argument moves.
+  // `primary` was built for this camera.  Behind everything older, so that no other argument moves.
   const CameraBlock* camera;
+  // null = the owned tiles shard_rank + k * shard_count.  Otherwise owned tile
+  // k = slot >> 12 is tile tile_list[k] (num_slots = listed tiles * 4096) and
+  // the kernels' LIST instantiation is launched (dev_shade.h slot_pixel_l):
+  // an arbitrary set of 64x64 tiles ("adaptive sampling", include/mrt.h).
+  // Behind `camera`, so that no other argument moves.
+  const uint32_t* tile_list;
 };
 
 // running-mean accumulation of one frame over the owned tiles
@@ -171,9 +177,33 @@ struct AccumArgs {
   uint32_t* host_counters;
   uint32_t copy_words, span_word, span_words, zero_words;
   // MRT_FLAG_MOMENTS: the luminance moments image (mean l, mean l^2, 0, 1), updated with the
-  // image from the one read of the radiance rows; null = none.  Last, so that no other argument moves.
+  // image from the one read of the radiance rows; null = none.  Behind everything older, so that no other
+  // argument moves.
   float4* moments;
+  // launch_accumulate_counted only (null otherwise): the tiles of the batch, as BounceArgs::tile_list;
+  // `image` and `moments` are then the COUNTED extra images E and EM and frame_index is not read
+  const uint32_t* tile_list;
 };
+
+// mrt_counted_merge: out = merge(a, b) of two counted images (include/mrt.h "adaptive sampling")
+struct MergeArgs {
+  const float4* a;
+  const float4* b;
+  float4* out;       // may be `a`
+  uint32_t count;    // W * H
+};
+
+// mrt_tile_priority: one float per 64x64 tile, row-major over tiles_x x tiles_y
+struct PriorityArgs {
+  const float4* image;
+  const float* variance;
+  const float4* guide_n;
+  float* priority;
+  uint32_t width, height, tiles_x;
+  float eps2;        // luminance_floor^2
+};
+
+constexpr uint32_t kMaxSelectTiles = 16384;   // mrt_tile_select: the tiles of an 8192 x 8192 frame
 
 constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_shade flags
 
@@ -221,6 +251,15 @@ constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_sha
   bool path_preferred(const DeviceScene& sc);                                                             \
   /* accumulateImage over the owned tiles of a batch of frames (in frame order) */                        \
   hipError_t launch_accumulate_frame(const AccumArgs& a, hipStream_t s);                                  \
+  /* the same into the counted extra images over the tiles of a.tile_list (a.num_slots = tiles * 4096):   \
+     E[p] = accumulate(E[p], c, n = E[p].w), E[p].w = n + 1, frame by frame; a.moments likewise */         \
+  hipError_t launch_accumulate_counted(const AccumArgs& a, hipStream_t s);                                \
+  hipError_t launch_counted_merge(const MergeArgs& a, hipStream_t s);                                     \
+  hipError_t launch_tile_priority(const PriorityArgs& a, uint32_t tiles, hipStream_t s);                  \
+  /* list[r] = the tile of rank r < count under (priority descending, tile ascending); exact, the same    \
+     code in both builds; tiles <= kMaxSelectTiles */                                                     \
+  hipError_t launch_tile_select(const float* priority, uint32_t tiles, uint32_t count, uint32_t* list,    \
+                                hipStream_t s);                                                           \
   /* blitFragment (Shaders.metal:33-70): tone map / sRGB / golden comparison of the RGBA32F image */     \
   hipError_t launch_display(const float4* image, const float4* reference, float4* out, uint32_t n,        \
                             uint32_t flags, float compare_scale, hipStream_t s);                          \

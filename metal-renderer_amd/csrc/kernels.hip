@@ -3,7 +3,7 @@
 // the headers it includes, by stage: dev_config.h (build selection, tunables),
 // dev_diag.h (diagnostic builds), dev_math.h, dev_lds.h, dev_traverse.h,
 // dev_sweep.h, dev_shadow.h, dev_shade.h, and the kernels kern_bounce.h,
-// kern_stream.h, kern_path.h, kern_stage.h.
+// kern_stream.h, kern_path.h, kern_stage.h, kern_adaptive.h.
 //
 // Compiled twice (see kernels.h): MRT_PRECISE=1 -> namespace mrt::precise,
 // MRT_PRECISE=0 -> mrt::fast.  Every device function restates one
@@ -18,6 +18,7 @@
 
 #include "diag_env.h"
 #include "kernels.h"
+#include "kern_adaptive.h"
 #include "kern_bounce.h"
 #include "kern_path.h"
 #include "kern_stage.h"
@@ -136,9 +137,13 @@ template <int STACK, int MODE>
 hipError_t launch_path_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
   const int stack = STACK < 0 ? -STACK : STACK;
   const DeviceScene f = fit_path_lds_nodes(sc, MODE, stack);
-  // (a moved camera: the CAM instantiation, same launch bounds and LDS)
-  if (a.camera) path_kernel<STACK, MODE, true><<<dim3(grid), dim3(kBlock), path_lds_bytes(f, MODE, stack), s>>>(f, a);
-  else path_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), path_lds_bytes(f, MODE, stack), s>>>(f, a);
+  // (a moved camera: the CAM instantiation, a tile list: the LIST one; same launch bounds and LDS)
+  const size_t lds = path_lds_bytes(f, MODE, stack);
+  if (a.tile_list) {
+    if (a.camera) path_kernel<STACK, MODE, true, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
+    else path_kernel<STACK, MODE, false, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
+  } else if (a.camera) path_kernel<STACK, MODE, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
+  else path_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
   return hipGetLastError();
 }
 
@@ -176,6 +181,7 @@ template <int STACK, int MODE>
 hipError_t launch_bounce_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
   const DeviceScene f = fit_lds_nodes(sc, MODE, STACK < 0 ? -STACK : STACK, grid);
   const size_t lds = bounce_lds_bytes(f, MODE, STACK < 0 ? -STACK : STACK, grid);
+  if (a.tile_list) return hipErrorNotSupported;   // the per-bounce kernel (MRT_DIAG builds of a renderer) has no LIST instantiation
   if (a.camera) bounce_kernel<STACK, MODE, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
   else bounce_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
   return hipGetLastError();
@@ -216,10 +222,14 @@ hipError_t dispatch(const DeviceScene& sc, const BounceArgs* a, uint32_t stack_e
 // wave-local streaming wavefront: whole-scene-in-LDS scenes, the stack in LDS
 template <int STACK>
 hipError_t launch_stream_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
-  if (a.camera)
-    stream_kernel<STACK, kAllLds, true><<<dim3(grid), dim3(kBlock), bounce_lds_bytes(sc, kAllLds, STACK, 0), s>>>(sc, a);
+  const size_t lds = bounce_lds_bytes(sc, kAllLds, STACK, 0);
+  if (a.tile_list) {   // the LIST instantiations (dev_shade.h slot_pixel_l)
+    if (a.camera) stream_kernel<STACK, kAllLds, true, true><<<dim3(grid), dim3(kBlock), lds, s>>>(sc, a);
+    else stream_kernel<STACK, kAllLds, false, true><<<dim3(grid), dim3(kBlock), lds, s>>>(sc, a);
+  } else if (a.camera)
+    stream_kernel<STACK, kAllLds, true><<<dim3(grid), dim3(kBlock), lds, s>>>(sc, a);
   else
-    stream_kernel<STACK, kAllLds><<<dim3(grid), dim3(kBlock), bounce_lds_bytes(sc, kAllLds, STACK, 0), s>>>(sc, a);
+    stream_kernel<STACK, kAllLds><<<dim3(grid), dim3(kBlock), lds, s>>>(sc, a);
   return hipGetLastError();
 }
 // the stream kernel's own persistent grid: every block slot its LDS (scene
@@ -324,6 +334,31 @@ hipError_t launch_accumulate_frame(const AccumArgs& a, hipStream_t s) {
   const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(blocks_for(a.num_slots), 4096));
   if (a.moments) accumulate_frame_kernel<true><<<dim3(blocks), dim3(kBlock), 0, s>>>(a);
   else accumulate_frame_kernel<false><<<dim3(blocks), dim3(kBlock), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_accumulate_counted(const AccumArgs& a, hipStream_t s) {
+  if (!a.tile_list || !a.moments) return hipErrorInvalidValue;
+  const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(blocks_for(a.num_slots), 4096));
+  accumulate_counted_kernel<<<dim3(blocks), dim3(kBlock), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_counted_merge(const MergeArgs& a, hipStream_t s) {
+  if (a.count == 0) return hipErrorInvalidValue;
+  counted_merge_kernel<<<dim3(blocks_for(a.count)), dim3(kBlock), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_priority(const PriorityArgs& a, uint32_t tiles, hipStream_t s) {
+  if (tiles == 0 || a.tiles_x == 0) return hipErrorInvalidValue;
+  tile_priority_kernel<<<dim3(tiles), dim3(kBlock), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_select(const float* priority, uint32_t tiles, uint32_t count, uint32_t* list, hipStream_t s) {
+  if (count == 0 || count > tiles || tiles > kMaxSelectTiles) return hipErrorInvalidValue;
+  tile_select_kernel<<<dim3(blocks_for(tiles)), dim3(kBlock), 0, s>>>(priority, tiles, count, list);
   return hipGetLastError();
 }
 

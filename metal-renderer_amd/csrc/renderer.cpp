@@ -26,6 +26,13 @@ using namespace mrt::host;
 
 namespace {
 
+// pixels of tile t inside the image
+uint64_t tile_pixels(const mrt_renderer* r, uint32_t t) {
+  const uint32_t tx = t % r->tiles_x, ty = t / r->tiles_x;
+  return (uint64_t)std::min<uint32_t>(mrt::kTile, r->desc.width - tx * mrt::kTile) *
+         std::min<uint32_t>(mrt::kTile, r->desc.height - ty * mrt::kTile);
+}
+
 int finalize_draw(mrt_renderer* r, DrawRecord& d) {
   if (!d.pending) return MRT_OK;
   HIP_TRY(hipEventSynchronize(d.stop));
@@ -37,12 +44,17 @@ int finalize_draw(mrt_renderer* r, DrawRecord& d) {
   // synchronous copy, so the host never waits for work queued after it
   HIP_TRY(hipEventSynchronize(d.copied));
   const uint32_t* cnt = static_cast<const uint32_t*>(d.host);
-  uint64_t active = r->owned_pixels * d.frames;   // bounce 0: every owned pixel's camera ray
+  if (d.listed) {   // a refine draw: its list is on the host by now (uploaded from there, or copied back behind the draw)
+    d.pixels = 0;
+    for (uint32_t k = 0; k < d.listed; ++k) d.pixels += tile_pixels(r, d.list_host[k]);
+    r->refine_stats.paths += d.pixels * d.frames;
+  }
+  uint64_t active = d.pixels * d.frames;   // bounce 0: every rendered pixel's camera ray
   for (uint32_t k = 0; k < lay.batches; ++k)
     for (uint32_t b = 0; b + 1 < lay.L; ++b) active += cnt[lay.total(k, b)];
   r->stats.active_ray_bounces += active;
   r->stats.last_draw_ms = ms;
-  const uint64_t paths = r->owned_pixels * d.frames;
+  const uint64_t paths = d.pixels * d.frames;
   r->stats.mpaths_per_s = ms > 0.0f ? (double)paths / (ms * 1e-3) / 1e6 : 0.0;
   r->stats.kernel_launches += (uint64_t)lay.batches * (r->path_mode || r->stream_mode ? 1u : lay.L);
   for (uint32_t k = 0; k < lay.batches; ++k) {
@@ -77,19 +89,21 @@ int finalize_pending(mrt_renderer* r) {
 
 // the noise chunks of frames [f0, f0 + n): generated (host threads, unless
 // the worker already has) and uploaded asynchronously; never waits for the GPU
-int acquire_noise(mrt_renderer* r, int64_t f0, uint32_t n, std::vector<mrt::NoiseSchedule::Chunk*>* out) {
+// (of schedule `noise`: the renderer's, or the refine draws' own)
+int acquire_noise(mrt_renderer* r, mrt::NoiseSchedule* noise, int64_t f0, uint32_t n,
+                  std::vector<mrt::NoiseSchedule::Chunk*>* out) {
   using NS = mrt::NoiseSchedule;
   const int64_t k0 = NS::chunk_of(f0), k1 = NS::chunk_of(f0 + (int64_t)n - 1);
-  HIP_TRY(r->noise->poll(k0, k1));   // (never evicts a chunk this draw reads)
-  const uint64_t waits = r->noise->counters().waits;
+  HIP_TRY(noise->poll(k0, k1));   // (never evicts a chunk this draw reads)
+  const uint64_t waits = noise->counters().waits;
   for (int64_t k = k0; k <= k1; ++k) {
     NS::Chunk* c = nullptr;
-    HIP_TRY(r->noise->acquire(k, r->draw_seq, &c));
+    HIP_TRY(noise->acquire(k, r->draw_seq, &c));
     if (out) out->push_back(c);
   }
-  if (r->noise->counters().waits != waits) r->stats.noise_waits += 1;
+  if (noise->counters().waits != waits) r->stats.noise_waits += 1;
   // the next chunk's tables are generated while these frames render
-  r->noise->prefetch(k1 + 1);
+  noise->prefetch(k1 + 1);
   return MRT_OK;
 }
 
@@ -269,16 +283,18 @@ int alloc_frame_buffers(mrt_renderer* r) {
 
 // A draw's frame batches: up to r->batch frames each, none crossing a noise
 // chunk (64 frames, a multiple of the batch): a 64-frame draw from a multiple
-// of 64 is one batch.  chunks: those of the draw's frames, in order
+// of 64 is one batch.  f0: the draw's first frame; chunks: those of the draw's
+// frames, in order
 struct Batch { uint64_t f; uint32_t frames; mrt::NoiseSchedule::Chunk* noise; };
-std::vector<Batch> plan_batches(const mrt_renderer* r, uint32_t n, const std::vector<mrt::NoiseSchedule::Chunk*>& chunks) {
+std::vector<Batch> plan_batches(const mrt_renderer* r, uint64_t f0, uint32_t n,
+                                const std::vector<mrt::NoiseSchedule::Chunk*>& chunks) {
   using NS = mrt::NoiseSchedule;
   std::vector<Batch> batches;
-  for (uint64_t f = r->frame_index, end = r->frame_index + n; f < end;) {
+  for (uint64_t f = f0, end = f0 + n; f < end;) {
     const int64_t k = NS::chunk_of((int64_t)f);
     const uint64_t chunk_end = (uint64_t)(k + 1) * NS::kChunkFrames;
     const uint32_t b = (uint32_t)std::min<uint64_t>({(uint64_t)r->batch, end - f, chunk_end - f});
-    batches.push_back({f, b, chunks[(size_t)(k - NS::chunk_of((int64_t)r->frame_index))]});
+    batches.push_back({f, b, chunks[(size_t)(k - NS::chunk_of((int64_t)f0))]});
     f += b;
   }
   return batches;
@@ -311,9 +327,10 @@ int size_draw_record(DrawRecord& d, size_t timed_events, bool* fresh) {
 }
 
 // The arguments of bounce launch b of `bt`, the draw's k-th batch, on slot
-// `fs` with camera generation `cg` (path / stream kernel: the one launch, b = 0)
-int bounce_args(const mrt_renderer* r, const DrawRecord& d, const Batch& bt, uint32_t k, uint32_t b, const FrameSlot& fs,
-                const CameraGen* cg, mrt::BounceArgs& a) {
+// `fs` with camera generation `cg` (path / stream kernel: the one launch, b = 0);
+// src.tiles > 0: over the renderer's tile list instead of the owned tiles
+int bounce_args(const mrt_renderer* r, const DrawSource& src, const DrawRecord& d, const Batch& bt, uint32_t k, uint32_t b,
+                const FrameSlot& fs, const CameraGen* cg, mrt::BounceArgs& a) {
   const uint32_t L = r->desc.max_path_length;
   uint32_t* cnt = d.counters.as<uint32_t>();
   uint32_t* seg = fs.segments.as<uint32_t>();
@@ -327,7 +344,8 @@ int bounce_args(const mrt_renderer* r, const DrawRecord& d, const Batch& bt, uin
   a.shard_rank = r->desc.shard_rank;
   a.shard_count = r->desc.shard_count;
   a.tiles_x = r->tiles_x;
-  a.num_slots = r->owned_tiles * 4096u;
+  a.num_slots = (src.tiles ? src.tiles : r->owned_tiles) * 4096u;
+  a.tile_list = src.tiles ? r->tile_list.as<uint32_t>() : nullptr;
   a.div_tiles = mrt::magic_div(a.tiles_x);
   a.div_slots = mrt::magic_div(a.num_slots);
   a.div_batch = mrt::magic_div(bt.frames);
@@ -367,7 +385,9 @@ int bounce_args(const mrt_renderer* r, const DrawRecord& d, const Batch& bt, uin
 
 // The arguments of batch `bt`'s accumulate; fold: the draw's last one, which
 // copies the draw's statistics to the pinned copy and zeroes the counters
-mrt::AccumArgs accum_args(const mrt_renderer* r, const DrawRecord& d, const Batch& bt, const FrameSlot& fs, bool fold) {
+// src.tiles > 0: the counted accumulate over the tile list into E / EM
+mrt::AccumArgs accum_args(const mrt_renderer* r, const DrawSource& src, const DrawRecord& d, const Batch& bt,
+                          const FrameSlot& fs, bool fold) {
   mrt::AccumArgs acc{};
   acc.width = r->desc.width;
   acc.height = r->desc.height;
@@ -378,11 +398,12 @@ mrt::AccumArgs accum_args(const mrt_renderer* r, const DrawRecord& d, const Batc
   acc.tiles_x = r->tiles_x;
   // (MRT_DEBUG bit 256, ablation: the accumulate launches but touches no
   // pixel — its statistics fold alone; a wrong image)
-  acc.num_slots = (r->debug & 256u) ? 0u : r->owned_tiles * 4096u;
+  acc.num_slots = (r->debug & 256u) ? 0u : (src.tiles ? src.tiles : r->owned_tiles) * 4096u;
   acc.radiance = fs.radiance.as<float4>();
-  acc.image = reinterpret_cast<float4*>(r->image);
+  acc.image = reinterpret_cast<float4*>(src.image);
   acc.accumulate = (r->desc.flags & MRT_FLAG_NO_ACCUMULATE) ? 0u : 1u;
-  acc.moments = r->moments.as<float4>();   // (null without MRT_FLAG_MOMENTS)
+  acc.moments = reinterpret_cast<float4*>(src.moments);   // (null without MRT_FLAG_MOMENTS)
+  acc.tile_list = src.tiles ? r->tile_list.as<uint32_t>() : nullptr;
   if (fold) {
     acc.counters = d.counters.as<uint32_t>();
     acc.host_counters = static_cast<uint32_t*>(d.host_dev);
@@ -530,21 +551,252 @@ int temporal_usable(const mrt_renderer* r, const char* what) {
   return MRT_OK;
 }
 
+// while the extra image E holds samples (adaptive sampling), every resolve is
+// followed by the counted merge with it: `out` = merge(out, extra), in place
+int merge_extras(mrt_renderer* r, DevBuf& out, const DevBuf& extra) {
+  if (!r->extras_valid) return MRT_OK;
+  return mrt_counted_merge(out.as<float>(), extra.as<float>(), out.as<float>(), r->desc.width, r->desc.height,
+                           r->desc.flags & MRT_FLAG_PRECISE, r->stream);
+}
+
 // resolve(image, frame_index, history if valid) into `out`, on the main stream
 int resolve_into(mrt_renderer* r, DevBuf& out) {
   const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
   if (out.bytes != bytes || !out.p) HIP_TRY(out.alloc(bytes));
-  return mrt_temporal_resolve(r->image, r->frame_index, r->history_valid ? r->history.as<float>() : nullptr,
-                              out.as<float>(), r->desc.width, r->desc.height, r->stream);
+  const int rc = mrt_temporal_resolve(r->image, r->frame_index, r->history_valid ? r->history.as<float>() : nullptr,
+                                      out.as<float>(), r->desc.width, r->desc.height, r->stream);
+  return rc ? rc : merge_extras(r, out, r->extra);
 }
 
 // the same for the moments image and its history (MRT_FLAG_MOMENTS)
 int resolve_moments_into(mrt_renderer* r, DevBuf& out) {
   const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
   if (out.bytes != bytes || !out.p) HIP_TRY(out.alloc(bytes));
-  return mrt_temporal_resolve(r->moments.as<float>(), r->frame_index,
-                              r->history_valid ? r->moments_history.as<float>() : nullptr, out.as<float>(),
-                              r->desc.width, r->desc.height, r->stream);
+  const int rc = mrt_temporal_resolve(r->moments.as<float>(), r->frame_index,
+                                      r->history_valid ? r->moments_history.as<float>() : nullptr, out.as<float>(),
+                                      r->desc.width, r->desc.height, r->stream);
+  return rc ? rc : merge_extras(r, out, r->extra_moments);
+}
+
+int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src);   // below
+
+// ---- adaptive sampling (include/mrt.h: mrt_renderer_refine) ----
+int refine_usable(const mrt_renderer* r, const char* what) {
+  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
+  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
+    return fail(MRT_ERR_STATE, std::string(what) + ": the renderer was created without MRT_FLAG_MOMENTS");
+  if (r->desc.shard_count > 1) return fail(MRT_ERR_STATE, std::string(what) + ": not on a sharded renderer");
+  if (r->desc.flags & MRT_FLAG_STATIC_NOISE)
+    return fail(MRT_ERR_STATE, std::string(what) + ": not with MRT_FLAG_STATIC_NOISE (every extra frame would repeat)");
+  if (!r->path_mode && !r->stream_mode)
+    return fail(MRT_ERR_STATE, std::string(what) + ": the per-bounce kernel has no tile-list instantiation");
+  return MRT_OK;
+}
+
+// E, EM, the list, the priorities, the second noise schedule and the list's
+// event: made at the first refine / draw_tiles, E and EM zeroed on the main stream
+int ensure_extras(mrt_renderer* r) {
+  HIP_TRY(hipSetDevice(r->scene->device));
+  const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
+  const size_t tile_bytes = (size_t)r->tiles_x * r->tiles_y * 4;
+  if (!r->list_ready) HIP_TRY(hipEventCreateWithFlags(&r->list_ready, hipEventDisableTiming));
+  if (!r->refine_noise) {
+    r->refine_noise = std::make_unique<mrt::NoiseSchedule>(r->desc.seed ^ MRT_REFINE_SEED_XOR, false);
+    HIP_TRY(r->refine_noise->init());
+  }
+  for (DevBuf* b : {&r->extra, &r->extra_moments})
+    if (b->bytes != bytes || !b->p) {
+      r->extras_current = false;
+      HIP_TRY(b->alloc(bytes));
+    }
+  for (DevBuf* b : {&r->tile_list, &r->tile_priority})
+    if (b->bytes != tile_bytes || !b->p) {
+      r->priority_current = false;
+      r->list_count = 0;
+      HIP_TRY(b->alloc(tile_bytes));
+    }
+  if (!r->extras_current) {
+    HIP_TRY(hipMemsetAsync(r->extra.p, 0, bytes, r->stream));
+    HIP_TRY(hipMemsetAsync(r->extra_moments.p, 0, bytes, r->stream));
+    r->extras_current = true;
+    r->extras_valid = false;
+  }
+  return MRT_OK;
+}
+
+// `frames` extra frames of the `count` tiles of the device list (host_list:
+// uploaded first) into E / EM, from the refine schedule at the extra-frame counter
+int draw_extra(mrt_renderer* r, const uint32_t* host_list, uint32_t count, uint32_t frames) {
+  DrawSource src;
+  src.noise = r->refine_noise.get();
+  src.f0 = r->refine_stats.extra_frames;
+  src.tiles = count;
+  src.host_list = host_list;
+  src.image = r->extra.as<float>();
+  src.moments = r->extra_moments.as<float>();
+  r->refine_stats.extra_frames += frames;   // whatever becomes of the draw: no noise is ever read twice
+  const int rc = draw_frames(r, frames, src);
+  if (rc) return rc;
+  r->extras_valid = true;
+  r->list_count = count;
+  r->refine_stats.passes += 1;
+  r->refine_stats.tile_frames += (uint64_t)count * frames;
+  return MRT_OK;
+}
+
+// mrt_renderer_read_extra / _read_extra_moments
+int read_extra_plane(mrt_renderer* r, const DevBuf& plane, float* rgba, size_t count) {
+  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
+  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
+  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
+  if (!r->extras_current) return fail(MRT_ERR_STATE, "no refine or draw_tiles has run at the renderer's current size");
+  const int rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(rgba, plane.p, need * 4, hipMemcpyDeviceToHost));
+  return MRT_OK;
+}
+
+// Enqueue n frames of `src` (host_internal.h DrawSource): the draw loop of
+// mrt_renderer_draw_n and of the refine draws.  The caller advances its own
+// frame counter and statistics.
+int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src) {
+  DrawRecord& d = r->draws[r->draw_next];
+  // at most kDrawRing (3) draws in flight: the ring entry's previous draw must
+  // have finished — the reference's MaxBuffersInFlight semaphore
+  // (renderer/Renderer.mm:16, :593-600), the only host wait of a draw
+  if (d.pending && hipEventQuery(d.copied) == hipErrorNotReady) r->stats.inflight_waits += 1;
+  int rc = finalize_draw(r, d);
+  if (rc) return rc;
+  r->draw_seq += 1;
+  std::vector<mrt::NoiseSchedule::Chunk*> chunks;
+  rc = acquire_noise(r, src.noise, (int64_t)src.f0, n, &chunks);
+  if (rc) return rc;
+  const std::vector<Batch> batches = plan_batches(r, src.f0, n, chunks);
+  const uint32_t nb = (uint32_t)batches.size();
+  d.layout = CounterLayout(nb, r->desc.max_path_length);   // (the entry's previous draw is read back: nothing reads its layout)
+  const uint32_t launches_per_batch = r->path_mode || r->stream_mode ? 1u : r->desc.max_path_length;
+  const bool profile = (r->desc.flags & MRT_FLAG_PROFILE) != 0;
+  bool fresh = false;
+  rc = size_draw_record(d, profile ? (size_t)2 * nb * launches_per_batch : 0, &fresh);   // at most every batch is timed
+  if (rc) return rc;
+  if (src.tiles) {
+    // the list: a host list goes to the device from the entry's pinned staging;
+    // one chosen on the device comes back to it behind the draw (finalize_draw
+    // counts its pixels).  On the main stream, which follows every launch that
+    // read the previous list; the render streams wait for it through the event
+    const uint32_t T = r->tiles_x * r->tiles_y;
+    if (d.list_cap < T) {
+      if (d.list_host) HIP_TRY(hipHostFree(d.list_host));
+      d.list_host = nullptr;
+      d.list_cap = 0;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d.list_host), (size_t)T * 4, hipHostMallocDefault));
+      d.list_cap = T;
+    }
+    if (src.host_list) {
+      std::memcpy(d.list_host, src.host_list, (size_t)src.tiles * 4);
+      HIP_TRY(hipMemcpyAsync(r->tile_list.p, d.list_host, (size_t)src.tiles * 4, hipMemcpyHostToDevice, r->stream));
+    } else {
+      HIP_TRY(hipMemcpyAsync(d.list_host, r->tile_list.p, (size_t)src.tiles * 4, hipMemcpyDeviceToHost, r->stream));
+    }
+    HIP_TRY(hipEventRecord(r->list_ready, r->stream));
+  }
+  HIP_TRY(hipEventRecord(d.start, r->stream));
+  // The render launches never wait on the main stream (it only carries
+  // accumulates and image work; a noise chunk's upload is waited for through
+  // its own event): the counters are cleared on the first batch's render
+  // stream and the draw's other render streams wait for that.
+  // The draw's last accumulate copies its statistics to the pinned host copy
+  // and zeroes the counters for the ring entry's next draw (whose host side
+  // has waited for that accumulate in finalize_draw): a fresh buffer, or one
+  // whose last draw stopped before its folding accumulate, is the only one to
+  // clear here.  MRT_COUNTER_FOLD=0: memset + copy per draw.
+  const uint32_t s0 = r->slot_next;
+  const bool clear = fresh || !d.clean || !r->counter_fold;
+  d.clean = false;   // set again once this draw's folding accumulate is enqueued
+  if (clear) HIP_TRY(hipMemsetAsync(d.counters.p, 0, d.counters.bytes, r->slots[s0].stream));
+  if (clear && r->inflight > 1 && nb > 1) {
+    HIP_TRY(hipEventRecord(d.cleared, r->slots[s0].stream));
+    for (uint32_t j = 1; j < std::min(nb, r->inflight); ++j)
+      HIP_TRY(hipStreamWaitEvent(r->slots[(s0 + j) % r->inflight].stream, d.cleared, 0));
+  }
+  size_t ev = 0;
+  for (uint32_t k = 0; k < nb; ++k) {
+    const Batch& bt = batches[k];
+    const uint32_t slot = (s0 + k) % r->inflight;
+    FrameSlot& fs = r->slots[slot];
+    const bool own = fs.stream != r->stream;
+    // the slot's radiance is free once the accumulate that last read it ran.
+    // (Rotating batch-sized regions of it instead, so that a single-frame
+    // draw waits only once per 64 frames, measured -1.1 % on the per-frame
+    // cadence: the next kernel then competes with the accumulates for CUs.)
+    if (own && fs.acc_recorded) HIP_TRY(hipStreamWaitEvent(fs.stream, fs.acc_done, 0));
+    if (own && src.tiles) HIP_TRY(hipStreamWaitEvent(fs.stream, r->list_ready, 0));
+    // the noise chunk's upload (once per chunk upload and render stream)
+    if (!(bt.noise->waited_streams & (1u << slot))) {
+      HIP_TRY(hipStreamWaitEvent(fs.stream, bt.noise->ready, 0));
+      bt.noise->waited_streams |= 1u << slot;
+    }
+    // the camera generation's upload, likewise (set_camera with draws in flight)
+    CameraGen* cg = r->cam_cur;
+    if (!(cg->waited_streams & (1u << slot))) {
+      HIP_TRY(hipStreamWaitEvent(fs.stream, cg->ready, 0));
+      cg->waited_streams |= 1u << slot;
+    }
+    // every batch holding a frame f with f % profile_every == 0: every
+    // batch of a batched draw, every 8th single-frame draw
+    const bool timed = profile && ((bt.f % r->profile_every) == 0 || (bt.f % r->profile_every) + bt.frames > r->profile_every);
+    for (uint32_t b = 0; b < launches_per_batch; ++b) {
+      mrt::BounceArgs a{};
+      rc = bounce_args(r, src, d, bt, k, b, fs, cg, a);
+      if (rc) return rc;
+      if (timed) HIP_TRY(hipEventRecord(d.kernel_events[ev++], fs.stream));
+      if (r->path_mode)
+        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_paths(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
+      else if (r->stream_mode)
+        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_stream(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
+      else
+        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_bounce(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
+      if (timed) HIP_TRY(hipEventRecord(d.kernel_events[ev++], fs.stream));
+    }
+    // accumulateImage for frames f .. f+batch-1 on the main stream, in batch
+    // order (the running mean's order), behind this batch's render launch
+    if (own) {
+      HIP_TRY(hipEventRecord(fs.kernel_done, fs.stream));
+      HIP_TRY(hipStreamWaitEvent(r->stream, fs.kernel_done, 0));
+    }
+    const bool fold = k + 1 == nb && r->counter_fold;
+    if (src.tiles)
+      HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_accumulate_counted(accum_args(r, src, d, bt, fs, fold), r->stream)));
+    else
+      HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_accumulate_frame(accum_args(r, src, d, bt, fs, fold), r->stream)));
+    HIP_TRY(hipEventRecord(fs.acc_done, r->stream));
+    fs.acc_recorded = true;
+    if (fold) d.clean = true;
+  }
+  r->slot_next = (s0 + nb) % r->inflight;
+  HIP_TRY(hipEventRecord(d.stop, r->stream));
+  // the chunks' buffers are reusable once this draw's accumulates (which
+  // follow every render launch of the draw) have run
+  for (mrt::NoiseSchedule::Chunk* c : chunks) {
+    HIP_TRY(hipEventRecord(c->last_use, r->stream));
+    c->used = true;
+  }
+  {   // enqueued while the previous draw is still rendering (frames in flight)
+    const DrawRecord& prev = r->draws[(r->draw_next + kDrawRing - 1) % kDrawRing];
+    if (prev.pending && hipEventQuery(prev.stop) == hipErrorNotReady) r->stats.draws_overlapped += 1;
+  }
+  // (no stream of its own: a process has few hardware queues — 4 by
+  // default — and two streams sharing one serialise their launches)
+  if (!r->counter_fold)
+    HIP_TRY(hipMemcpyAsync(d.host, d.counters.p, d.layout.bytes, hipMemcpyDeviceToHost, r->stream));
+  HIP_TRY(hipEventRecord(d.copied, r->stream));
+  d.pending = true;
+  d.frames = n;
+  d.pixels = src.tiles ? 0 : r->owned_pixels;
+  d.listed = src.tiles;
+  d.events = ev;
+  r->draw_next = (r->draw_next + 1) % kDrawRing;
+  return MRT_OK;
 }
 
 }  // namespace
@@ -695,6 +947,8 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   r->guides_current = r->denoised_current = false;
   r->history_valid = r->resolved_current = false;
   r->variance_current = false;
+  r->extras_current = r->extras_valid = r->priority_current = false;   // re-made (and zeroed) by the next refine / draw_tiles
+  r->list_count = 0;
   if (r->denoised.p) {     // a renderer that has denoised keeps its buffers, at the new size
     const size_t bytes = (size_t)width * height * 16;
     HIP_TRY(r->guide_n.alloc(bytes));
@@ -723,6 +977,12 @@ int mrt_renderer_reset(mrt_renderer* r) {
   if (r->image_foreign || !r->own_image) {
     HIP_TRY(hipMemsetAsync(r->image, 0, (size_t)r->desc.width * r->desc.height * 16, r->stream));
     r->image_foreign = false;
+  }
+  if (r->extras_valid) {      // the extra samples go with the frames they refined (stream-ordered, as above)
+    const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
+    HIP_TRY(hipMemsetAsync(r->extra.p, 0, bytes, r->stream));
+    HIP_TRY(hipMemsetAsync(r->extra_moments.p, 0, bytes, r->stream));
+    r->extras_valid = false;
   }
   r->frame_index = 0;
   r->stats.frame_index = 0;   // cumulative counters (paths, A, kernel time) persist
@@ -758,7 +1018,7 @@ int mrt_renderer_get_camera(const mrt_renderer* r, mrt_camera* out) {
 
 int mrt_renderer_prepare(mrt_renderer* r, uint32_t n) {
   if (!r) return fail(MRT_ERR_INVALID, "null renderer");
-  return acquire_noise(r, (int64_t)r->frame_index, std::max<uint32_t>(1, n), nullptr);
+  return acquire_noise(r, r->noise.get(), (int64_t)r->frame_index, std::max<uint32_t>(1, n), nullptr);
 }
 
 int mrt_renderer_draw_n(mrt_renderer* r, uint32_t n) {
@@ -766,116 +1026,14 @@ int mrt_renderer_draw_n(mrt_renderer* r, uint32_t n) {
   if (r->max_frames)   // MAX_FRAMES: renderer/Renderer.mm:589-590
     n = r->frame_index >= r->max_frames ? 0u : (uint32_t)std::min<uint64_t>(n, r->max_frames - r->frame_index);
   if (n == 0) return MRT_OK;
-  DrawRecord& d = r->draws[r->draw_next];
-  // at most kDrawRing (3) draws in flight: the ring entry's previous draw must
-  // have finished — the reference's MaxBuffersInFlight semaphore
-  // (renderer/Renderer.mm:16, :593-600), the only host wait of a draw
-  if (d.pending && hipEventQuery(d.copied) == hipErrorNotReady) r->stats.inflight_waits += 1;
-  int rc = finalize_draw(r, d);
+  DrawSource src;
+  src.noise = r->noise.get();
+  src.f0 = r->frame_index;
+  src.image = r->image;
+  src.moments = r->moments.as<float>();
+  const int rc = draw_frames(r, n, src);
   if (rc) return rc;
-  r->draw_seq += 1;
-  std::vector<mrt::NoiseSchedule::Chunk*> chunks;
-  rc = acquire_noise(r, (int64_t)r->frame_index, n, &chunks);
-  if (rc) return rc;
-  const std::vector<Batch> batches = plan_batches(r, n, chunks);
-  const uint32_t nb = (uint32_t)batches.size();
-  d.layout = CounterLayout(nb, r->desc.max_path_length);   // (the entry's previous draw is read back: nothing reads its layout)
-  const uint32_t launches_per_batch = r->path_mode || r->stream_mode ? 1u : r->desc.max_path_length;
-  const bool profile = (r->desc.flags & MRT_FLAG_PROFILE) != 0;
-  bool fresh = false;
-  rc = size_draw_record(d, profile ? (size_t)2 * nb * launches_per_batch : 0, &fresh);   // at most every batch is timed
-  if (rc) return rc;
-  HIP_TRY(hipEventRecord(d.start, r->stream));
-  // The render launches never wait on the main stream (it only carries
-  // accumulates and image work; a noise chunk's upload is waited for through
-  // its own event): the counters are cleared on the first batch's render
-  // stream and the draw's other render streams wait for that.
-  // The draw's last accumulate copies its statistics to the pinned host copy
-  // and zeroes the counters for the ring entry's next draw (whose host side
-  // has waited for that accumulate in finalize_draw): a fresh buffer, or one
-  // whose last draw stopped before its folding accumulate, is the only one to
-  // clear here.  MRT_COUNTER_FOLD=0: memset + copy per draw.
-  const uint32_t s0 = r->slot_next;
-  const bool clear = fresh || !d.clean || !r->counter_fold;
-  d.clean = false;   // set again once this draw's folding accumulate is enqueued
-  if (clear) HIP_TRY(hipMemsetAsync(d.counters.p, 0, d.counters.bytes, r->slots[s0].stream));
-  if (clear && r->inflight > 1 && nb > 1) {
-    HIP_TRY(hipEventRecord(d.cleared, r->slots[s0].stream));
-    for (uint32_t j = 1; j < std::min(nb, r->inflight); ++j)
-      HIP_TRY(hipStreamWaitEvent(r->slots[(s0 + j) % r->inflight].stream, d.cleared, 0));
-  }
-  size_t ev = 0;
-  for (uint32_t k = 0; k < nb; ++k) {
-    const Batch& bt = batches[k];
-    const uint32_t slot = (s0 + k) % r->inflight;
-    FrameSlot& fs = r->slots[slot];
-    const bool own = fs.stream != r->stream;
-    // the slot's radiance is free once the accumulate that last read it ran.
-    // (Rotating batch-sized regions of it instead, so that a single-frame
-    // draw waits only once per 64 frames, measured -1.1 % on the per-frame
-    // cadence: the next kernel then competes with the accumulates for CUs.)
-    if (own && fs.acc_recorded) HIP_TRY(hipStreamWaitEvent(fs.stream, fs.acc_done, 0));
-    // the noise chunk's upload (once per chunk upload and render stream)
-    if (!(bt.noise->waited_streams & (1u << slot))) {
-      HIP_TRY(hipStreamWaitEvent(fs.stream, bt.noise->ready, 0));
-      bt.noise->waited_streams |= 1u << slot;
-    }
-    // the camera generation's upload, likewise (set_camera with draws in flight)
-    CameraGen* cg = r->cam_cur;
-    if (!(cg->waited_streams & (1u << slot))) {
-      HIP_TRY(hipStreamWaitEvent(fs.stream, cg->ready, 0));
-      cg->waited_streams |= 1u << slot;
-    }
-    // every batch holding a frame f with f % profile_every == 0: every
-    // batch of a batched draw, every 8th single-frame draw
-    const bool timed = profile && ((bt.f % r->profile_every) == 0 || (bt.f % r->profile_every) + bt.frames > r->profile_every);
-    for (uint32_t b = 0; b < launches_per_batch; ++b) {
-      mrt::BounceArgs a{};
-      rc = bounce_args(r, d, bt, k, b, fs, cg, a);
-      if (rc) return rc;
-      if (timed) HIP_TRY(hipEventRecord(d.kernel_events[ev++], fs.stream));
-      if (r->path_mode)
-        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_paths(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
-      else if (r->stream_mode)
-        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_stream(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
-      else
-        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_bounce(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
-      if (timed) HIP_TRY(hipEventRecord(d.kernel_events[ev++], fs.stream));
-    }
-    // accumulateImage for frames f .. f+batch-1 on the main stream, in batch
-    // order (the running mean's order), behind this batch's render launch
-    if (own) {
-      HIP_TRY(hipEventRecord(fs.kernel_done, fs.stream));
-      HIP_TRY(hipStreamWaitEvent(r->stream, fs.kernel_done, 0));
-    }
-    const bool fold = k + 1 == nb && r->counter_fold;
-    HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_accumulate_frame(accum_args(r, d, bt, fs, fold), r->stream)));
-    HIP_TRY(hipEventRecord(fs.acc_done, r->stream));
-    fs.acc_recorded = true;
-    if (fold) d.clean = true;
-  }
-  r->slot_next = (s0 + nb) % r->inflight;
-  HIP_TRY(hipEventRecord(d.stop, r->stream));
-  // the chunks' buffers are reusable once this draw's accumulates (which
-  // follow every render launch of the draw) have run
-  for (mrt::NoiseSchedule::Chunk* c : chunks) {
-    HIP_TRY(hipEventRecord(c->last_use, r->stream));
-    c->used = true;
-  }
-  {   // enqueued while the previous draw is still rendering (frames in flight)
-    const DrawRecord& prev = r->draws[(r->draw_next + kDrawRing - 1) % kDrawRing];
-    if (prev.pending && hipEventQuery(prev.stop) == hipErrorNotReady) r->stats.draws_overlapped += 1;
-  }
   r->stats.draws += 1;
-  // (no stream of its own: a process has few hardware queues — 4 by
-  // default — and two streams sharing one serialise their launches)
-  if (!r->counter_fold)
-    HIP_TRY(hipMemcpyAsync(d.host, d.counters.p, d.layout.bytes, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipEventRecord(d.copied, r->stream));
-  d.pending = true;
-  d.frames = n;
-  d.events = ev;
-  r->draw_next = (r->draw_next + 1) % kDrawRing;
   r->frame_index += n;
   r->stats.frame_index = r->frame_index;
   r->stats.paths += r->owned_pixels * n;
@@ -1156,6 +1314,103 @@ int mrt_renderer_read_variance(mrt_renderer* r, float* plane, size_t count) {
   return MRT_OK;
 }
 
+// ---- adaptive sampling (include/mrt.h: mrt_renderer_refine) -----------------
+int mrt_renderer_draw_tiles(mrt_renderer* r, const uint32_t* tiles, uint32_t count, uint32_t frames) {
+  int rc = refine_usable(r, "mrt_renderer_draw_tiles");
+  if (rc) return rc;
+  const uint32_t T = r->tiles_x * r->tiles_y;
+  if (!tiles || count == 0 || count > T || frames == 0)
+    return fail(MRT_ERR_INVALID, "mrt_renderer_draw_tiles: need a list of 1..tiles_x * tiles_y tiles and frames >= 1");
+  std::vector<bool> seen(T, false);
+  for (uint32_t k = 0; k < count; ++k) {
+    if (tiles[k] >= T) return fail(MRT_ERR_INVALID, "mrt_renderer_draw_tiles: tile " + std::to_string(tiles[k]) + " out of range");
+    if (seen[tiles[k]]) return fail(MRT_ERR_INVALID, "mrt_renderer_draw_tiles: tile " + std::to_string(tiles[k]) + " listed twice");
+    seen[tiles[k]] = true;
+  }
+  rc = ensure_extras(r);
+  if (rc) return rc;
+  return draw_extra(r, tiles, count, frames);
+}
+
+int mrt_renderer_refine(mrt_renderer* r, uint32_t frames, uint32_t tile_count, const mrt_adaptive_params* params) {
+  int rc = refine_usable(r, "mrt_renderer_refine");
+  if (rc) return rc;
+  const uint32_t W = r->desc.width, H = r->desc.height, T = r->tiles_x * r->tiles_y;
+  if (frames == 0 || tile_count == 0 || tile_count > T || T > mrt::kMaxSelectTiles)
+    return fail(MRT_ERR_INVALID, "mrt_renderer_refine: need frames >= 1 and 1 <= tile_count <= tiles_x * tiles_y <= 16384");
+  mrt_adaptive_params p;
+  if (params) p = *params;
+  else (void)mrt_adaptive_params_default(&p);
+  rc = mrt_adaptive_params_check(&p);
+  if (rc) return rc;
+  if (r->frame_index == 0 && !r->history_valid)
+    return fail(MRT_ERR_STATE, "mrt_renderer_refine: no frame accumulated and no valid history");
+  mrt_svgf_params sp;
+  (void)mrt_svgf_params_default(&sp);
+  rc = ensure_extras(r);
+  if (rc) return rc;
+  const size_t bytes = (size_t)W * H * 16;
+  if (r->variance.bytes != bytes / 4 || !r->variance.p) {
+    r->variance_current = false;
+    HIP_TRY(r->variance.alloc(bytes / 4));
+  }
+  rc = ensure_guides(r);
+  if (rc) return rc;
+  rc = mrt_renderer_resolve(r);
+  if (rc) return rc;
+  rc = resolve_moments_into(r, r->moments_resolved);
+  if (rc) return rc;
+  rc = mrt_variance(r->moments_resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
+                    r->variance.as<float>(), W, H, &sp, r->stream);
+  if (rc) return rc;
+  r->variance_current = true;
+  rc = mrt_tile_priority(r->resolved.as<float>(), r->variance.as<float>(), r->guide_n.as<float>(),
+                         r->tile_priority.as<float>(), W, H, &p, r->desc.flags & MRT_FLAG_PRECISE, r->stream);
+  if (rc) return rc;
+  r->priority_current = true;
+  rc = mrt_tile_select(r->tile_priority.as<float>(), T, tile_count, r->tile_list.as<uint32_t>(), r->stream);
+  if (rc) return rc;
+  return draw_extra(r, nullptr, tile_count, frames);
+}
+
+int mrt_renderer_read_extra(mrt_renderer* r, float* rgba, size_t count) {
+  return r ? read_extra_plane(r, r->extra, rgba, count) : fail(MRT_ERR_INVALID, "null argument");
+}
+
+int mrt_renderer_read_extra_moments(mrt_renderer* r, float* rgba, size_t count) {
+  return r ? read_extra_plane(r, r->extra_moments, rgba, count) : fail(MRT_ERR_INVALID, "null argument");
+}
+
+int mrt_renderer_read_tile_priority(mrt_renderer* r, float* priority, size_t count) {
+  if (!r || !priority) return fail(MRT_ERR_INVALID, "null argument");
+  const size_t T = (size_t)r->tiles_x * r->tiles_y;
+  if (count < T) return fail(MRT_ERR_INVALID, "output buffer too small");
+  if (!r->priority_current) return fail(MRT_ERR_STATE, "no refine has run at the renderer's current size");
+  const int rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(priority, r->tile_priority.p, T * 4, hipMemcpyDeviceToHost));
+  return MRT_OK;
+}
+
+int mrt_renderer_read_tile_list(mrt_renderer* r, uint32_t* tiles, size_t capacity, uint32_t* count) {
+  if (!r || !tiles || !count) return fail(MRT_ERR_INVALID, "null argument");
+  if (r->list_count == 0) return fail(MRT_ERR_STATE, "no refine or draw_tiles has run at the renderer's current size");
+  if (capacity < r->list_count) return fail(MRT_ERR_INVALID, "output buffer too small");
+  const int rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(tiles, r->tile_list.p, (size_t)r->list_count * 4, hipMemcpyDeviceToHost));
+  *count = r->list_count;
+  return MRT_OK;
+}
+
+int mrt_renderer_refine_stats(mrt_renderer* r, mrt_refine_stats* stats) {
+  if (!r || !stats) return fail(MRT_ERR_INVALID, "null argument");
+  const int rc = finalize_pending(r);   // counts the pixels of the lists not yet read back
+  if (rc) return rc;
+  *stats = r->refine_stats;
+  return MRT_OK;
+}
+
 int mrt_renderer_load_reference(mrt_renderer* r, const char* path) {
   if (!r || !path) return fail(MRT_ERR_INVALID, "null argument");
   std::vector<float> img;
@@ -1278,6 +1533,10 @@ int mrt_renderer_destroy(mrt_renderer* r) {
     if (d.copied) (void)hipEventDestroy(d.copied);
     if (d.host) (void)hipHostFree(d.host);
   }
+  if (r->list_ready) (void)hipEventDestroy(r->list_ready);
+  for (DrawRecord& d : r->draws)
+    if (d.list_host) (void)hipHostFree(d.list_host);
+  r->refine_noise.reset();
   r->noise.reset();   // joins the worker; the draws reading its chunks have finished (stream synchronised above)
   if (r->own_stream) (void)hipStreamDestroy(r->stream);
   delete r;

@@ -509,6 +509,74 @@ int mrt_debug_denoise_variance_step(const float* image, const float* variance, c
   return svgf_run(image, variance, guide_n, guide_p, out, nullptr, nullptr, W, H, params, 1u, step_log2, path, false, stream);
 }
 
+// ---- adaptive sampling (include/mrt.h) ---------------------------------------
+int mrt_adaptive_params_default(mrt_adaptive_params* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_adaptive_params_default: null params");
+  out->luminance_floor = 0.01f;
+  return MRT_OK;
+}
+
+int mrt_adaptive_params_check(const mrt_adaptive_params* p) {
+  if (!p) return fail(MRT_ERR_INVALID, "adaptive params: null");
+  if (!std::isfinite(p->luminance_floor) || !(p->luminance_floor > 0.0f))
+    return fail(MRT_ERR_INVALID, "adaptive params: luminance_floor must be finite and positive");
+  return MRT_OK;
+}
+
+int mrt_counted_merge(const float* a, const float* b, float* out, uint32_t W, uint32_t H, uint32_t flags, void* stream) {
+  if (!a || !b || !out || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_counted_merge: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  if (planes_overlap(b, out, bytes) || (out != a && planes_overlap(a, out, bytes)))
+    return fail(MRT_ERR_INVALID, "mrt_counted_merge: out may be a itself; any other overlap with an input is invalid");
+  mrt::MergeArgs m{};
+  m.a = reinterpret_cast<const float4*>(a);
+  m.b = reinterpret_cast<const float4*>(b);
+  m.out = reinterpret_cast<float4*>(out);
+  m.count = W * H;
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_counted_merge(m, (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+int mrt_tile_priority(const float* image, const float* variance, const float* guide_n, float* priority, uint32_t W,
+                      uint32_t H, const mrt_adaptive_params* params, uint32_t flags, void* stream) {
+  if (!image || !variance || !guide_n || !priority || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_tile_priority: bad argument");
+  const int rc = mrt_adaptive_params_check(params);
+  if (rc) return rc;
+  const uint32_t tx = (W + mrt::kTile - 1) / mrt::kTile, ty = (H + mrt::kTile - 1) / mrt::kTile;
+  const size_t bytes = (size_t)W * H * 16, out_bytes = (size_t)tx * ty * 4;
+  const struct { const float* p; size_t n; } in[] = {{image, bytes}, {variance, bytes / 4}, {guide_n, bytes}};
+  for (const auto& b : in) {
+    const char* p = (const char*)b.p;
+    const char* q = (const char*)priority;
+    if (p < q + out_bytes && q < p + b.n) return fail(MRT_ERR_INVALID, "mrt_tile_priority: priority must not overlap an input");
+  }
+  mrt::PriorityArgs a{};
+  a.image = reinterpret_cast<const float4*>(image);
+  a.variance = variance;
+  a.guide_n = reinterpret_cast<const float4*>(guide_n);
+  a.priority = priority;
+  a.width = W;
+  a.height = H;
+  a.tiles_x = tx;
+  a.eps2 = params->luminance_floor * params->luminance_floor;
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_tile_priority(a, tx * ty, (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+int mrt_tile_select(const float* priority, uint32_t tiles, uint32_t count, uint32_t* list, void* stream) {
+  if (!priority || !list) return fail(MRT_ERR_INVALID, "mrt_tile_select: null argument");
+  if (count == 0 || count > tiles || tiles > mrt::kMaxSelectTiles)
+    return fail(MRT_ERR_INVALID, "mrt_tile_select: need 1 <= count <= tiles <= 16384");
+  const char* p = (const char*)priority;
+  const char* q = (const char*)list;
+  if (p < q + (size_t)count * 4 && q < p + (size_t)tiles * 4)
+    return fail(MRT_ERR_INVALID, "mrt_tile_select: list must not overlap priority");
+  HIP_TRY(mrt::fast::launch_tile_select(priority, tiles, count, list, (hipStream_t)stream));   // exact: one code in both builds
+  return MRT_OK;
+}
+
 // ---- temporal history (include/mrt.h) --------------------------------------
 int mrt_reproject_params_default(mrt_reproject_params* out) {
   if (!out) return fail(MRT_ERR_INVALID, "mrt_reproject_params_default: null params");

@@ -42,6 +42,8 @@ FLAG_STATIC_NOISE = 4       # ANIMATE_NOISE 0
 FLAG_NO_ACCUMULATE = 8      # ACCUMULATE_IMAGE false
 FLAG_DEBUG_MATERIAL = 16    # DEBUG_MATERIAL 1
 FLAG_MOMENTS = 32           # luminance moments accumulated beside the image (variance-guided denoising)
+REFINE_SEED_XOR = 0x9E3779B97F4A7C15   # MRT_REFINE_SEED_XOR: the refine draws' noise seed is seed ^ this
+TILE = 64                   # the unit of adaptive sampling (and of sharding): 64x64 pixels
 COMM_ID_BYTES = 128
 EXCHANGE_GATHER, EXCHANGE_REDUCE, EXCHANGE_OVERLAP = 1, 2, 0x100
 DEFAULT_SEED = 0x6D6574616C2D7274  # "metal-rt"
@@ -239,6 +241,32 @@ class SvgfParams(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AdaptiveParams(ctypes.Structure):
+    """mrt_adaptive_params (include/mrt.h): the tile priority's parameters."""
+    _fields_ = [("luminance_floor", ctypes.c_float)]
+
+    @classmethod
+    def default(cls) -> "AdaptiveParams":
+        p = cls()
+        _check(lib().mrt_adaptive_params_default(ctypes.byref(p)), "mrt_adaptive_params_default")
+        return p
+
+    def check(self) -> None:
+        _check(lib().mrt_adaptive_params_check(ctypes.byref(self)), "mrt_adaptive_params_check")
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class RefineStats(ctypes.Structure):
+    """mrt_refine_stats (include/mrt.h)."""
+    _fields_ = [("passes", ctypes.c_uint64), ("extra_frames", ctypes.c_uint64), ("tile_frames", ctypes.c_uint64),
+                ("paths", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 EXPORTED = [
     "mrt_scene_create", "mrt_scene_info_get", "mrt_scene_export", "mrt_scene_destroy", "mrt_scene_check_bvh",
     "mrt_raygen", "mrt_intersect", "mrt_shade", "mrt_resolve_shadow", "mrt_accumulate",
@@ -267,6 +295,10 @@ EXPORTED = [
     "mrt_moments", "mrt_svgf_params_default", "mrt_svgf_params_check", "mrt_variance", "mrt_denoise_variance",
     "mrt_renderer_read_moments", "mrt_renderer_moments", "mrt_renderer_denoise_variance",
     "mrt_renderer_read_variance", "mrt_debug_denoise_variance_step",
+    "mrt_adaptive_params_default", "mrt_adaptive_params_check", "mrt_counted_merge", "mrt_tile_priority",
+    "mrt_tile_select", "mrt_renderer_draw_tiles", "mrt_renderer_refine", "mrt_renderer_read_extra",
+    "mrt_renderer_read_extra_moments", "mrt_renderer_read_tile_priority", "mrt_renderer_read_tile_list",
+    "mrt_renderer_refine_stats",
 ]
 
 _lib = None
@@ -389,6 +421,18 @@ def lib() -> ctypes.CDLL:
         "mrt_renderer_denoise_variance": [vp, ctypes.POINTER(SvgfParams)],
         "mrt_renderer_read_variance": [vp, vp, ctypes.c_size_t],
         "mrt_debug_denoise_variance_step": [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(SvgfParams), u32, u32, vp],
+        "mrt_adaptive_params_default": [ctypes.POINTER(AdaptiveParams)],
+        "mrt_adaptive_params_check": [ctypes.POINTER(AdaptiveParams)],
+        "mrt_counted_merge": [vp, vp, vp, u32, u32, u32, vp],
+        "mrt_tile_priority": [vp, vp, vp, vp, u32, u32, ctypes.POINTER(AdaptiveParams), u32, vp],
+        "mrt_tile_select": [vp, u32, u32, vp, vp],
+        "mrt_renderer_draw_tiles": [vp, vp, u32, u32],
+        "mrt_renderer_refine": [vp, u32, u32, ctypes.POINTER(AdaptiveParams)],
+        "mrt_renderer_read_extra": [vp, vp, ctypes.c_size_t],
+        "mrt_renderer_read_extra_moments": [vp, vp, ctypes.c_size_t],
+        "mrt_renderer_read_tile_priority": [vp, vp, ctypes.c_size_t],
+        "mrt_renderer_read_tile_list": [vp, vp, ctypes.c_size_t, ctypes.POINTER(u32)],
+        "mrt_renderer_refine_stats": [vp, ctypes.POINTER(RefineStats)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -694,6 +738,63 @@ class Renderer:
                "mrt_renderer_read_variance")
         return v
 
+    # ---- adaptive sampling (include/mrt.h: mrt_renderer_refine) ----
+    def tile_count(self) -> int:
+        return ((self.width + TILE - 1) // TILE) * ((self.height + TILE - 1) // TILE)
+
+    def draw_tiles(self, tiles, frames: int = 1) -> None:
+        """`frames` extra frames of the listed 64x64 tiles (row-major tile
+        indices, distinct) into the counted extra images; the image, the
+        moments and stats()['frame_index'] are not touched (no host wait)."""
+        import numpy as np
+        t = np.ascontiguousarray(tiles, np.uint32).reshape(-1)
+        _check(lib().mrt_renderer_draw_tiles(self._h, ctypes.c_void_p(t.ctypes.data), t.size, frames),
+               "mrt_renderer_draw_tiles")
+
+    def refine(self, frames: int, tiles: int, params: "AdaptiveParams | None" = None) -> None:
+        """One adaptive pass: the variance plane of what has been accumulated,
+        a priority per tile, the `tiles` tiles of highest priority chosen on
+        the device, and `frames` extra frames of them (no host wait); params
+        None = AdaptiveParams.default()."""
+        _check(lib().mrt_renderer_refine(self._h, frames, tiles, ctypes.byref(params) if params is not None else None),
+               "mrt_renderer_refine")
+
+    def _read_extra(self, fn, what):
+        import numpy as np
+        img = np.zeros((self.height, self.width, 4), np.float32)
+        _check(fn(self._h, ctypes.c_void_p(img.ctypes.data), img.size), what)
+        return img
+
+    def read_extra(self):
+        """[H, W, 4] float32 extra image E: (r, g, b, extra samples), row 0 = bottom."""
+        return self._read_extra(lib().mrt_renderer_read_extra, "mrt_renderer_read_extra")
+
+    def read_extra_moments(self):
+        """[H, W, 4] float32 extra moments EM: (mean l, mean l*l, 0, extra samples)."""
+        return self._read_extra(lib().mrt_renderer_read_extra_moments, "mrt_renderer_read_extra_moments")
+
+    def read_tile_priority(self):
+        """float32 priorities of the last refine, one per tile (row-major)."""
+        import numpy as np
+        p = np.zeros(self.tile_count(), np.float32)
+        _check(lib().mrt_renderer_read_tile_priority(self._h, ctypes.c_void_p(p.ctypes.data), p.size),
+               "mrt_renderer_read_tile_priority")
+        return p
+
+    def read_tile_list(self):
+        """uint32 tile indices the last refine or draw_tiles drew, in rank order."""
+        import numpy as np
+        t = np.zeros(self.tile_count(), np.uint32)
+        n = ctypes.c_uint32()
+        _check(lib().mrt_renderer_read_tile_list(self._h, ctypes.c_void_p(t.ctypes.data), t.size, ctypes.byref(n)),
+               "mrt_renderer_read_tile_list")
+        return t[:n.value].copy()
+
+    def refine_stats(self) -> dict:
+        s = RefineStats()
+        _check(lib().mrt_renderer_refine_stats(self._h, ctypes.byref(s)), "mrt_renderer_refine_stats")
+        return s.as_dict()
+
     # ---- multi-GPU exchange (include/mrt.h: mrt_renderer_exchange) ----
     def exchange(self, comm: "Comm", mode: int = EXCHANGE_GATHER) -> None:
         """Enqueue the image exchange of this shard renderer on its stream:
@@ -862,6 +963,31 @@ def debug_denoise_variance_step(image_ptr: int, variance_ptr: int, n_ptr: int, p
     _check(lib().mrt_debug_denoise_variance_step(image_ptr, variance_ptr, n_ptr, p_ptr, out_ptr, width, height,
                                                  ctypes.byref(params), step_log2, path, stream),
            "mrt_debug_denoise_variance_step")
+    if sync:
+        synchronize(stream)
+
+
+def counted_merge(a_ptr: int, b_ptr: int, out_ptr: int, width: int, height: int, precise=True, stream=None,
+                  sync=True) -> None:
+    """Merge two counted images (mrt_counted_merge); out_ptr may be a_ptr."""
+    _check(lib().mrt_counted_merge(a_ptr, b_ptr, out_ptr, width, height, _flags(precise), stream), "mrt_counted_merge")
+    if sync:
+        synchronize(stream)
+
+
+def tile_priority(image_ptr: int, variance_ptr: int, n_ptr: int, priority_ptr: int, width: int, height: int,
+                  params: "AdaptiveParams | None", precise=True, stream=None, sync=True) -> None:
+    """One float per 64x64 tile: the relative squared error a further sample buys (mrt_tile_priority)."""
+    _check(lib().mrt_tile_priority(image_ptr, variance_ptr, n_ptr, priority_ptr, width, height,
+                                   ctypes.byref(params) if params is not None else None, _flags(precise), stream),
+           "mrt_tile_priority")
+    if sync:
+        synchronize(stream)
+
+
+def tile_select(priority_ptr: int, tiles: int, count: int, list_ptr: int, stream=None, sync=True) -> None:
+    """The `count` tiles of highest priority, uint32, in rank order (mrt_tile_select)."""
+    _check(lib().mrt_tile_select(priority_ptr, tiles, count, list_ptr, stream), "mrt_tile_select")
     if sync:
         synchronize(stream)
 
