@@ -473,6 +473,56 @@ int mrt_tile_priority(const float* image, const float* variance, const float* gu
  * builds.  count == 0, count > tiles, tiles > 16384 (an 8192 x 8192 frame), or
  * list overlapping priority, is MRT_ERR_INVALID. */
 int mrt_tile_select(const float* priority, uint32_t tiles, uint32_t count, uint32_t* list, void* stream);
+/* The error estimate of a stop rule (mrt_renderer_converge below; DESIGN.md
+ * §2.1r).  A pixel COUNTS under mrt_tile_priority's conditions — inside the
+ * image, word_p < 0x80000000, image[p].rgb finite — and its term is
+ * mrt_tile_priority's, v_p / (l_p l_p + eps^2): the relative squared error of
+ * the pixel's mean.  pixels[t] (uint32 per tile) = the number of the tile's
+ * counted pixels; mean_error[t] (float per tile) = the sum of their terms /
+ * pixels[t], or 0 when there are none (the sum in any order: the kernel adds
+ * the float terms and divides in double and rounds once, in both builds).  The
+ * estimate is only as good as l_p: with a noisy
+ * image below the variance it understates the error severalfold (§2.1r), so
+ * `image` is meant to be a denoised one.  The inputs are only read.
+ * params == NULL, or an output overlapping an input or the other output, is
+ * MRT_ERR_INVALID. */
+int mrt_tile_error(const float* image, const float* variance, const float* guide_n, float* mean_error,
+                   uint32_t* pixels, uint32_t width, uint32_t height, const mrt_adaptive_params* params,
+                   uint32_t flags, void* stream);
+typedef struct mrt_error_summary {
+  float frame_error;       /* sum of key(t) pixels[t] / sum of pixels[t] over the tiles with pixels[t] > 0 (0 if none;
+                              the sums in any order, every operation rounded, the same in both builds) */
+  float max_tile_error;    /* the largest key */
+  uint32_t tiles_above;    /* A */
+  uint32_t tiles_listed;   /* min(A, max_count) */
+  uint32_t tiles_counted;  /* tiles with pixels[t] > 0 */
+  uint32_t pixels;         /* sum of pixels[t] */
+  uint32_t reserved[2];    /* 0 */
+} mrt_error_summary;
+/* key(t) = mean_error[t] if it is finite and > 0 and pixels[t] > 0, else 0.
+ * Tile t is ABOVE iff key(t) > threshold (strictly); A is the number of above
+ * tiles.  list[r] (uint32), r < min(A, max_count), = the above tile of rank r
+ * under (key descending, tile index ascending); entries beyond that are not
+ * written.  Exact given the inputs, and the same in both builds.  `summary`
+ * (device memory) is written in full.  The inputs are only read.  A threshold
+ * that is not finite or is negative, tiles == 0, tiles > 16384, max_count == 0,
+ * max_count > tiles, or any overlap among the four buffers, is MRT_ERR_INVALID. */
+int mrt_tile_threshold(const float* mean_error, const uint32_t* pixels, uint32_t tiles, float threshold,
+                       uint32_t max_count, uint32_t* list, mrt_error_summary* summary, void* stream);
+typedef struct mrt_converge_params {
+  float target_error;         /* > 0: a tile is done when its mean error is not above it */
+  uint32_t frames_per_pass;   /* >= 1: extra frames a pass gives every tile it draws */
+  uint32_t max_passes;        /* >= 1: draws at most */
+  uint32_t max_tiles;         /* tiles a pass draws at most; 0 = no cap */
+  uint64_t max_tile_frames;   /* tile-frames the whole call may draw; 0 = no budget */
+  float luminance_floor;      /* > 0: eps of the estimate */
+} mrt_converge_params;
+/* Host only.  target_error = 1e-3, frames_per_pass = 8, max_passes = 64,
+ * max_tiles = 0, max_tile_frames = 0, luminance_floor = 0.01. */
+int mrt_converge_params_default(mrt_converge_params* out);
+/* Host only.  MRT_ERR_INVALID (with a message naming the field) for a field
+ * outside the ranges above, a non-finite one included. */
+int mrt_converge_params_check(const mrt_converge_params* p);
 
 /* ---- renderer (B-1) ------------------------------------------------------ */
 typedef struct mrt_renderer_desc {
@@ -731,6 +781,54 @@ typedef struct mrt_refine_stats {   /* cumulative since create; never reset */
                               list is next read back: mrt_renderer_refine_stats synchronises */
 } mrt_refine_stats;
 int mrt_renderer_refine_stats(mrt_renderer* r, mrt_refine_stats* stats);
+/* Sampling to a target error.  mrt_renderer_error estimates
+ * and draws nothing: mrt_renderer_denoise_variance(r, svgf) (NULL = its
+ * default); mrt_tile_error(the denoised buffer, the variance plane that call
+ * fed to the filter, the guide normals) with eps = luminance_floor (0 = 0.01)
+ * into two per-tile planes the renderer owns; mrt_tile_threshold(threshold,
+ * max_count = the frame's tile count) into the renderer's tile list, which
+ * then holds out->tiles_listed tiles (read_tile_list: MRT_ERR_STATE while that
+ * is 0); and the summary copied to pinned host memory and WAITED FOR — the one
+ * host wait of the call, which therefore also waits for every draw enqueued
+ * before it.  The resolved, variance and denoised buffers are left as
+ * denoise_variance leaves them.  Preconditions: those of mrt_renderer_refine
+ * (MRT_FLAG_MOMENTS, not sharded, no MRT_FLAG_STATIC_NOISE, not the per-bounce
+ * kernel), more than 16384 tiles is MRT_ERR_INVALID, and MRT_ERR_STATE when
+ * fewer than svgf.min_frames frames have been accumulated and there is no
+ * valid history: below min_frames the variance is the spatial estimate, which
+ * is off by a factor of 8 to 30 as an error estimate.  Extra samples do not
+ * count towards that. */
+int mrt_renderer_error(mrt_renderer* r, const mrt_svgf_params* svgf, float luminance_floor, float threshold,
+                       mrt_error_summary* out);
+/* The two planes of the last mrt_renderer_error or _converge (one float and one
+ * uint32 per tile; `count` = the capacity of each); synchronises.
+ * MRT_ERR_STATE before one has run at the current size. */
+int mrt_renderer_read_tile_error(mrt_renderer* r, float* mean_error, uint32_t* pixels, size_t count);
+typedef struct mrt_converge_result {
+  uint32_t converged;           /* 1: the last estimate found no tile above the target */
+  uint32_t passes;              /* draws made */
+  uint64_t tile_frames;         /* sum over them of tiles x frames_per_pass */
+  mrt_error_summary first, last;   /* the first and the last estimate (the same one when passes == 0) */
+} mrt_converge_result;
+/* Repeats: estimate as mrt_renderer_error with the default svgf parameters,
+ * eps = params->luminance_floor and threshold = params->target_error;
+ * n = min(tiles_above, max_tiles or the tile count, floor(what is left of
+ * max_tile_frames / frames_per_pass)); tiles_above == 0 stops with
+ * converged = 1; otherwise n == 0 or max_passes draws made stops with
+ * converged = 0; otherwise frames_per_pass extra frames of the first n listed
+ * tiles (the n worst), from the device list exactly as mrt_renderer_refine
+ * hands its list over: E, EM, the refine noise schedule and mrt_refine_stats
+ * behave as documented there, and the accumulation image, the moments image and
+ * mrt_stats.frame_index, .paths and .draws are never touched.  The call always
+ * ends on an estimate, so the resolved, variance and denoised buffers are
+ * current for everything drawn and read_denoised after it is the finished
+ * picture.  One host wait per estimate.  params NULL =
+ * mrt_converge_params_default; a failed parameter or state check changes
+ * nothing.  The rule looks at its own estimate: a tile whose estimate happens
+ * to fall low stops early and is not looked at again, so the error of the
+ * tiles it declares done is, on average, above what it reports (optional
+ * stopping; stated, not corrected). */
+int mrt_renderer_converge(mrt_renderer* r, const mrt_converge_params* params, mrt_converge_result* out);
 int mrt_renderer_stats(const mrt_renderer* r, mrt_stats* stats);
 int mrt_renderer_destroy(mrt_renderer* r);
 

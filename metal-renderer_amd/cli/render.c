@@ -32,6 +32,17 @@
  *                   [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]
  *                   [--orbit-steps K --orbit-degrees D]
  *                   [--refine-passes P --refine-frames F --refine-tiles K]
+ *                   [--target-error E [--converge-frames F] [--converge-max-passes P]
+ *                    [--converge-budget N]]
+ * --target-error E (single rank only, not with --refine-*; the other three
+ * need it): sampling to a target error.  The renderer accumulates luminance
+ * moments, and after the draws mrt_renderer_converge with target_error = E,
+ * frames_per_pass = F, max_passes = P and max_tile_frames = N (each the default
+ * of mrt_converge_params_default when not given) draws extra frames of the
+ * tiles whose estimated relative squared error is above E until none is.  One
+ * line on stdout reports it: passes, tile-frames, the first and the last
+ * frame_error, and converged.  --out then receives what --denoise-variance
+ * gives, which holds the extra samples.
  * --refine-passes P (single rank only; --refine-frames F, default 1, and
  * --refine-tiles K, default a quarter of the frame's 64x64 tiles, imply it with
  * P = 1): adaptive sampling.  The renderer accumulates luminance moments, and
@@ -101,6 +112,11 @@ typedef struct {
   /* adaptive sampling (mrt_renderer_refine) */
   uint32_t refine_passes, refine_frames, refine_tiles;
   int refine_set;
+  /* sampling to a target error (mrt_renderer_converge) */
+  int target_set, converge_set;
+  float target_error;
+  uint32_t converge_frames, converge_max_passes;
+  uint64_t converge_budget;
   uint32_t orbit_steps;
   int orbit_degrees_set;
   float orbit_degrees;
@@ -129,12 +145,16 @@ static void usage(void) {
           "                  [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]\n"
           "                  [--orbit-steps K --orbit-degrees D]\n"
           "                  [--refine-passes P --refine-frames F --refine-tiles K]\n"
+          "                  [--target-error E [--converge-frames F] [--converge-max-passes P] [--converge-budget N]]\n"
           "  --orbit-steps K --orbit-degrees D (one rank): after the first --spp frames, K times: turn the eye by D\n"
           "  degrees about the world's vertical (y) axis through the target, whatever --up says, move the camera\n"
           "  keeping the accumulated history, draw --spp frames; --out gets the resolved image.  --orbit-degrees\n"
           "  alone is an error.\n"
           "  --refine-passes P --refine-frames F --refine-tiles K (one rank): after the draws, P times F extra frames\n"
-          "  of the K 64x64 tiles whose variance says they need them most; --out gets an image that holds them.\n");
+          "  of the K 64x64 tiles whose variance says they need them most; --out gets an image that holds them.\n"
+          "  --target-error E (one rank, not with --refine-*): after the draws, F extra frames per pass of the tiles\n"
+          "  whose estimated relative squared error is above E, until none is, P passes are drawn or N tile-frames\n"
+          "  are spent; prints one line about it; --out gets the --denoise-variance image.\n");
 }
 
 /* --scene cornellbox -> <dir of this executable>/../scenes/cornellbox.obj */
@@ -188,6 +208,10 @@ static int parse(int argc, char** argv, options* o) {
     else if (VAL("--refine-passes")) { o->refine_passes = (uint32_t)strtoul(v, NULL, 0); o->refine_set = 1; }
     else if (VAL("--refine-frames")) { o->refine_frames = (uint32_t)strtoul(v, NULL, 0); o->refine_set = 1; }
     else if (VAL("--refine-tiles")) { o->refine_tiles = (uint32_t)strtoul(v, NULL, 0); o->refine_set = 1; }
+    else if (VAL("--target-error")) { o->target_error = strtof(v, NULL); o->target_set = 1; }
+    else if (VAL("--converge-frames")) { o->converge_frames = (uint32_t)strtoul(v, NULL, 0); o->converge_set = 1; }
+    else if (VAL("--converge-max-passes")) { o->converge_max_passes = (uint32_t)strtoul(v, NULL, 0); o->converge_set = 1; }
+    else if (VAL("--converge-budget")) { o->converge_budget = strtoull(v, NULL, 0); o->converge_set = 1; }
     else if (VAL("--svgf-iterations")) { o->svgf_iterations = (uint32_t)strtoul(v, NULL, 0); o->denoise_variance = o->svgf_iterations_set = 1; }
     else if (VAL("--svgf-sigma-luminance")) { o->svgf_sigma_luminance = strtof(v, NULL); o->denoise_variance = o->svgf_sigma_set = 1; }
     else if (strcmp(a, "--denoise") == 0) o->denoise = 1;
@@ -233,6 +257,25 @@ static int parse(int argc, char** argv, options* o) {
       const uint32_t tiles = ((o->width + 63) / 64) * ((o->height + 63) / 64);
       o->refine_tiles = tiles / 4 ? tiles / 4 : 1;
     }
+  }
+  if (o->converge_set && !o->target_set) {
+    fprintf(stderr, "mrt_render: --converge-frames, --converge-max-passes and --converge-budget need --target-error E\n");
+    return -1;
+  }
+  if (o->target_set) {
+    if (o->gpus > 1) {
+      fprintf(stderr, "mrt_render: --target-error is single rank only (a sharded renderer keeps no moments)\n");
+      return -1;
+    }
+    if (o->refine_set) {
+      fprintf(stderr, "mrt_render: --target-error and --refine-passes exclude each other\n");
+      return -1;
+    }
+    if (o->denoise) {
+      fprintf(stderr, "mrt_render: --target-error and --denoise exclude each other\n");
+      return -1;
+    }
+    o->denoise_variance = 1;   /* the image it saves */
   }
   if (o->denoise_variance || o->refine_set) o->flags |= MRT_FLAG_MOMENTS;
   return 0;
@@ -352,6 +395,19 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
   }
   for (uint32_t k = 0; k < o->refine_passes; ++k)   /* (single rank) nor does this */
     if (mrt_renderer_refine(r, o->refine_frames, o->refine_tiles, NULL)) return die("mrt_renderer_refine");
+  if (o->target_set) {   /* (single rank) this waits for the GPU once per estimate */
+    mrt_converge_params cp;
+    mrt_converge_result cr;
+    if (mrt_converge_params_default(&cp)) return die("mrt_converge_params_default");
+    cp.target_error = o->target_error;
+    if (o->converge_frames) cp.frames_per_pass = o->converge_frames;
+    if (o->converge_max_passes) cp.max_passes = o->converge_max_passes;
+    cp.max_tile_frames = o->converge_budget;
+    if (mrt_renderer_converge(r, &cp, &cr)) return die("mrt_renderer_converge");
+    printf("{\"converge_passes\": %u, \"tile_frames\": %" PRIu64 ", \"first_frame_error\": %.9g, "
+           "\"last_frame_error\": %.9g, \"converged\": %u}\n",
+           cr.passes, cr.tile_frames, (double)cr.first.frame_error, (double)cr.last.frame_error, cr.converged);
+  }
   if (rccl) {
     if (mrt_renderer_exchange(r, comm, MRT_EXCHANGE_GATHER)) return die("mrt_renderer_exchange");
   } else if (N > 1) {

@@ -370,6 +370,12 @@ struct mrt_renderer {
   bool priority_current = false;   // a refine has run at the current size
   uint32_t list_count = 0;         // entries of tile_list the last refine / draw_tiles drew
   mrt_refine_stats refine_stats{};
+  // sampling to a target error (mrt_renderer_error / _converge): the two
+  // per-tile planes of mrt_tile_error, the device summary and its pinned host
+  // copy; made at the first estimate, the planes re-made by resize
+  mrt::host::DevBuf tile_error, tile_pixels, error_summary;
+  mrt_error_summary* summary_host = nullptr;
+  bool tile_error_current = false;   // an estimate has run at the current size
   struct DisplaySlot {          // mrt_renderer_display_enqueue / _map: pinned copies of the blit
     float* host = nullptr;
     size_t floats = 0;

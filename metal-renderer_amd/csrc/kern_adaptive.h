@@ -1,7 +1,8 @@
 // kern_adaptive.h — adaptive sampling (include/mrt.h "adaptive sampling",
 // DESIGN.md §2.1q): the counted accumulate of a refine draw, the merge of two
-// counted images, the per-tile priority from the variance plane and the
-// selection of the highest-priority tiles.  The render kernels read the tile
+// counted images, the per-tile priority from the variance plane, the
+// selection of the highest-priority tiles, and the error estimate of a stop
+// rule (§2.1r): the per-tile mean relative error and the tiles above a threshold.  The render kernels read the tile
 // list through slot_pixel_l (dev_shade.h).
 #pragma once
 #include "kern_stage.h"
@@ -90,34 +91,79 @@ __global__ __launch_bounds__(kBlock) void counted_merge_kernel(MergeArgs a) {
   a.out[i] = o;
 }
 
-// mrt_tile_priority: one block per tile, a wave per row of 64 pixels (16 rows
-// each); the lanes' partial sums are reduced through the wave (DPP shuffles),
-// the four waves' through LDS.  Rows and columns outside the image are skipped.
+// a / b correctly rounded in both builds (the fast build's own division is not):
+// the double quotient of two floats rounds to the float quotient (53 >= 2 * 24 + 2)
+__device__ __forceinline__ float ieee_div(float a, float b) { return (float)((double)a / (double)b); }
+
+// mrt_tile_priority and mrt_tile_error: one block per tile, a wave per row of
+// 64 pixels (16 rows each); the lanes' partial sums are reduced through the
+// wave (DPP shuffles), the four waves' through LDS.  Rows and columns outside
+// the image are skipped.
+// MRT_TILE_LANE_TERMS is the part the two kernels share: a lane's walk down its
+// column of tile blockIdx.x, with ADD executed on the `term` of every pixel that
+// counts.  A macro and not a function: behind a function boundary, however
+// inlined, the compiler splits the pixel's rgb load in two and allocates
+// registers anew, and tile_priority_kernel's code is to stay what it was, to the
+// instruction.
+#define MRT_TILE_LANE_TERMS(a, ADD)                                     \
+  const uint32_t t = blockIdx.x;                                        \
+  const uint32_t ty = t / a.tiles_x, tx = t - ty * a.tiles_x;           \
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;     \
+  const uint32_t x = tx * kTile + lane;                                 \
+  if (x < a.width) {                                                    \
+    for (uint32_t r = wave; r < kTile; r += kBlock / 64) {              \
+      const uint32_t y = ty * kTile + r;                                \
+      if (y >= a.height) break;                                         \
+      const size_t i = (size_t)y * a.width + x;                         \
+      if (fbits(a.guide_n[i].w) >= 0x80000000u) continue;               \
+      const float4 c = a.image[i];                                      \
+      if (!finite_rgb(c)) continue;                                     \
+      const float l = luminance(mk(c));                                 \
+      const float term = m_div(a.variance[i], l * l + a.eps2);          \
+      ADD;                                                              \
+    }                                                                   \
+  }
+
 __global__ __launch_bounds__(kBlock) void tile_priority_kernel(PriorityArgs a) {
   __shared__ float s_part[kBlock / 64];
-  const uint32_t t = blockIdx.x;
-  const uint32_t ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t x = tx * kTile + lane;
   float sum = 0.0f;
-  if (x < a.width) {
-    for (uint32_t r = wave; r < kTile; r += kBlock / 64) {
-      const uint32_t y = ty * kTile + r;
-      if (y >= a.height) break;
-      const size_t i = (size_t)y * a.width + x;
-      if (fbits(a.guide_n[i].w) >= 0x80000000u) continue;
-      const float4 c = a.image[i];
-      if (!finite_rgb(c)) continue;
-      const float l = luminance(mk(c));
-      sum += m_div(a.variance[i], l * l + a.eps2);
-    }
-  }
+  MRT_TILE_LANE_TERMS(a, sum += term)
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
   if (lane == 0) s_part[wave] = sum;
   __syncthreads();
   if (threadIdx.x == 0) a.priority[t] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
 }
+
+// mrt_tile_error: the same terms, counted, and summed in double (the order is
+// free, so no order is left to matter: up to 4096 float terms add up exactly
+// enough that the mean, args.p.priority[t], is the float nearest to that of the
+// terms; the double adds of a lane hide behind its loads)
+__global__ __launch_bounds__(kBlock) void tile_error_kernel(ErrorArgs args) {
+  __shared__ double s_part[kBlock / 64];
+  __shared__ uint32_t s_count[kBlock / 64];
+  const PriorityArgs& a = args.p;
+  double sum = 0.0;
+  uint32_t counted = 0;
+  MRT_TILE_LANE_TERMS(a, (sum += (double)term, counted += 1u))
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    sum += __shfl_xor(sum, o);
+    counted += __shfl_xor(counted, o);
+  }
+  if (lane == 0) {
+    s_part[wave] = sum;
+    s_count[wave] = counted;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double total = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+    const uint32_t n = (s_count[0] + s_count[1]) + (s_count[2] + s_count[3]);
+    a.priority[t] = n ? (float)(total / (double)n) : 0.0f;
+    args.pixels[t] = n;
+  }
+}
+#undef MRT_TILE_LANE_TERMS
 
 // mrt_tile_select: rank by counting.  Tile t's rank is the number of tiles
 // that beat it under (priority descending, tile index ascending); a priority
@@ -146,6 +192,79 @@ __global__ __launch_bounds__(kBlock) void tile_select_kernel(const float* priori
     }
   }
   if (t < tiles && rank < count) list[rank] = t;
+}
+
+// mrt_tile_threshold: tile_select_kernel's ranking over key(t) = the mean error
+// of a tile with counted pixels, where only a tile above the threshold is
+// listed: every such tile outranks every other, so the above tiles hold the
+// ranks 0 .. A-1 and list[r] still has one writer.  Block 0, which stages every
+// tile like the others, also sums the summary from what it stages (a thread
+// the tiles u = threadIdx.x mod 256, then wave and LDS as above) and writes it
+// from thread 0 with ordinary stores.
+__device__ __forceinline__ float threshold_key(float e, uint32_t pixels) { return pixels ? select_key(e) : 0.0f; }
+__global__ __launch_bounds__(kBlock) void tile_threshold_kernel(ThresholdArgs a) {
+  __shared__ float s_key[kBlock];
+  __shared__ float s_f[2][kBlock / 64];
+  __shared__ uint32_t s_u[3][kBlock / 64];
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  const float mine = t < a.tiles ? threshold_key(a.mean_error[t], a.pixels[t]) : 0.0f;
+  const bool first = blockIdx.x == 0;
+  uint32_t rank = 0;
+  float weighted = 0.0f, worst = 0.0f;
+  uint32_t above = 0, counted = 0, pixels = 0;
+  for (uint32_t base = 0; base < a.tiles; base += kBlock) {
+    const uint32_t u = base + threadIdx.x;
+    const uint32_t n_u = u < a.tiles ? a.pixels[u] : 0u;
+    const float k_u = u < a.tiles ? threshold_key(a.mean_error[u], n_u) : 0.0f;
+    __syncthreads();
+    s_key[threadIdx.x] = k_u;
+    __syncthreads();
+    if (first) {
+      weighted += (float)((double)k_u * (double)n_u);   // the rounded product, never contracted into the sum
+      worst = fmaxf(worst, k_u);
+      above += k_u > a.threshold ? 1u : 0u;
+      counted += n_u ? 1u : 0u;
+      pixels += n_u;
+    }
+    const uint32_t n = min((uint32_t)kBlock, a.tiles - base);
+    for (uint32_t k = 0; k < n; ++k) {
+      const float other = s_key[k];   // an LDS broadcast
+      rank += (other > mine || (other == mine && base + k < t)) ? 1u : 0u;
+    }
+  }
+  if (t < a.tiles && mine > a.threshold && rank < a.max_count) a.list[rank] = t;
+  if (!first) return;   // (the whole block)
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    weighted += __shfl_xor(weighted, o);
+    worst = fmaxf(worst, __shfl_xor(worst, o));
+    above += __shfl_xor(above, o);
+    counted += __shfl_xor(counted, o);
+    pixels += __shfl_xor(pixels, o);
+  }
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    s_f[0][wave] = weighted;
+    s_f[1][wave] = worst;
+    s_u[0][wave] = above;
+    s_u[1][wave] = counted;
+    s_u[2][wave] = pixels;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float w = (s_f[0][0] + s_f[0][1]) + (s_f[0][2] + s_f[0][3]);
+    const uint32_t A = (s_u[0][0] + s_u[0][1]) + (s_u[0][2] + s_u[0][3]);
+    const uint32_t px = (s_u[2][0] + s_u[2][1]) + (s_u[2][2] + s_u[2][3]);
+    ErrorSummary o;
+    o.frame_error = px ? ieee_div(w, float(px)) : 0.0f;
+    o.max_tile_error = fmaxf(fmaxf(s_f[1][0], s_f[1][1]), fmaxf(s_f[1][2], s_f[1][3]));
+    o.tiles_above = A;
+    o.tiles_listed = min(A, a.max_count);
+    o.tiles_counted = (s_u[1][0] + s_u[1][1]) + (s_u[1][2] + s_u[1][3]);
+    o.pixels = px;
+    o.reserved[0] = o.reserved[1] = 0u;
+    *a.summary = o;
+  }
 }
 
 }  // namespace

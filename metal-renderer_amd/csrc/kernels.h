@@ -205,6 +205,29 @@ struct PriorityArgs {
 
 constexpr uint32_t kMaxSelectTiles = 16384;   // mrt_tile_select: the tiles of an 8192 x 8192 frame
 
+// mrt_tile_error: mrt_tile_priority's sum over the same pixels, as a mean with its count
+struct ErrorArgs {
+  PriorityArgs p;    // p.priority = mean_error
+  uint32_t* pixels;  // one count per tile
+};
+
+// mrt_error_summary (include/mrt.h), field for field
+struct ErrorSummary {
+  float frame_error, max_tile_error;
+  uint32_t tiles_above, tiles_listed, tiles_counted, pixels;
+  uint32_t reserved[2];
+};
+
+// mrt_tile_threshold
+struct ThresholdArgs {
+  const float* mean_error;
+  const uint32_t* pixels;
+  uint32_t* list;
+  ErrorSummary* summary;
+  uint32_t tiles, max_count;
+  float threshold;
+};
+
 constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_shade flags
 
 #define MRT_DECLARE_LAUNCHERS(NS)                                                                         \
@@ -260,6 +283,10 @@ constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_sha
      code in both builds; tiles <= kMaxSelectTiles */                                                     \
   hipError_t launch_tile_select(const float* priority, uint32_t tiles, uint32_t count, uint32_t* list,    \
                                 hipStream_t s);                                                           \
+  hipError_t launch_tile_error(const ErrorArgs& a, uint32_t tiles, hipStream_t s);                        \
+  /* the tiles whose key exceeds a.threshold, ranked as launch_tile_select ranks, and the summary; exact, \
+     the same code in both builds; a.tiles <= kMaxSelectTiles */                                          \
+  hipError_t launch_tile_threshold(const ThresholdArgs& a, hipStream_t s);                                \
   /* blitFragment (Shaders.metal:33-70): tone map / sRGB / golden comparison of the RGBA32F image */     \
   hipError_t launch_display(const float4* image, const float4* reference, float4* out, uint32_t n,        \
                             uint32_t flags, float compare_scale, hipStream_t s);                          \

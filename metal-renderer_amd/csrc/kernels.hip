@@ -362,6 +362,18 @@ hipError_t launch_tile_select(const float* priority, uint32_t tiles, uint32_t co
   return hipGetLastError();
 }
 
+hipError_t launch_tile_error(const ErrorArgs& a, uint32_t tiles, hipStream_t s) {
+  if (tiles == 0 || a.p.tiles_x == 0) return hipErrorInvalidValue;
+  tile_error_kernel<<<dim3(tiles), dim3(kBlock), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_threshold(const ThresholdArgs& a, hipStream_t s) {
+  if (a.tiles == 0 || a.tiles > kMaxSelectTiles || a.max_count == 0 || a.max_count > a.tiles) return hipErrorInvalidValue;
+  tile_threshold_kernel<<<dim3(blocks_for(a.tiles)), dim3(kBlock), 0, s>>>(a);
+  return hipGetLastError();
+}
+
 hipError_t launch_moments(uint32_t W, uint32_t H, uint32_t frame_index, const RefRay* rays, float* moments,
                           hipStream_t s) {
   moments_kernel<<<dim3(blocks_for(W * H)), dim3(kBlock), 0, s>>>(W, H, frame_index, rays,

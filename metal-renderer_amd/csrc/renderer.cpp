@@ -948,6 +948,7 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   r->history_valid = r->resolved_current = false;
   r->variance_current = false;
   r->extras_current = r->extras_valid = r->priority_current = false;   // re-made (and zeroed) by the next refine / draw_tiles
+  r->tile_error_current = false;
   r->list_count = 0;
   if (r->denoised.p) {     // a renderer that has denoised keeps its buffers, at the new size
     const size_t bytes = (size_t)width * height * 16;
@@ -1411,6 +1412,124 @@ int mrt_renderer_refine_stats(mrt_renderer* r, mrt_refine_stats* stats) {
   return MRT_OK;
 }
 
+// ---- sampling to a target error (include/mrt.h: mrt_renderer_converge) -------
+namespace {
+// everything an estimate checks, before it changes anything
+int estimate_usable(mrt_renderer* r, const char* what, const mrt_svgf_params& sp, const mrt_adaptive_params& ap,
+                    float threshold) {
+  int rc = refine_usable(r, what);
+  if (rc) return rc;
+  if (r->tiles_x * r->tiles_y > mrt::kMaxSelectTiles)
+    return fail(MRT_ERR_INVALID, std::string(what) + ": more than 16384 tiles");
+  if (!std::isfinite(threshold) || threshold < 0.0f)
+    return fail(MRT_ERR_INVALID, std::string(what) + ": the threshold must be finite and not negative");
+  rc = mrt_svgf_params_check(&sp);
+  if (rc) return rc;
+  rc = mrt_adaptive_params_check(&ap);
+  if (rc) return rc;
+  if (r->frame_index < sp.min_frames && !r->history_valid)
+    return fail(MRT_ERR_STATE, std::string(what) + ": fewer than min_frames frames accumulated and no valid history");
+  return MRT_OK;
+}
+
+// one estimate (estimate_usable has passed): denoise_variance, the per-tile
+// error, the tiles above `threshold` into the tile list, and the summary
+// brought to the host — the one host wait
+int estimate(mrt_renderer* r, const mrt_svgf_params& sp, const mrt_adaptive_params& ap, float threshold,
+             mrt_error_summary* out) {
+  const uint32_t W = r->desc.width, H = r->desc.height, T = r->tiles_x * r->tiles_y;
+  int rc = ensure_extras(r);   // (the tile list lives with E and EM)
+  if (rc) return rc;
+  for (DevBuf* b : {&r->tile_error, &r->tile_pixels})
+    if (b->bytes != (size_t)T * 4 || !b->p) {
+      r->tile_error_current = false;
+      HIP_TRY(b->alloc((size_t)T * 4));
+    }
+  if (!r->error_summary.p) HIP_TRY(r->error_summary.alloc(sizeof(mrt_error_summary)));
+  if (!r->summary_host)
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->summary_host), sizeof(mrt_error_summary), hipHostMallocDefault));
+  rc = mrt_renderer_denoise_variance(r, &sp);
+  if (rc) return rc;
+  rc = mrt_tile_error(r->denoised.as<float>(), r->variance.as<float>(), r->guide_n.as<float>(),
+                      r->tile_error.as<float>(), r->tile_pixels.as<uint32_t>(), W, H, &ap,
+                      r->desc.flags & MRT_FLAG_PRECISE, r->stream);
+  if (rc) return rc;
+  r->tile_error_current = true;
+  r->list_count = 0;   // the list is rewritten: nothing of it is known until the summary is back
+  rc = mrt_tile_threshold(r->tile_error.as<float>(), r->tile_pixels.as<uint32_t>(), T, threshold, T,
+                          r->tile_list.as<uint32_t>(), r->error_summary.as<mrt_error_summary>(), r->stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(r->summary_host, r->error_summary.p, sizeof(mrt_error_summary), hipMemcpyDeviceToHost, r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  *out = *r->summary_host;
+  r->list_count = out->tiles_listed;
+  return MRT_OK;
+}
+}  // namespace
+
+int mrt_renderer_error(mrt_renderer* r, const mrt_svgf_params* svgf, float luminance_floor, float threshold,
+                       mrt_error_summary* out) {
+  if (!r || !out) return fail(MRT_ERR_INVALID, "null argument");
+  mrt_svgf_params sp;
+  if (svgf) sp = *svgf;
+  else (void)mrt_svgf_params_default(&sp);
+  mrt_adaptive_params ap;
+  (void)mrt_adaptive_params_default(&ap);
+  if (luminance_floor != 0.0f) ap.luminance_floor = luminance_floor;
+  const int rc = estimate_usable(r, "mrt_renderer_error", sp, ap, threshold);
+  return rc ? rc : estimate(r, sp, ap, threshold, out);
+}
+
+int mrt_renderer_read_tile_error(mrt_renderer* r, float* mean_error, uint32_t* pixels, size_t count) {
+  if (!r || !mean_error || !pixels) return fail(MRT_ERR_INVALID, "null argument");
+  const size_t T = (size_t)r->tiles_x * r->tiles_y;
+  if (count < T) return fail(MRT_ERR_INVALID, "output buffer too small");
+  if (!r->tile_error_current) return fail(MRT_ERR_STATE, "no error estimate has run at the renderer's current size");
+  const int rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(mean_error, r->tile_error.p, T * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(pixels, r->tile_pixels.p, T * 4, hipMemcpyDeviceToHost));
+  return MRT_OK;
+}
+
+int mrt_renderer_converge(mrt_renderer* r, const mrt_converge_params* params, mrt_converge_result* out) {
+  if (!r || !out) return fail(MRT_ERR_INVALID, "null argument");
+  mrt_converge_params p;
+  if (params) p = *params;
+  else (void)mrt_converge_params_default(&p);
+  int rc = mrt_converge_params_check(&p);
+  if (rc) return rc;
+  mrt_svgf_params sp;
+  (void)mrt_svgf_params_default(&sp);
+  mrt_adaptive_params ap;
+  ap.luminance_floor = p.luminance_floor;
+  rc = estimate_usable(r, "mrt_renderer_converge", sp, ap, p.target_error);
+  if (rc) return rc;
+  const uint32_t T = r->tiles_x * r->tiles_y;
+  const uint32_t cap = p.max_tiles ? std::min(p.max_tiles, T) : T;
+  mrt_converge_result res{};
+  for (;;) {
+    mrt_error_summary s;
+    rc = estimate(r, sp, ap, p.target_error, &s);
+    if (rc) return rc;
+    if (res.passes == 0) res.first = s;
+    res.last = s;
+    if (s.tiles_above == 0) {
+      res.converged = 1;
+      break;
+    }
+    uint64_t n = std::min(s.tiles_above, cap);
+    if (p.max_tile_frames) n = std::min<uint64_t>(n, (p.max_tile_frames - res.tile_frames) / p.frames_per_pass);
+    if (n == 0 || res.passes >= p.max_passes) break;
+    rc = draw_extra(r, nullptr, (uint32_t)n, p.frames_per_pass);   // the n worst: the head of the device list
+    if (rc) return rc;
+    res.passes += 1;
+    res.tile_frames += n * p.frames_per_pass;
+  }
+  *out = res;
+  return MRT_OK;
+}
+
 int mrt_renderer_load_reference(mrt_renderer* r, const char* path) {
   if (!r || !path) return fail(MRT_ERR_INVALID, "null argument");
   std::vector<float> img;
@@ -1534,6 +1653,7 @@ int mrt_renderer_destroy(mrt_renderer* r) {
     if (d.host) (void)hipHostFree(d.host);
   }
   if (r->list_ready) (void)hipEventDestroy(r->list_ready);
+  if (r->summary_host) (void)hipHostFree(r->summary_host);
   for (DrawRecord& d : r->draws)
     if (d.list_host) (void)hipHostFree(d.list_host);
   r->refine_noise.reset();

@@ -577,6 +577,93 @@ int mrt_tile_select(const float* priority, uint32_t tiles, uint32_t count, uint3
   return MRT_OK;
 }
 
+namespace {
+struct Span { const void* p; size_t n; };
+bool spans_overlap(const Span& a, const Span& b) {
+  const char* p = (const char*)a.p;
+  const char* q = (const char*)b.p;
+  return p < q + b.n && q < p + a.n;
+}
+}  // namespace
+
+int mrt_tile_error(const float* image, const float* variance, const float* guide_n, float* mean_error, uint32_t* pixels,
+                   uint32_t W, uint32_t H, const mrt_adaptive_params* params, uint32_t flags, void* stream) {
+  if (!image || !variance || !guide_n || !mean_error || !pixels || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_tile_error: bad argument");
+  const int rc = mrt_adaptive_params_check(params);
+  if (rc) return rc;
+  const uint32_t tx = (W + mrt::kTile - 1) / mrt::kTile, ty = (H + mrt::kTile - 1) / mrt::kTile;
+  const size_t bytes = (size_t)W * H * 16, out_bytes = (size_t)tx * ty * 4;
+  const Span in[] = {{image, bytes}, {variance, bytes / 4}, {guide_n, bytes}};
+  const Span out[] = {{mean_error, out_bytes}, {pixels, out_bytes}};
+  for (const Span& o : out)
+    for (const Span& b : in)
+      if (spans_overlap(o, b)) return fail(MRT_ERR_INVALID, "mrt_tile_error: an output must not overlap an input");
+  if (spans_overlap(out[0], out[1])) return fail(MRT_ERR_INVALID, "mrt_tile_error: mean_error and pixels must not overlap");
+  mrt::ErrorArgs a{};
+  a.p.image = reinterpret_cast<const float4*>(image);
+  a.p.variance = variance;
+  a.p.guide_n = reinterpret_cast<const float4*>(guide_n);
+  a.p.priority = mean_error;
+  a.p.width = W;
+  a.p.height = H;
+  a.p.tiles_x = tx;
+  a.p.eps2 = params->luminance_floor * params->luminance_floor;
+  a.pixels = pixels;
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_tile_error(a, tx * ty, (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+static_assert(sizeof(mrt_error_summary) == sizeof(mrt::ErrorSummary) && sizeof(mrt_error_summary) == 32 &&
+                  offsetof(mrt_error_summary, pixels) == offsetof(mrt::ErrorSummary, pixels),
+              "mrt_error_summary and the kernels' copy of it");
+
+int mrt_tile_threshold(const float* mean_error, const uint32_t* pixels, uint32_t tiles, float threshold,
+                       uint32_t max_count, uint32_t* list, mrt_error_summary* summary, void* stream) {
+  if (!mean_error || !pixels || !list || !summary) return fail(MRT_ERR_INVALID, "mrt_tile_threshold: null argument");
+  if (!std::isfinite(threshold) || threshold < 0.0f)
+    return fail(MRT_ERR_INVALID, "mrt_tile_threshold: threshold must be finite and not negative");
+  if (tiles == 0 || tiles > mrt::kMaxSelectTiles || max_count == 0 || max_count > tiles)
+    return fail(MRT_ERR_INVALID, "mrt_tile_threshold: need 1 <= max_count <= tiles <= 16384");
+  const Span b[] = {{mean_error, (size_t)tiles * 4}, {pixels, (size_t)tiles * 4}, {list, (size_t)max_count * 4},
+                    {summary, sizeof(mrt_error_summary)}};
+  for (int i = 0; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j)
+      if (spans_overlap(b[i], b[j])) return fail(MRT_ERR_INVALID, "mrt_tile_threshold: the buffers must not overlap");
+  mrt::ThresholdArgs a{};
+  a.mean_error = mean_error;
+  a.pixels = pixels;
+  a.list = list;
+  a.summary = reinterpret_cast<mrt::ErrorSummary*>(summary);
+  a.tiles = tiles;
+  a.max_count = max_count;
+  a.threshold = threshold;
+  HIP_TRY(mrt::fast::launch_tile_threshold(a, (hipStream_t)stream));   // exact: one code in both builds
+  return MRT_OK;
+}
+
+int mrt_converge_params_default(mrt_converge_params* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_converge_params_default: null params");
+  out->target_error = 1e-3f;
+  out->frames_per_pass = 8;
+  out->max_passes = 64;
+  out->max_tiles = 0;
+  out->max_tile_frames = 0;
+  out->luminance_floor = 0.01f;
+  return MRT_OK;
+}
+
+int mrt_converge_params_check(const mrt_converge_params* p) {
+  if (!p) return fail(MRT_ERR_INVALID, "converge params: null");
+  if (!std::isfinite(p->target_error) || !(p->target_error > 0.0f))
+    return fail(MRT_ERR_INVALID, "converge params: target_error must be finite and positive");
+  if (p->frames_per_pass < 1) return fail(MRT_ERR_INVALID, "converge params: frames_per_pass must be at least 1");
+  if (p->max_passes < 1) return fail(MRT_ERR_INVALID, "converge params: max_passes must be at least 1");
+  if (!std::isfinite(p->luminance_floor) || !(p->luminance_floor > 0.0f))
+    return fail(MRT_ERR_INVALID, "converge params: luminance_floor must be finite and positive");
+  return MRT_OK;
+}
+
 // ---- temporal history (include/mrt.h) --------------------------------------
 int mrt_reproject_params_default(mrt_reproject_params* out) {
   if (!out) return fail(MRT_ERR_INVALID, "mrt_reproject_params_default: null params");

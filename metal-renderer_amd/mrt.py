@@ -267,6 +267,48 @@ class RefineStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ErrorSummary(ctypes.Structure):
+    """mrt_error_summary (include/mrt.h): what mrt_tile_threshold found."""
+    _fields_ = [("frame_error", ctypes.c_float), ("max_tile_error", ctypes.c_float), ("tiles_above", ctypes.c_uint32),
+                ("tiles_listed", ctypes.c_uint32), ("tiles_counted", ctypes.c_uint32), ("pixels", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class ConvergeParams(ctypes.Structure):
+    """mrt_converge_params (include/mrt.h): the stop rule of Renderer.converge."""
+    _fields_ = [("target_error", ctypes.c_float), ("frames_per_pass", ctypes.c_uint32), ("max_passes", ctypes.c_uint32),
+                ("max_tiles", ctypes.c_uint32), ("max_tile_frames", ctypes.c_uint64), ("luminance_floor", ctypes.c_float)]
+
+    @classmethod
+    def default(cls, **fields) -> "ConvergeParams":
+        p = cls()
+        _check(lib().mrt_converge_params_default(ctypes.byref(p)), "mrt_converge_params_default")
+        for k, v in fields.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"ConvergeParams has no field {k}")
+            setattr(p, k, v)
+        return p
+
+    def check(self) -> None:
+        _check(lib().mrt_converge_params_check(ctypes.byref(self)), "mrt_converge_params_check")
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ConvergeResult(ctypes.Structure):
+    """mrt_converge_result (include/mrt.h)."""
+    _fields_ = [("converged", ctypes.c_uint32), ("passes", ctypes.c_uint32), ("tile_frames", ctypes.c_uint64),
+                ("first", ErrorSummary), ("last", ErrorSummary)]
+
+    def as_dict(self):
+        return {"converged": self.converged, "passes": self.passes, "tile_frames": self.tile_frames,
+                "first": self.first.as_dict(), "last": self.last.as_dict()}
+
+
 EXPORTED = [
     "mrt_scene_create", "mrt_scene_info_get", "mrt_scene_export", "mrt_scene_destroy", "mrt_scene_check_bvh",
     "mrt_raygen", "mrt_intersect", "mrt_shade", "mrt_resolve_shadow", "mrt_accumulate",
@@ -299,6 +341,8 @@ EXPORTED = [
     "mrt_tile_select", "mrt_renderer_draw_tiles", "mrt_renderer_refine", "mrt_renderer_read_extra",
     "mrt_renderer_read_extra_moments", "mrt_renderer_read_tile_priority", "mrt_renderer_read_tile_list",
     "mrt_renderer_refine_stats",
+    "mrt_tile_error", "mrt_tile_threshold", "mrt_converge_params_default", "mrt_converge_params_check",
+    "mrt_renderer_error", "mrt_renderer_read_tile_error", "mrt_renderer_converge",
 ]
 
 _lib = None
@@ -433,6 +477,14 @@ def lib() -> ctypes.CDLL:
         "mrt_renderer_read_tile_priority": [vp, vp, ctypes.c_size_t],
         "mrt_renderer_read_tile_list": [vp, vp, ctypes.c_size_t, ctypes.POINTER(u32)],
         "mrt_renderer_refine_stats": [vp, ctypes.POINTER(RefineStats)],
+        "mrt_tile_error": [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(AdaptiveParams), u32, vp],
+        "mrt_tile_threshold": [vp, vp, u32, ctypes.c_float, u32, vp, vp, vp],
+        "mrt_converge_params_default": [ctypes.POINTER(ConvergeParams)],
+        "mrt_converge_params_check": [ctypes.POINTER(ConvergeParams)],
+        "mrt_renderer_error": [vp, ctypes.POINTER(SvgfParams), ctypes.c_float, ctypes.c_float,
+                               ctypes.POINTER(ErrorSummary)],
+        "mrt_renderer_read_tile_error": [vp, vp, vp, ctypes.c_size_t],
+        "mrt_renderer_converge": [vp, ctypes.POINTER(ConvergeParams), ctypes.POINTER(ConvergeResult)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -795,6 +847,40 @@ class Renderer:
         _check(lib().mrt_renderer_refine_stats(self._h, ctypes.byref(s)), "mrt_renderer_refine_stats")
         return s.as_dict()
 
+    # ---- sampling to a target error (include/mrt.h: mrt_renderer_converge) ----
+    def error_estimate(self, threshold: float = 0.0, svgf: "SvgfParams | None" = None,
+                       luminance_floor: float = 0.0) -> dict:
+        """denoise_variance(svgf), then the mean relative squared error per tile
+        with the denoised image below the variance, and the tiles above
+        `threshold` into the tile list; draws nothing.  Returns the summary
+        (ErrorSummary.as_dict()).  Waits for the device once."""
+        s = ErrorSummary()
+        _check(lib().mrt_renderer_error(self._h, ctypes.byref(svgf) if svgf is not None else None, luminance_floor,
+                                        threshold, ctypes.byref(s)), "mrt_renderer_error")
+        return s.as_dict()
+
+    def read_tile_error(self):
+        """(float32 mean error, uint32 counted pixels) per tile of the last error_estimate or converge."""
+        import numpy as np
+        e, n = np.zeros(self.tile_count(), np.float32), np.zeros(self.tile_count(), np.uint32)
+        _check(lib().mrt_renderer_read_tile_error(self._h, ctypes.c_void_p(e.ctypes.data), ctypes.c_void_p(n.ctypes.data),
+                                                  e.size), "mrt_renderer_read_tile_error")
+        return e, n
+
+    def converge(self, params: "ConvergeParams | None" = None, **fields) -> dict:
+        """Estimate, draw params.frames_per_pass extra frames of the tiles
+        above params.target_error, and repeat until none is above it or a limit
+        ends the loop; always ends on an estimate, so read_denoised() is the
+        finished picture.  params None = ConvergeParams.default(**fields).
+        Returns ConvergeResult.as_dict()."""
+        if params is None:
+            params = ConvergeParams.default(**fields)
+        elif fields:
+            raise TypeError("pass either params or fields")
+        res = ConvergeResult()
+        _check(lib().mrt_renderer_converge(self._h, ctypes.byref(params), ctypes.byref(res)), "mrt_renderer_converge")
+        return res.as_dict()
+
     # ---- multi-GPU exchange (include/mrt.h: mrt_renderer_exchange) ----
     def exchange(self, comm: "Comm", mode: int = EXCHANGE_GATHER) -> None:
         """Enqueue the image exchange of this shard renderer on its stream:
@@ -981,6 +1067,26 @@ def tile_priority(image_ptr: int, variance_ptr: int, n_ptr: int, priority_ptr: i
     _check(lib().mrt_tile_priority(image_ptr, variance_ptr, n_ptr, priority_ptr, width, height,
                                    ctypes.byref(params) if params is not None else None, _flags(precise), stream),
            "mrt_tile_priority")
+    if sync:
+        synchronize(stream)
+
+
+def tile_error(image_ptr: int, variance_ptr: int, n_ptr: int, mean_ptr: int, pixels_ptr: int, width: int, height: int,
+               params: "AdaptiveParams | None", precise=True, stream=None, sync=True) -> None:
+    """Per 64x64 tile: the mean of v / (l^2 + eps^2) over the counted pixels, and their number (mrt_tile_error)."""
+    _check(lib().mrt_tile_error(image_ptr, variance_ptr, n_ptr, mean_ptr, pixels_ptr, width, height,
+                                ctypes.byref(params) if params is not None else None, _flags(precise), stream),
+           "mrt_tile_error")
+    if sync:
+        synchronize(stream)
+
+
+def tile_threshold(mean_ptr: int, pixels_ptr: int, tiles: int, threshold: float, max_count: int, list_ptr: int,
+                   summary_ptr: int, stream=None, sync=True) -> None:
+    """The tiles whose mean error exceeds `threshold`, worst first, and an
+    ErrorSummary in device memory (mrt_tile_threshold)."""
+    _check(lib().mrt_tile_threshold(mean_ptr, pixels_ptr, tiles, threshold, max_count, list_ptr, summary_ptr, stream),
+           "mrt_tile_threshold")
     if sync:
         synchronize(stream)
 
