@@ -427,6 +427,53 @@ int mrt_denoise_variance(const float* image, const float* variance, const float*
                          float* out, float* scratch, float* variance_out /* may be NULL */, uint32_t width,
                          uint32_t height, const mrt_svgf_params* params, void* stream);
 
+/* ---- firefly suppression -----------------------------------------------------
+ * An outlier clamp ahead of the variance-guided filter: a
+ * pixel whose luminance lies far above that of its neighbours on the same
+ * surface is scaled down to a cap.  The filter's luminance weight is built to
+ * keep such a pixel, so without the clamp it survives the filter.  The clamp is
+ * BIASED: it removes energy and does not redistribute it; it is off unless
+ * asked for (mrt_renderer_set_firefly below), and it never touches the variance
+ * plane.  Not in the reference.  Device pointers throughout; lum is the lum of
+ * "variance-guided denoising" above. */
+typedef struct mrt_firefly_params {
+  uint32_t radius;          /* R, 1..3: the window is {-R..R}^2 */
+  float k;                  /* > 0: cap = mean + k * standard deviation */
+  uint32_t min_taps;        /* >= 1: fewer counting taps leave the pixel alone */
+  float normal_cos_min;     /* [-1, 1] */
+  float plane_tolerance;    /* > 0 */
+} mrt_firefly_params;
+/* Host only.  radius = 2, k = 3, min_taps = 3, normal_cos_min = 0.9,
+ * plane_tolerance = 0.01. */
+int mrt_firefly_params_default(mrt_firefly_params* out);
+/* Host only.  MRT_ERR_INVALID (with a message naming the field) for a field
+ * outside the ranges above, a non-finite one included. */
+int mrt_firefly_params_check(const mrt_firefly_params* p);
+/* image and out are W*H float4, the guide planes as mrt_guides writes them.
+ * Per pixel p, out[p] = image[p] bitwise, alpha included, unless ALL of:
+ *   (a) p is filterable (word_p < 0x80000000), c_p = image[p].rgb is finite and
+ *       l_p = lum(c_p) > 0;
+ *   (b) no pixel q of the window p + {-R..R}^2 inside the image is a light
+ *       pixel, 0x80000000 <= word_q < 0xFFFFFFFF (a miss is not a light);
+ *   (c) over the window's taps q != p, dy outer and dx inner, a tap COUNTS iff
+ *       q is inside the image, word_q == word_p, c_q is finite,
+ *       n_p.n_q >= normal_cos_min and |n_p.(x_q - x_p)| <= plane_tolerance t_p
+ *       (a comparison with a NaN guide value is false); N, the number of
+ *       counting taps, is at least min_taps;
+ *   (d) with l_q = lum(c_q) over the counting taps, m = (sum l_q) / N,
+ *       s2 = max(0, (sum l_q^2) / N - m m) and cap = m + k sqrt(s2): l_p > cap.
+ * Then out[p].rgb = c_p (cap / l_p), alpha copied; cap == 0 (every counting
+ * neighbour black) makes the pixel 0.  A pixel with a non-finite colour is left
+ * for the filter to repair.  `clamped` (one uint32, may be NULL) is zeroed on
+ * the stream and then receives the number of pixels whose rgb changed.
+ * IEEE division and square root, contraction allowed: the result agrees with
+ * the definition to rounding; the decision (d) may differ where l_p and cap
+ * agree to rounding.  Not in place: `out` or `clamped` overlapping an input or
+ * each other, and params == NULL, is MRT_ERR_INVALID (and writes nothing). */
+int mrt_firefly_clamp(const float* image, const float* guide_n, const float* guide_p, float* out,
+                      uint32_t* clamped /* device, may be NULL */, uint32_t width, uint32_t height,
+                      const mrt_firefly_params* params, void* stream);
+
 /* ---- adaptive sampling ------------------------------------------------------
  * Spend further samples where the variance plane says the error is: a priority
  * per 64x64 tile, the tiles of highest priority, and draws of an arbitrary
@@ -714,6 +761,31 @@ int mrt_renderer_denoise_variance(mrt_renderer* r, const mrt_svgf_params* params
  * the filter (or the last mrt_renderer_refine chose its tiles by, whichever ran
  * later); synchronises.  MRT_ERR_STATE before one has run at the current size. */
 int mrt_renderer_read_variance(mrt_renderer* r, float* plane, size_t count);
+/* Firefly suppression on a renderer (the section of that name above).  Off by
+ * default; params NULL switches it off.  The params are checked, and a failed
+ * check changes nothing.  Needs MRT_FLAG_MOMENTS (MRT_ERR_STATE without it, as
+ * mrt_renderer_denoise_variance).  The setting persists across reset, resize,
+ * set_camera and move_camera.  While it is on, mrt_renderer_denoise_variance —
+ * and through it mrt_renderer_error and mrt_renderer_converge — enqueues,
+ * between the resolve and mrt_variance, on the main stream and without a host
+ * wait, mrt_firefly_clamp(resolved, guide planes) into a clamped buffer the
+ * renderer owns (16 B per pixel and one counter, allocated at the first such
+ * call, re-made by resize), and the filter is fed that buffer instead of the
+ * resolved one.  The variance plane still comes from the moments; the resolved
+ * buffer (read_resolved), the accumulation image, the moments, the extra images
+ * and the history are never written by it.  While it is off every call
+ * enqueues exactly what it enqueues without this section.  The clamp is biased
+ * (it removes energy), and so are the denoised image and the error estimate
+ * built on it: DESIGN.md §2.1s.  mrt_renderer_denoise and _denoise_resolved do
+ * not clamp. */
+int mrt_renderer_set_firefly(mrt_renderer* r, const mrt_firefly_params* params /* NULL = off */);
+/* *out = the params in force (mrt_firefly_params_default while it has never been
+ * on), *enabled = 1 or 0; either may be NULL. */
+int mrt_renderer_get_firefly(const mrt_renderer* r, mrt_firefly_params* out, uint32_t* enabled);
+/* The clamped buffer (W*H*4 floats) and *clamped_pixels (may be NULL), the
+ * count, of the last clamp; synchronises.  MRT_ERR_STATE before one has run at
+ * the current size. */
+int mrt_renderer_read_clamped(mrt_renderer* r, float* rgba, size_t count, uint32_t* clamped_pixels);
 /* Adaptive sampling on a renderer (the section of that name above): extra
  * frames of chosen tiles, accumulated into two counted images the renderer
  * owns beside its image — E, the extra image (r, g, b, n), and EM, the extra

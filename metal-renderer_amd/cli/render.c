@@ -30,6 +30,7 @@
  *                   [--aperture LENS_RADIUS] [--focus DISTANCE]
  *                   [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]
  *                   [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]
+ *                   [--firefly [K]]
  *                   [--orbit-steps K --orbit-degrees D]
  *                   [--refine-passes P --refine-frames F --refine-tiles K]
  *                   [--target-error E [--converge-frames F] [--converge-max-passes P]
@@ -69,6 +70,10 @@
  * of mrt_renderer_denoise_variance, run after the last draw (with --orbit-steps
  * after the last move's draw); --svgf-iterations and --svgf-sigma-luminance
  * override a default of mrt_svgf_params_default and imply it.
+ * --firefly [K] (with --denoise-variance or --target-error, a usage error
+ * otherwise): mrt_renderer_set_firefly with mrt_firefly_params_default, k = K
+ * if given — outliers are clamped ahead of the variance-guided filter (biased:
+ * energy is removed, not redistributed).
  * The camera options go through mrt_camera_look_at / mrt_renderer_set_camera
  * (fov: full horizontal angle; --aperture > 0: a thin lens, focused at --focus
  * or else on the target); without any of them the reference's camera renders.
@@ -108,6 +113,9 @@ typedef struct {
   int denoise_variance, svgf_iterations_set, svgf_sigma_set;
   uint32_t svgf_iterations;
   float svgf_sigma_luminance;
+  /* firefly suppression (mrt_renderer_set_firefly) */
+  int firefly, firefly_k_set;
+  float firefly_k;
   /* orbit with temporal history (mrt_renderer_move_camera) */
   /* adaptive sampling (mrt_renderer_refine) */
   uint32_t refine_passes, refine_frames, refine_tiles;
@@ -143,6 +151,7 @@ static void usage(void) {
           "                  [--aperture LENS_RADIUS] [--focus DISTANCE]\n"
           "                  [--denoise] [--denoise-iterations N] [--denoise-sigma-color S]\n"
           "                  [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]\n"
+          "                  [--firefly [K]]\n"
           "                  [--orbit-steps K --orbit-degrees D]\n"
           "                  [--refine-passes P --refine-frames F --refine-tiles K]\n"
           "                  [--target-error E [--converge-frames F] [--converge-max-passes P] [--converge-budget N]]\n"
@@ -154,7 +163,9 @@ static void usage(void) {
           "  of the K 64x64 tiles whose variance says they need them most; --out gets an image that holds them.\n"
           "  --target-error E (one rank, not with --refine-*): after the draws, F extra frames per pass of the tiles\n"
           "  whose estimated relative squared error is above E, until none is, P passes are drawn or N tile-frames\n"
-          "  are spent; prints one line about it; --out gets the --denoise-variance image.\n");
+          "  are spent; prints one line about it; --out gets the --denoise-variance image.\n"
+          "  --firefly [K] (with --denoise-variance or --target-error only): clamp outliers above mean + K standard\n"
+          "  deviations (default 3) of their neighbourhood ahead of the variance-guided filter; biased.\n");
 }
 
 /* --scene cornellbox -> <dir of this executable>/../scenes/cornellbox.obj */
@@ -214,6 +225,12 @@ static int parse(int argc, char** argv, options* o) {
     else if (VAL("--converge-budget")) { o->converge_budget = strtoull(v, NULL, 0); o->converge_set = 1; }
     else if (VAL("--svgf-iterations")) { o->svgf_iterations = (uint32_t)strtoul(v, NULL, 0); o->denoise_variance = o->svgf_iterations_set = 1; }
     else if (VAL("--svgf-sigma-luminance")) { o->svgf_sigma_luminance = strtof(v, NULL); o->denoise_variance = o->svgf_sigma_set = 1; }
+    else if (strcmp(a, "--firefly") == 0) {   /* the value is optional: taken when the next argument is a number */
+      char* end = NULL;
+      const float k = v ? strtof(v, &end) : 0.0f;
+      o->firefly = 1;
+      if (v && end != v && *end == 0) { o->firefly_k = k; o->firefly_k_set = 1; ++i; }
+    }
     else if (strcmp(a, "--denoise") == 0) o->denoise = 1;
     else if (strcmp(a, "--denoise-variance") == 0) o->denoise_variance = 1;
     else if (strcmp(a, "--precise") == 0) o->flags |= MRT_FLAG_PRECISE;
@@ -276,6 +293,11 @@ static int parse(int argc, char** argv, options* o) {
       return -1;
     }
     o->denoise_variance = 1;   /* the image it saves */
+  }
+  if (o->firefly && !o->denoise_variance) {
+    fprintf(stderr, "mrt_render: --firefly needs --denoise-variance or --target-error\n");
+    usage();
+    return -1;
   }
   if (o->denoise_variance || o->refine_set) o->flags |= MRT_FLAG_MOMENTS;
   return 0;
@@ -379,6 +401,12 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
     mrt_camera cam;
     if (make_camera(o, o->eye, o->pose_set, &cam)) return 1;
     if (mrt_renderer_set_camera(r, &cam)) return die("mrt_renderer_set_camera");
+  }
+  if (o->firefly) {
+    mrt_firefly_params fp;
+    if (mrt_firefly_params_default(&fp)) return die("mrt_firefly_params_default");
+    if (o->firefly_k_set) fp.k = o->firefly_k;
+    if (mrt_renderer_set_firefly(r, &fp)) return die("mrt_renderer_set_firefly");
   }
   struct timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);

@@ -358,6 +358,14 @@ struct mrt_renderer {
   // history's validity is history_valid.
   mrt::host::DevBuf moments, moments_prev, moments_history, moments_resolved, variance;
   bool variance_current = false;   // a denoise_variance has run at the current size
+  // firefly suppression (mrt_renderer_set_firefly): while it is on,
+  // denoise_variance filters the clamped copy of the resolved buffer — 16 B per
+  // pixel and, behind them, the counter of changed pixels; made at the first
+  // clamp, re-made by resize.  The setting survives reset, resize and moves.
+  bool firefly_on = false;
+  mrt_firefly_params firefly{2, 3.0f, 3, 0.9f, 0.01f};   // mrt_firefly_params_default
+  mrt::host::DevBuf clamped;
+  bool clamped_current = false;    // a clamp has run at the current size
   // adaptive sampling (mrt_renderer_refine / _draw_tiles): everything is made at
   // the first call and re-made by resize.  E and EM are counted images beside
   // the image and the moments; the second noise schedule (seed ^

@@ -947,6 +947,7 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   r->guides_current = r->denoised_current = false;
   r->history_valid = r->resolved_current = false;
   r->variance_current = false;
+  r->clamped_current = false;
   r->extras_current = r->extras_valid = r->priority_current = false;   // re-made (and zeroed) by the next refine / draw_tiles
   r->tile_error_current = false;
   r->list_count = 0;
@@ -963,6 +964,7 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
                       &r->resolved, &r->moments_prev, &r->moments_history, &r->moments_resolved})
       if (b->p && b->bytes != bytes) HIP_TRY(b->alloc(bytes));
     if (r->variance.p && r->variance.bytes != bytes / 4) HIP_TRY(r->variance.alloc(bytes / 4));
+    if (r->clamped.p && r->clamped.bytes != bytes + 16) HIP_TRY(r->clamped.alloc(bytes + 16));
   }
   return alloc_frame_buffers(r);
 }
@@ -1291,15 +1293,60 @@ int mrt_renderer_denoise_variance(mrt_renderer* r, const mrt_svgf_params* params
   if (rc) return rc;
   rc = resolve_moments_into(r, r->moments_resolved);
   if (rc) return rc;
+  const float* filtered = r->resolved.as<float>();
+  if (r->firefly_on) {   // the filter's input is the clamped copy; the resolved buffer stays as it is
+    if (r->clamped.bytes != bytes + 16 || !r->clamped.p) {
+      r->clamped_current = false;
+      HIP_TRY(r->clamped.alloc(bytes + 16));
+    }
+    rc = mrt_firefly_clamp(r->resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
+                           r->clamped.as<float>(), reinterpret_cast<uint32_t*>(r->clamped.as<char>() + bytes), W, H,
+                           &r->firefly, r->stream);
+    if (rc) return rc;
+    r->clamped_current = true;
+    filtered = r->clamped.as<float>();
+  }
   rc = mrt_variance(r->moments_resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
                     r->variance.as<float>(), W, H, &p, r->stream);
   if (rc) return rc;
   r->variance_current = true;
-  rc = mrt_denoise_variance(r->resolved.as<float>(), r->variance.as<float>(), r->guide_n.as<float>(),
-                            r->guide_p.as<float>(), r->denoised.as<float>(), r->denoise_scratch.as<float>(), nullptr, W,
-                            H, &p, r->stream);
+  rc = mrt_denoise_variance(filtered, r->variance.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
+                            r->denoised.as<float>(), r->denoise_scratch.as<float>(), nullptr, W, H, &p, r->stream);
   if (rc) return rc;
   r->denoised_current = true;
+  return MRT_OK;
+}
+
+// ---- firefly suppression (include/mrt.h: mrt_renderer_set_firefly) ----------
+int mrt_renderer_set_firefly(mrt_renderer* r, const mrt_firefly_params* params) {
+  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
+  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
+    return fail(MRT_ERR_STATE, "mrt_renderer_set_firefly: the renderer was created without MRT_FLAG_MOMENTS");
+  if (!params) {
+    r->firefly_on = false;
+    return MRT_OK;
+  }
+  const int rc = mrt_firefly_params_check(params);
+  if (rc) return rc;
+  r->firefly = *params;
+  r->firefly_on = true;
+  return MRT_OK;
+}
+
+int mrt_renderer_get_firefly(const mrt_renderer* r, mrt_firefly_params* out, uint32_t* enabled) {
+  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
+  if (out) *out = r->firefly;
+  if (enabled) *enabled = r->firefly_on ? 1u : 0u;
+  return MRT_OK;
+}
+
+int mrt_renderer_read_clamped(mrt_renderer* r, float* rgba, size_t count, uint32_t* clamped_pixels) {
+  const int rc = read_plane(r, &mrt_renderer::clamped, &mrt_renderer::clamped_current,
+                            "no firefly clamp has run at the renderer's current size", rgba, count);
+  if (rc) return rc;
+  if (clamped_pixels)
+    HIP_TRY(hipMemcpy(clamped_pixels, r->clamped.as<char>() + (size_t)r->desc.width * r->desc.height * 16, 4,
+                      hipMemcpyDeviceToHost));
   return MRT_OK;
 }
 

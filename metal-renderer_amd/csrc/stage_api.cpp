@@ -8,6 +8,7 @@
 
 #include "host_internal.h"
 #include "denoise.h"
+#include "firefly.h"
 #include "image.h"
 #include "noise.h"
 #include "temporal.h"
@@ -507,6 +508,65 @@ int mrt_debug_denoise_variance_step(const float* image, const float* variance, c
   if (step_log2 > 14 || path > mrt::kAtrousStaged)
     return fail(MRT_ERR_INVALID, "mrt_debug_denoise_variance_step: step at most 2^14, path 0, 1 or 2");
   return svgf_run(image, variance, guide_n, guide_p, out, nullptr, nullptr, W, H, params, 1u, step_log2, path, false, stream);
+}
+
+// ---- firefly suppression (include/mrt.h) -------------------------------------
+int mrt_firefly_params_default(mrt_firefly_params* out) {
+  if (!out) return fail(MRT_ERR_INVALID, "mrt_firefly_params_default: null params");
+  out->radius = 2;
+  out->k = 3.0f;
+  out->min_taps = 3;
+  out->normal_cos_min = 0.9f;
+  out->plane_tolerance = 0.01f;
+  return MRT_OK;
+}
+
+int mrt_firefly_params_check(const mrt_firefly_params* p) {
+  if (!p) return fail(MRT_ERR_INVALID, "firefly params: null");
+  if (p->radius < 1 || p->radius > 3) return fail(MRT_ERR_INVALID, "firefly params: radius must be 1, 2 or 3");
+  if (!std::isfinite(p->k) || !(p->k > 0.0f)) return fail(MRT_ERR_INVALID, "firefly params: k must be finite and positive");
+  if (p->min_taps < 1) return fail(MRT_ERR_INVALID, "firefly params: min_taps must be at least 1");
+  if (!(p->normal_cos_min >= -1.0f && p->normal_cos_min <= 1.0f))
+    return fail(MRT_ERR_INVALID, "firefly params: normal_cos_min must be in [-1, 1]");
+  if (!std::isfinite(p->plane_tolerance) || !(p->plane_tolerance > 0.0f))
+    return fail(MRT_ERR_INVALID, "firefly params: plane_tolerance must be finite and positive");
+  return MRT_OK;
+}
+
+int mrt_firefly_clamp(const float* image, const float* guide_n, const float* guide_p, float* out, uint32_t* clamped,
+                      uint32_t W, uint32_t H, const mrt_firefly_params* params, void* stream) {
+  if (!image || !guide_n || !guide_p || !out || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_firefly_clamp: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+    const char* p = (const char*)a;
+    const char* q = (const char*)b;
+    return p < q + nb && q < p + na;
+  };
+  for (const float* in : {image, guide_n, guide_p})
+    if (overlap(in, bytes, out, bytes) || (clamped && overlap(in, bytes, clamped, 4)))
+      return fail(MRT_ERR_INVALID, "mrt_firefly_clamp: out and clamped must not overlap an input");
+  if (clamped && overlap(out, bytes, clamped, 4))
+    return fail(MRT_ERR_INVALID, "mrt_firefly_clamp: out and clamped must not overlap each other");
+  const int rc = mrt_firefly_params_check(params);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (clamped) HIP_TRY(hipMemsetAsync(clamped, 0, 4, s));
+  mrt::FireflyArgs a{};
+  a.image = reinterpret_cast<const float4*>(image);
+  a.guide_n = reinterpret_cast<const float4*>(guide_n);
+  a.guide_p = reinterpret_cast<const float4*>(guide_p);
+  a.out = reinterpret_cast<float4*>(out);
+  a.clamped = clamped;
+  a.width = W;
+  a.height = H;
+  a.radius = params->radius;
+  a.k = params->k;
+  a.min_taps = params->min_taps;
+  a.normal_cos_min = params->normal_cos_min;
+  a.plane_tolerance = params->plane_tolerance;
+  HIP_TRY(mrt::launch_firefly(a, s));
+  return MRT_OK;
 }
 
 // ---- adaptive sampling (include/mrt.h) ---------------------------------------

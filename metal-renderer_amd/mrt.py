@@ -241,6 +241,27 @@ class SvgfParams(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FireflyParams(ctypes.Structure):
+    """mrt_firefly_params (include/mrt.h): the outlier clamp ahead of the
+    variance-guided filter."""
+    _fields_ = [
+        ("radius", ctypes.c_uint32), ("k", ctypes.c_float), ("min_taps", ctypes.c_uint32),
+        ("normal_cos_min", ctypes.c_float), ("plane_tolerance", ctypes.c_float),
+    ]
+
+    @classmethod
+    def default(cls) -> "FireflyParams":
+        p = cls()
+        _check(lib().mrt_firefly_params_default(ctypes.byref(p)), "mrt_firefly_params_default")
+        return p
+
+    def check(self) -> None:
+        _check(lib().mrt_firefly_params_check(ctypes.byref(self)), "mrt_firefly_params_check")
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AdaptiveParams(ctypes.Structure):
     """mrt_adaptive_params (include/mrt.h): the tile priority's parameters."""
     _fields_ = [("luminance_floor", ctypes.c_float)]
@@ -343,6 +364,8 @@ EXPORTED = [
     "mrt_renderer_refine_stats",
     "mrt_tile_error", "mrt_tile_threshold", "mrt_converge_params_default", "mrt_converge_params_check",
     "mrt_renderer_error", "mrt_renderer_read_tile_error", "mrt_renderer_converge",
+    "mrt_firefly_params_default", "mrt_firefly_params_check", "mrt_firefly_clamp", "mrt_renderer_set_firefly",
+    "mrt_renderer_get_firefly", "mrt_renderer_read_clamped",
 ]
 
 _lib = None
@@ -485,6 +508,12 @@ def lib() -> ctypes.CDLL:
                                ctypes.POINTER(ErrorSummary)],
         "mrt_renderer_read_tile_error": [vp, vp, vp, ctypes.c_size_t],
         "mrt_renderer_converge": [vp, ctypes.POINTER(ConvergeParams), ctypes.POINTER(ConvergeResult)],
+        "mrt_firefly_params_default": [ctypes.POINTER(FireflyParams)],
+        "mrt_firefly_params_check": [ctypes.POINTER(FireflyParams)],
+        "mrt_firefly_clamp": [vp, vp, vp, vp, vp, u32, u32, ctypes.POINTER(FireflyParams), vp],
+        "mrt_renderer_set_firefly": [vp, ctypes.POINTER(FireflyParams)],
+        "mrt_renderer_get_firefly": [vp, ctypes.POINTER(FireflyParams), ctypes.POINTER(u32)],
+        "mrt_renderer_read_clamped": [vp, vp, ctypes.c_size_t, ctypes.POINTER(u32)],
     }
     for name, args in sig.items():
         fn = getattr(L, name, None)
@@ -790,6 +819,30 @@ class Renderer:
                "mrt_renderer_read_variance")
         return v
 
+    # ---- firefly suppression (include/mrt.h: mrt_renderer_set_firefly) ----
+    def set_firefly(self, params: "FireflyParams | None") -> None:
+        """Clamp outliers of the resolved buffer ahead of denoise_variance's
+        filter (and so of error_estimate and converge); None switches it off.
+        Biased: energy is removed, not redistributed."""
+        _check(lib().mrt_renderer_set_firefly(self._h, ctypes.byref(params) if params is not None else None),
+               "mrt_renderer_set_firefly")
+
+    @property
+    def firefly(self) -> "FireflyParams | None":
+        """The clamp's parameters while it is on, else None."""
+        p, on = FireflyParams(), ctypes.c_uint32()
+        _check(lib().mrt_renderer_get_firefly(self._h, ctypes.byref(p), ctypes.byref(on)), "mrt_renderer_get_firefly")
+        return p if on.value else None
+
+    def read_clamped(self):
+        """([H, W, 4] float32, pixels changed): what the last clamp fed to the filter."""
+        import numpy as np
+        img = np.zeros((self.height, self.width, 4), np.float32)
+        n = ctypes.c_uint32()
+        _check(lib().mrt_renderer_read_clamped(self._h, ctypes.c_void_p(img.ctypes.data), img.size, ctypes.byref(n)),
+               "mrt_renderer_read_clamped")
+        return img, n.value
+
     # ---- adaptive sampling (include/mrt.h: mrt_renderer_refine) ----
     def tile_count(self) -> int:
         return ((self.width + TILE - 1) // TILE) * ((self.height + TILE - 1) // TILE)
@@ -1038,6 +1091,15 @@ def denoise_variance(image_ptr: int, variance_ptr: int, n_ptr: int, p_ptr: int, 
     _check(lib().mrt_denoise_variance(image_ptr, variance_ptr, n_ptr, p_ptr, out_ptr, scratch_ptr, variance_out_ptr,
                                       width, height, ctypes.byref(params) if params is not None else None, stream),
            "mrt_denoise_variance")
+    if sync:
+        synchronize(stream)
+
+
+def firefly_clamp(image_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, clamped_ptr: "int | None", width: int,
+                  height: int, params: "FireflyParams | None", stream=None, sync=True) -> None:
+    """The outlier clamp (mrt_firefly_clamp) on device buffers; clamped_ptr: one uint32 or None."""
+    _check(lib().mrt_firefly_clamp(image_ptr, n_ptr, p_ptr, out_ptr, clamped_ptr, width, height,
+                                   ctypes.byref(params) if params is not None else None, stream), "mrt_firefly_clamp")
     if sync:
         synchronize(stream)
 
