@@ -3,7 +3,10 @@
 // (mrt_scene, mrt_accel, mrt_renderer, mrt_comm) and the few functions that
 // cross units.  The units: scene_api.cpp (scene, accel), stage_api.cpp (the
 // stage-level ABI and the standalone image entry points), renderer.cpp (the
-// renderer and its draw loop), exchange.cpp (RCCL communicator, tile exchange).
+// renderer, its cameras and its draw loop), renderer_post.cpp (the images a
+// renderer derives from what it accumulated: denoised, resolved, history,
+// variance, clamped, extras, tile planes, display), exchange.cpp (RCCL
+// communicator, tile exchange).
 // Everything shared lives in mrt::host; the units use that namespace.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -138,9 +141,24 @@ struct DrawSource {
   mrt::NoiseSchedule* noise = nullptr;
   uint64_t f0 = 0;
   uint32_t tiles = 0;                       // listed tiles; 0 = the owned tiles
+  uint32_t* list = nullptr;                 // listed: the device list (null otherwise)
   const uint32_t* host_list = nullptr;      // listed: to upload (null: the device list is already chosen)
   float* image = nullptr;                   // accumulation image, or E
   float* moments = nullptr;                 // moments image (may be null), or EM
+};
+
+// What a reader copies to the host once the renderer is idle (read_back): `need`
+// 4-B elements from `src` into the caller's buffer and, where the reader has a
+// second output, need2 from src2.  stale: the entry point's own message while
+// the plane is not `current` (computed at the renderer's current size)
+struct ReadSpec {
+  size_t need = 0;
+  const void* src = nullptr;
+  bool current = true;
+  const char* stale = nullptr;
+  const void* src2 = nullptr;
+  size_t need2 = 0;
+  bool flush = false;                       // a deferred exchange lands first (the image)
 };
 
 // One in-flight frame: its queues, segment counts, per-pixel path radiance and
@@ -401,6 +419,19 @@ mrt::CameraBlock camera_block(const mrt_camera& c);
 bool camera_is_default(const mrt_camera& c);
 int guides_with_spill(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, float* guide_n,
                       float* guide_p, uint32_t flags, uint32_t* spill, void* stream);
+
+// renderer.cpp: the draw loop and its statistics; `cam` put in force, or the
+// renderer left as it was; a reader's checks, wait and copy; an image to a file
+int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src);
+int finalize_pending(mrt_renderer* r);
+int swap_camera(mrt_renderer* r, const mrt_camera& cam);
+int read_back(mrt_renderer* r, void* out, size_t count, ReadSpec (*spec)(const mrt_renderer*), void* out2 = nullptr);
+int save_read(mrt_renderer* r, const char* path, int (*read)(mrt_renderer*, float*, size_t));
+
+// renderer_post.cpp: what resize, reset and destroy do about the derived images
+int post_resize(mrt_renderer* r);
+int post_reset(mrt_renderer* r);
+void post_destroy(mrt_renderer* r);
 
 // exchange.cpp: what the renderer's resize / reset, sync / destroy and image
 // readers do about its pending collective and deferred unpack

@@ -9,6 +9,9 @@
 // else ignored.  ZIP blocks are zlib streams of the predictor-coded,
 // byte-interleaved scanline data (OpenEXR's ImfZip: a delta predictor over the
 // bytes, then the even and odd bytes split into two halves).
+//
+// Behind it the writers of the renderer's save_* entry points: PFM, and
+// uncompressed scanline OpenEXR with FLOAT A, B, G, R channels, top-down.
 #include <zlib.h>
 
 #include <algorithm>
@@ -180,6 +183,85 @@ bool load_exr(const std::string& path, std::vector<float>& rgba, uint32_t& width
     }
   }
   return true;
+}
+
+bool write_pfm(const std::string& path, const std::vector<float>& rgba, uint32_t W, uint32_t H, std::string& err) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) { err = "cannot write " + path; return false; }
+  std::fprintf(f, "PF\n%u %u\n-1.0\n", W, H);
+  std::vector<float> row(3 * (size_t)W);
+  for (uint32_t y = 0; y < H; ++y) {   // PFM scanlines are bottom-to-top == our row order
+    for (uint32_t x = 0; x < W; ++x)
+      for (int c = 0; c < 3; ++c) row[3 * x + c] = rgba[4 * ((size_t)y * W + x) + c];
+    std::fwrite(row.data(), 4, row.size(), f);
+  }
+  std::fclose(f);
+  return true;
+}
+
+bool write_exr(const std::string& path, const std::vector<float>& rgba, uint32_t W, uint32_t H, std::string& err) {
+  std::vector<uint8_t> out;
+  auto put = [&](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; out.insert(out.end(), b, b + n); };
+  auto put_i32 = [&](int32_t v) { put(&v, 4); };
+  auto put_str = [&](const char* s) { put(s, std::strlen(s) + 1); };
+  auto attr = [&](const char* name, const char* type, const std::vector<uint8_t>& v) {
+    put_str(name); put_str(type); put_i32((int32_t)v.size()); put(v.data(), v.size());
+  };
+  const uint32_t magic = 20000630u, version = 2u;
+  put(&magic, 4); put(&version, 4);
+  std::vector<uint8_t> ch;
+  for (const char* c : {"A", "B", "G", "R"}) {
+    ch.insert(ch.end(), c, c + 2);
+    const int32_t pt = 2;  // FLOAT
+    const uint8_t plin[4] = {0, 0, 0, 0};
+    const int32_t xs = 1, ys = 1;
+    ch.insert(ch.end(), (const uint8_t*)&pt, (const uint8_t*)&pt + 4);
+    ch.insert(ch.end(), plin, plin + 4);
+    ch.insert(ch.end(), (const uint8_t*)&xs, (const uint8_t*)&xs + 4);
+    ch.insert(ch.end(), (const uint8_t*)&ys, (const uint8_t*)&ys + 4);
+  }
+  ch.push_back(0);
+  attr("channels", "chlist", ch);
+  attr("compression", "compression", {0});
+  const int32_t box[4] = {0, 0, (int32_t)W - 1, (int32_t)H - 1};
+  std::vector<uint8_t> bx((const uint8_t*)box, (const uint8_t*)box + 16);
+  attr("dataWindow", "box2i", bx);
+  attr("displayWindow", "box2i", bx);
+  attr("lineOrder", "lineOrder", {0});
+  const float par = 1.0f, ssw = 1.0f, swc[2] = {0.0f, 0.0f};
+  attr("pixelAspectRatio", "float", std::vector<uint8_t>((const uint8_t*)&par, (const uint8_t*)&par + 4));
+  attr("screenWindowCenter", "v2f", std::vector<uint8_t>((const uint8_t*)swc, (const uint8_t*)swc + 8));
+  attr("screenWindowWidth", "float", std::vector<uint8_t>((const uint8_t*)&ssw, (const uint8_t*)&ssw + 4));
+  out.push_back(0);
+  const size_t line_bytes = (size_t)W * 4 * 4;
+  uint64_t off = out.size() + 8ull * H;
+  for (uint32_t y = 0; y < H; ++y) { put(&off, 8); off += 8 + line_bytes; }
+  std::vector<float> line(4 * (size_t)W);
+  for (uint32_t y = 0; y < H; ++y) {
+    const uint32_t src = H - 1 - y;   // EXR is top-down; our row 0 is the bottom
+    for (int c = 0; c < 4; ++c) {      // A, B, G, R
+      const int comp = 3 - c;
+      for (uint32_t x = 0; x < W; ++x) line[(size_t)c * W + x] = rgba[4 * ((size_t)src * W + x) + comp];
+    }
+    put_i32((int32_t)y);
+    put_i32((int32_t)line_bytes);
+    put(line.data(), line_bytes);
+  }
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) { err = "cannot write " + path; return false; }
+  std::fwrite(out.data(), 1, out.size(), f);
+  std::fclose(f);
+  return true;
+}
+
+bool save_rgba(const std::string& path, const std::vector<float>& rgba, uint32_t W, uint32_t H, std::string& err, bool& io) {
+  auto ends = [&](const char* s) { const size_t n = std::strlen(s); return path.size() >= n && path.compare(path.size() - n, n, s) == 0; };
+  io = true;
+  if (ends(".pfm")) return write_pfm(path, rgba, W, H, err);
+  if (ends(".exr")) return write_exr(path, rgba, W, H, err);
+  io = false;
+  err = "unsupported image extension (use .pfm or .exr)";
+  return false;
 }
 
 }  // namespace mrt

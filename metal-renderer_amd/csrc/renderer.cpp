@@ -1,6 +1,7 @@
 // renderer.cpp — the renderer of include/mrt.h: life cycle, camera
-// generations, the draw loop and its statistics, and image read-back, denoise,
-// temporal resolve and display on a renderer.  (Scene: scene_api.cpp; stage
+// generations, the draw loop and its statistics, and the read-back of the
+// image.  (What a renderer derives from the image — filtered, resolved and
+// displayed images, tile planes: renderer_post.cpp; scene: scene_api.cpp; stage
 // calls: stage_api.cpp; multi-GPU exchange: exchange.cpp.)
 //
 // mrt_renderer_draw_n mirrors performRaytracing: (renderer/Renderer.mm:500-585)
@@ -13,8 +14,6 @@
 //                        (raygen fused into bounce 0, shadow resolve and
 //                        accumulation fused into the bounce where the path
 //                        ends)                                 = L launches
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
 
 #include "host_internal.h"
@@ -27,7 +26,7 @@ using namespace mrt::host;
 namespace {
 
 // pixels of tile t inside the image
-uint64_t tile_pixels(const mrt_renderer* r, uint32_t t) {
+uint64_t pixels_of_tile(const mrt_renderer* r, uint32_t t) {
   const uint32_t tx = t % r->tiles_x, ty = t / r->tiles_x;
   return (uint64_t)std::min<uint32_t>(mrt::kTile, r->desc.width - tx * mrt::kTile) *
          std::min<uint32_t>(mrt::kTile, r->desc.height - ty * mrt::kTile);
@@ -46,7 +45,7 @@ int finalize_draw(mrt_renderer* r, DrawRecord& d) {
   const uint32_t* cnt = static_cast<const uint32_t*>(d.host);
   if (d.listed) {   // a refine draw: its list is on the host by now (uploaded from there, or copied back behind the draw)
     d.pixels = 0;
-    for (uint32_t k = 0; k < d.listed; ++k) d.pixels += tile_pixels(r, d.list_host[k]);
+    for (uint32_t k = 0; k < d.listed; ++k) d.pixels += pixels_of_tile(r, d.list_host[k]);
     r->refine_stats.paths += d.pixels * d.frames;
   }
   uint64_t active = d.pixels * d.frames;   // bounce 0: every rendered pixel's camera ray
@@ -75,15 +74,6 @@ int finalize_draw(mrt_renderer* r, DrawRecord& d) {
     }
   }
   d.pending = false;
-  return MRT_OK;
-}
-
-// read back every pending draw, oldest first
-int finalize_pending(mrt_renderer* r) {
-  for (int i = 0; i < kDrawRing; ++i) {
-    const int rc = finalize_draw(r, r->draws[(r->draw_next + i) % kDrawRing]);
-    if (rc) return rc;
-  }
   return MRT_OK;
 }
 
@@ -345,7 +335,7 @@ int bounce_args(const mrt_renderer* r, const DrawSource& src, const DrawRecord& 
   a.shard_count = r->desc.shard_count;
   a.tiles_x = r->tiles_x;
   a.num_slots = (src.tiles ? src.tiles : r->owned_tiles) * 4096u;
-  a.tile_list = src.tiles ? r->tile_list.as<uint32_t>() : nullptr;
+  a.tile_list = src.list;
   a.div_tiles = mrt::magic_div(a.tiles_x);
   a.div_slots = mrt::magic_div(a.num_slots);
   a.div_batch = mrt::magic_div(bt.frames);
@@ -403,7 +393,7 @@ mrt::AccumArgs accum_args(const mrt_renderer* r, const DrawSource& src, const Dr
   acc.image = reinterpret_cast<float4*>(src.image);
   acc.accumulate = (r->desc.flags & MRT_FLAG_NO_ACCUMULATE) ? 0u : 1u;
   acc.moments = reinterpret_cast<float4*>(src.moments);   // (null without MRT_FLAG_MOMENTS)
-  acc.tile_list = src.tiles ? r->tile_list.as<uint32_t>() : nullptr;
+  acc.tile_list = src.list;
   if (fold) {
     acc.counters = d.counters.as<uint32_t>();
     acc.host_counters = static_cast<uint32_t*>(d.host_dev);
@@ -415,244 +405,65 @@ mrt::AccumArgs accum_args(const mrt_renderer* r, const DrawSource& src, const Dr
   return acc;
 }
 
-int write_pfm(const char* path, const std::vector<float>& rgba, uint32_t W, uint32_t H) {
-  FILE* f = std::fopen(path, "wb");
-  if (!f) return fail(MRT_ERR_IO, std::string("cannot write ") + path);
-  std::fprintf(f, "PF\n%u %u\n-1.0\n", W, H);
-  std::vector<float> row(3 * (size_t)W);
-  for (uint32_t y = 0; y < H; ++y) {   // PFM scanlines are bottom-to-top == our row order
-    for (uint32_t x = 0; x < W; ++x)
-      for (int c = 0; c < 3; ++c) row[3 * x + c] = rgba[4 * ((size_t)y * W + x) + c];
-    std::fwrite(row.data(), 4, row.size(), f);
+}  // namespace
+
+// what renderer_post.cpp uses too (host_internal.h)
+namespace mrt {
+namespace host {
+
+// read back every pending draw, oldest first
+int finalize_pending(mrt_renderer* r) {
+  for (int i = 0; i < kDrawRing; ++i) {
+    const int rc = finalize_draw(r, r->draws[(r->draw_next + i) % kDrawRing]);
+    if (rc) return rc;
   }
-  std::fclose(f);
   return MRT_OK;
 }
 
-// Uncompressed scanline OpenEXR, FLOAT A,B,G,R channels, top-down.
-int write_exr(const char* path, const std::vector<float>& rgba, uint32_t W, uint32_t H) {
-  std::vector<uint8_t> out;
-  auto put = [&](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; out.insert(out.end(), b, b + n); };
-  auto put_i32 = [&](int32_t v) { put(&v, 4); };
-  auto put_str = [&](const char* s) { put(s, std::strlen(s) + 1); };
-  auto attr = [&](const char* name, const char* type, const std::vector<uint8_t>& v) {
-    put_str(name); put_str(type); put_i32((int32_t)v.size()); put(v.data(), v.size());
-  };
-  const uint32_t magic = 20000630u, version = 2u;
-  put(&magic, 4); put(&version, 4);
-  std::vector<uint8_t> ch;
-  for (const char* c : {"A", "B", "G", "R"}) {
-    ch.insert(ch.end(), c, c + 2);
-    const int32_t pt = 2;  // FLOAT
-    const uint8_t plin[4] = {0, 0, 0, 0};
-    const int32_t xs = 1, ys = 1;
-    ch.insert(ch.end(), (const uint8_t*)&pt, (const uint8_t*)&pt + 4);
-    ch.insert(ch.end(), plin, plin + 4);
-    ch.insert(ch.end(), (const uint8_t*)&xs, (const uint8_t*)&xs + 4);
-    ch.insert(ch.end(), (const uint8_t*)&ys, (const uint8_t*)&ys + 4);
-  }
-  ch.push_back(0);
-  attr("channels", "chlist", ch);
-  attr("compression", "compression", {0});
-  const int32_t box[4] = {0, 0, (int32_t)W - 1, (int32_t)H - 1};
-  std::vector<uint8_t> bx((const uint8_t*)box, (const uint8_t*)box + 16);
-  attr("dataWindow", "box2i", bx);
-  attr("displayWindow", "box2i", bx);
-  attr("lineOrder", "lineOrder", {0});
-  const float par = 1.0f, ssw = 1.0f, swc[2] = {0.0f, 0.0f};
-  attr("pixelAspectRatio", "float", std::vector<uint8_t>((const uint8_t*)&par, (const uint8_t*)&par + 4));
-  attr("screenWindowCenter", "v2f", std::vector<uint8_t>((const uint8_t*)swc, (const uint8_t*)swc + 8));
-  attr("screenWindowWidth", "float", std::vector<uint8_t>((const uint8_t*)&ssw, (const uint8_t*)&ssw + 4));
-  out.push_back(0);
-  const size_t line_bytes = (size_t)W * 4 * 4;
-  uint64_t off = out.size() + 8ull * H;
-  for (uint32_t y = 0; y < H; ++y) { put(&off, 8); off += 8 + line_bytes; }
-  std::vector<float> line(4 * (size_t)W);
-  for (uint32_t y = 0; y < H; ++y) {
-    const uint32_t src = H - 1 - y;   // EXR is top-down; our row 0 is the bottom
-    for (int c = 0; c < 4; ++c) {      // A, B, G, R
-      const int comp = 3 - c;
-      for (uint32_t x = 0; x < W; ++x) line[(size_t)c * W + x] = rgba[4 * ((size_t)src * W + x) + comp];
-    }
-    put_i32((int32_t)y);
-    put_i32((int32_t)line_bytes);
-    put(line.data(), line_bytes);
-  }
-  FILE* f = std::fopen(path, "wb");
-  if (!f) return fail(MRT_ERR_IO, std::string("cannot write ") + path);
-  std::fwrite(out.data(), 1, out.size(), f);
-  std::fclose(f);
-  return MRT_OK;
-}
-
-int save_rgba(const char* path, const std::vector<float>& img, uint32_t W, uint32_t H) {
-  const std::string p(path);
-  auto ends = [&](const char* s) { const size_t n = std::strlen(s); return p.size() >= n && p.compare(p.size() - n, n, s) == 0; };
-  if (ends(".pfm")) return write_pfm(path, img, W, H);
-  if (ends(".exr")) return write_exr(path, img, W, H);
-  return fail(MRT_ERR_INVALID, "unsupported image extension (use .pfm or .exr)");
-}
-
-// mrt_renderer_read_denoised / _read_resolved: the derived plane `plane` to the
-// host once the renderer's work is done; current: it was computed at the
-// renderer's current size (else the entry point's own `stale` message)
-int read_plane(mrt_renderer* r, DevBuf mrt_renderer::*plane, bool mrt_renderer::*current, const char* stale,
-               float* rgba, size_t count) {
-  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
-  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
-  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
-  if (!(r->*current)) return fail(MRT_ERR_STATE, stale);
-  const int rc = mrt_renderer_sync(r);
+// Every mrt_renderer_read_*: the argument checks, the entry point's own answer
+// to a plane that is not current, the wait for the renderer's work, the copy
+// (host_internal.h ReadSpec; `spec` is asked once r is known not to be null)
+int read_back(mrt_renderer* r, void* out, size_t count, ReadSpec (*spec)(const mrt_renderer*), void* out2) {
+  if (!r || !out) return fail(MRT_ERR_INVALID, "null argument");
+  const ReadSpec s = spec(r);
+  if (count < s.need) return fail(MRT_ERR_INVALID, "output buffer too small");
+  if (!s.current) return fail(MRT_ERR_STATE, s.stale);
+  int rc = s.flush ? exchange_flush(r) : MRT_OK;
   if (rc) return rc;
-  HIP_TRY(hipMemcpy(rgba, (r->*plane).p, need * 4, hipMemcpyDeviceToHost));
+  rc = mrt_renderer_sync(r);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(out, s.src, s.need * 4, hipMemcpyDeviceToHost));
+  if (out2) HIP_TRY(hipMemcpy(out2, s.src2, s.need2 * 4, hipMemcpyDeviceToHost));
   return MRT_OK;
 }
 
-// mrt_renderer_save_image / _save_denoised / _save_resolved: what `read` returns, to `path`
+// every mrt_renderer_save_*: what `read` returns, to `path`
 int save_read(mrt_renderer* r, const char* path, int (*read)(mrt_renderer*, float*, size_t)) {
   if (!r || !path) return fail(MRT_ERR_INVALID, "null argument");
   const uint32_t W = r->desc.width, H = r->desc.height;
   std::vector<float> img((size_t)W * H * 4);
   const int rc = read(r, img.data(), img.size());
   if (rc) return rc;
-  return save_rgba(path, img, W, H);
+  std::string err;
+  bool io = false;
+  return mrt::save_rgba(path, img, W, H, err, io) ? MRT_OK : fail(io ? MRT_ERR_IO : MRT_ERR_INVALID, err);
 }
 
-// the guide planes of the camera in force, on the main stream (allocated here
-// when neither a denoise nor a move has made them yet).  The same allocation
-// and trace as in mrt_renderer_denoise, which stays as it was: keep the two in
-// step.  Known cost of leaving it alone: a renderer that moves before it has
-// a denoised buffer (made by the first mrt_renderer_denoise or
-// _denoise_resolved) has its guide planes freed (a host-synchronising
-// hipFree), re-made and traced again by its first mrt_renderer_denoise, whose
-// first-call test looks at the denoised buffer only.  Once per renderer and
-// size, and the result is the same.
-int ensure_guides(mrt_renderer* r) {
-  const uint32_t W = r->desc.width, H = r->desc.height;
-  const size_t bytes = (size_t)W * H * 16;
-  if (r->guide_n.bytes != bytes || !r->guide_n.p || r->guide_p.bytes != bytes || !r->guide_p.p) {
-    r->guides_current = false;
-    HIP_TRY(r->guide_n.alloc(bytes));
-    HIP_TRY(r->guide_p.alloc(bytes));
+// mrt_renderer_set_camera / _move_camera: `cam` (checked) in force — its lists
+// built and uploaded first, so a camera that cannot be installed leaves the
+// renderer as it was: the previous camera in force, nothing reset
+int swap_camera(mrt_renderer* r, const mrt_camera& cam) {
+  const mrt_camera old = r->camera;
+  const bool old_moved = r->camera_moved;
+  r->camera = cam;
+  r->camera_moved = !camera_is_default(cam);
+  const int rc = install_camera(r, false);
+  if (rc) {
+    r->camera = old;
+    r->camera_moved = old_moved;
+    return rc;
   }
-  if (r->guides_current) return MRT_OK;
-  if (!r->guide_spill.p) HIP_TRY(alloc_isect_spill(r->guide_spill, r->scene->dev.max_stack));
-  const int rc = guides_with_spill(r->scene, &r->camera, W, H, r->guide_n.as<float>(), r->guide_p.as<float>(),
-                                   r->desc.flags & MRT_FLAG_PRECISE, r->guide_spill.as<uint32_t>(), r->stream);
-  if (rc) return rc;
-  r->guides_current = true;
-  return MRT_OK;
-}
-
-int temporal_usable(const mrt_renderer* r, const char* what) {
-  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
-  if (r->desc.shard_count > 1)
-    return fail(MRT_ERR_STATE, std::string(what) + ": a sharded renderer keeps no temporal history");
-  return MRT_OK;
-}
-
-// while the extra image E holds samples (adaptive sampling), every resolve is
-// followed by the counted merge with it: `out` = merge(out, extra), in place
-int merge_extras(mrt_renderer* r, DevBuf& out, const DevBuf& extra) {
-  if (!r->extras_valid) return MRT_OK;
-  return mrt_counted_merge(out.as<float>(), extra.as<float>(), out.as<float>(), r->desc.width, r->desc.height,
-                           r->desc.flags & MRT_FLAG_PRECISE, r->stream);
-}
-
-// resolve(image, frame_index, history if valid) into `out`, on the main stream
-int resolve_into(mrt_renderer* r, DevBuf& out) {
-  const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
-  if (out.bytes != bytes || !out.p) HIP_TRY(out.alloc(bytes));
-  const int rc = mrt_temporal_resolve(r->image, r->frame_index, r->history_valid ? r->history.as<float>() : nullptr,
-                                      out.as<float>(), r->desc.width, r->desc.height, r->stream);
-  return rc ? rc : merge_extras(r, out, r->extra);
-}
-
-// the same for the moments image and its history (MRT_FLAG_MOMENTS)
-int resolve_moments_into(mrt_renderer* r, DevBuf& out) {
-  const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
-  if (out.bytes != bytes || !out.p) HIP_TRY(out.alloc(bytes));
-  const int rc = mrt_temporal_resolve(r->moments.as<float>(), r->frame_index,
-                                      r->history_valid ? r->moments_history.as<float>() : nullptr, out.as<float>(),
-                                      r->desc.width, r->desc.height, r->stream);
-  return rc ? rc : merge_extras(r, out, r->extra_moments);
-}
-
-int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src);   // below
-
-// ---- adaptive sampling (include/mrt.h: mrt_renderer_refine) ----
-int refine_usable(const mrt_renderer* r, const char* what) {
-  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
-  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
-    return fail(MRT_ERR_STATE, std::string(what) + ": the renderer was created without MRT_FLAG_MOMENTS");
-  if (r->desc.shard_count > 1) return fail(MRT_ERR_STATE, std::string(what) + ": not on a sharded renderer");
-  if (r->desc.flags & MRT_FLAG_STATIC_NOISE)
-    return fail(MRT_ERR_STATE, std::string(what) + ": not with MRT_FLAG_STATIC_NOISE (every extra frame would repeat)");
-  if (!r->path_mode && !r->stream_mode)
-    return fail(MRT_ERR_STATE, std::string(what) + ": the per-bounce kernel has no tile-list instantiation");
-  return MRT_OK;
-}
-
-// E, EM, the list, the priorities, the second noise schedule and the list's
-// event: made at the first refine / draw_tiles, E and EM zeroed on the main stream
-int ensure_extras(mrt_renderer* r) {
-  HIP_TRY(hipSetDevice(r->scene->device));
-  const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
-  const size_t tile_bytes = (size_t)r->tiles_x * r->tiles_y * 4;
-  if (!r->list_ready) HIP_TRY(hipEventCreateWithFlags(&r->list_ready, hipEventDisableTiming));
-  if (!r->refine_noise) {
-    r->refine_noise = std::make_unique<mrt::NoiseSchedule>(r->desc.seed ^ MRT_REFINE_SEED_XOR, false);
-    HIP_TRY(r->refine_noise->init());
-  }
-  for (DevBuf* b : {&r->extra, &r->extra_moments})
-    if (b->bytes != bytes || !b->p) {
-      r->extras_current = false;
-      HIP_TRY(b->alloc(bytes));
-    }
-  for (DevBuf* b : {&r->tile_list, &r->tile_priority})
-    if (b->bytes != tile_bytes || !b->p) {
-      r->priority_current = false;
-      r->list_count = 0;
-      HIP_TRY(b->alloc(tile_bytes));
-    }
-  if (!r->extras_current) {
-    HIP_TRY(hipMemsetAsync(r->extra.p, 0, bytes, r->stream));
-    HIP_TRY(hipMemsetAsync(r->extra_moments.p, 0, bytes, r->stream));
-    r->extras_current = true;
-    r->extras_valid = false;
-  }
-  return MRT_OK;
-}
-
-// `frames` extra frames of the `count` tiles of the device list (host_list:
-// uploaded first) into E / EM, from the refine schedule at the extra-frame counter
-int draw_extra(mrt_renderer* r, const uint32_t* host_list, uint32_t count, uint32_t frames) {
-  DrawSource src;
-  src.noise = r->refine_noise.get();
-  src.f0 = r->refine_stats.extra_frames;
-  src.tiles = count;
-  src.host_list = host_list;
-  src.image = r->extra.as<float>();
-  src.moments = r->extra_moments.as<float>();
-  r->refine_stats.extra_frames += frames;   // whatever becomes of the draw: no noise is ever read twice
-  const int rc = draw_frames(r, frames, src);
-  if (rc) return rc;
-  r->extras_valid = true;
-  r->list_count = count;
-  r->refine_stats.passes += 1;
-  r->refine_stats.tile_frames += (uint64_t)count * frames;
-  return MRT_OK;
-}
-
-// mrt_renderer_read_extra / _read_extra_moments
-int read_extra_plane(mrt_renderer* r, const DevBuf& plane, float* rgba, size_t count) {
-  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
-  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
-  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
-  if (!r->extras_current) return fail(MRT_ERR_STATE, "no refine or draw_tiles has run at the renderer's current size");
-  const int rc = mrt_renderer_sync(r);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(rgba, plane.p, need * 4, hipMemcpyDeviceToHost));
+  r->guides_current = false;   // the guide planes were traced with the previous camera
   return MRT_OK;
 }
 
@@ -694,9 +505,9 @@ int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src) {
     }
     if (src.host_list) {
       std::memcpy(d.list_host, src.host_list, (size_t)src.tiles * 4);
-      HIP_TRY(hipMemcpyAsync(r->tile_list.p, d.list_host, (size_t)src.tiles * 4, hipMemcpyHostToDevice, r->stream));
+      HIP_TRY(hipMemcpyAsync(src.list, d.list_host, (size_t)src.tiles * 4, hipMemcpyHostToDevice, r->stream));
     } else {
-      HIP_TRY(hipMemcpyAsync(d.list_host, r->tile_list.p, (size_t)src.tiles * 4, hipMemcpyDeviceToHost, r->stream));
+      HIP_TRY(hipMemcpyAsync(d.list_host, src.list, (size_t)src.tiles * 4, hipMemcpyDeviceToHost, r->stream));
     }
     HIP_TRY(hipEventRecord(r->list_ready, r->stream));
   }
@@ -799,7 +610,8 @@ int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src) {
   return MRT_OK;
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace mrt
 
 extern "C" {
 
@@ -944,29 +756,8 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   r->desc.width = width;
   r->desc.height = height;
   r->x.slab_floats = 0;    // the exchange buffers are re-sized for the new image at the next exchange
-  r->guides_current = r->denoised_current = false;
-  r->history_valid = r->resolved_current = false;
-  r->variance_current = false;
-  r->clamped_current = false;
-  r->extras_current = r->extras_valid = r->priority_current = false;   // re-made (and zeroed) by the next refine / draw_tiles
-  r->tile_error_current = false;
-  r->list_count = 0;
-  if (r->denoised.p) {     // a renderer that has denoised keeps its buffers, at the new size
-    const size_t bytes = (size_t)width * height * 16;
-    HIP_TRY(r->guide_n.alloc(bytes));
-    HIP_TRY(r->guide_p.alloc(bytes));
-    HIP_TRY(r->denoised.alloc(bytes));
-    HIP_TRY(r->denoise_scratch.alloc(bytes));
-  }
-  {   // likewise the temporal history's buffers, each where it exists
-    const size_t bytes = (size_t)width * height * 16;
-    for (DevBuf* b : {&r->guide_n, &r->guide_p, &r->prev_guide_n, &r->prev_guide_p, &r->temporal_prev, &r->history,
-                      &r->resolved, &r->moments_prev, &r->moments_history, &r->moments_resolved})
-      if (b->p && b->bytes != bytes) HIP_TRY(b->alloc(bytes));
-    if (r->variance.p && r->variance.bytes != bytes / 4) HIP_TRY(r->variance.alloc(bytes / 4));
-    if (r->clamped.p && r->clamped.bytes != bytes + 16) HIP_TRY(r->clamped.alloc(bytes + 16));
-  }
-  return alloc_frame_buffers(r);
+  rc = post_resize(r);     // everything derived from the image: stale, its buffers re-made at the new size
+  return rc ? rc : alloc_frame_buffers(r);
 }
 
 int mrt_renderer_reset(mrt_renderer* r) {
@@ -981,12 +772,8 @@ int mrt_renderer_reset(mrt_renderer* r) {
     HIP_TRY(hipMemsetAsync(r->image, 0, (size_t)r->desc.width * r->desc.height * 16, r->stream));
     r->image_foreign = false;
   }
-  if (r->extras_valid) {      // the extra samples go with the frames they refined (stream-ordered, as above)
-    const size_t bytes = (size_t)r->desc.width * r->desc.height * 16;
-    HIP_TRY(hipMemsetAsync(r->extra.p, 0, bytes, r->stream));
-    HIP_TRY(hipMemsetAsync(r->extra_moments.p, 0, bytes, r->stream));
-    r->extras_valid = false;
-  }
+  rc = post_reset(r);   // samples beside the image go with its frames (stream-ordered, as above)
+  if (rc) return rc;
   r->frame_index = 0;
   r->stats.frame_index = 0;   // cumulative counters (paths, A, kernel time) persist
   r->history_valid = false;   // (mrt_renderer_move_camera sets it again once it has reprojected)
@@ -997,20 +784,8 @@ int mrt_renderer_set_camera(mrt_renderer* r, const mrt_camera* cam) {
   if (!r) return fail(MRT_ERR_INVALID, "null renderer");
   int rc = mrt_camera_check(cam);
   if (rc) return rc;
-  // lists and upload first: a camera that cannot be installed leaves the
-  // renderer as it was — the previous camera in force, nothing reset
-  const mrt_camera old = r->camera;
-  const bool old_moved = r->camera_moved;
-  r->camera = *cam;
-  r->camera_moved = !camera_is_default(*cam);
-  rc = install_camera(r, false);
-  if (rc) {
-    r->camera = old;
-    r->camera_moved = old_moved;
-    return rc;
-  }
-  r->guides_current = false;   // the guide planes were traced with the previous camera
-  return mrt_renderer_reset(r);
+  rc = swap_camera(r, *cam);
+  return rc ? rc : mrt_renderer_reset(r);
 }
 
 int mrt_renderer_get_camera(const mrt_renderer* r, mrt_camera* out) {
@@ -1076,586 +851,12 @@ int mrt_renderer_stream(mrt_renderer* r, void** stream) {
 }
 
 int mrt_renderer_read_image(mrt_renderer* r, float* rgba, size_t count) {
-  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
-  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
-  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
-  int rc = exchange_flush(r);   // a deferred (overlapped) exchange lands first
-  if (rc) return rc;
-  rc = mrt_renderer_sync(r);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(rgba, r->image, need * 4, hipMemcpyDeviceToHost));
-  return MRT_OK;
+  return read_back(r, rgba, count, [](const mrt_renderer* r) {   // (flush: a deferred, overlapped exchange lands first)
+    return ReadSpec{(size_t)r->desc.width * r->desc.height * 4, r->image, true, nullptr, nullptr, 0, /*flush*/ true};
+  });
 }
 
 int mrt_renderer_save_image(mrt_renderer* r, const char* path) { return save_read(r, path, mrt_renderer_read_image); }
-
-int mrt_renderer_denoise(mrt_renderer* r, const mrt_denoise_params* params) {
-  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
-  if (r->frame_index == 0)
-    return fail(MRT_ERR_STATE, "mrt_renderer_denoise: no frame accumulated since create, resize, reset or set_camera");
-  mrt_denoise_params p;
-  if (params) p = *params;
-  else (void)mrt_denoise_params_default(r->frame_index, &p);
-  int rc = mrt_denoise_params_check(&p);
-  if (rc) return rc;
-  const uint32_t W = r->desc.width, H = r->desc.height;
-  const size_t bytes = (size_t)W * H * 16;
-  HIP_TRY(hipSetDevice(r->scene->device));
-  if (r->denoised.bytes != bytes || !r->denoised.p) {   // first denoise (resize re-makes existing buffers)
-    r->guides_current = r->denoised_current = false;
-    HIP_TRY(r->guide_n.alloc(bytes));
-    HIP_TRY(r->guide_p.alloc(bytes));
-    HIP_TRY(r->denoised.alloc(bytes));
-    HIP_TRY(r->denoise_scratch.alloc(bytes));
-  }
-  rc = exchange_flush(r);   // a deferred (overlapped) exchange lands in the image first
-  if (rc) return rc;
-  if (!r->guides_current) {
-    if (!r->guide_spill.p) HIP_TRY(alloc_isect_spill(r->guide_spill, r->scene->dev.max_stack));
-    rc = guides_with_spill(r->scene, &r->camera, W, H, r->guide_n.as<float>(), r->guide_p.as<float>(),
-                           r->desc.flags & MRT_FLAG_PRECISE, r->guide_spill.as<uint32_t>(), r->stream);
-    if (rc) return rc;
-    r->guides_current = true;
-  }
-  rc = mrt_denoise(r->image, r->guide_n.as<float>(), r->guide_p.as<float>(), r->denoised.as<float>(),
-                   r->denoise_scratch.as<float>(), W, H, &p, r->stream);
-  if (rc) return rc;
-  r->denoised_current = true;
-  return MRT_OK;
-}
-
-int mrt_renderer_read_denoised(mrt_renderer* r, float* rgba, size_t count) {
-  return read_plane(r, &mrt_renderer::denoised, &mrt_renderer::denoised_current,
-                    "no denoise has run at the renderer's current size", rgba, count);
-}
-
-int mrt_renderer_save_denoised(mrt_renderer* r, const char* path) { return save_read(r, path, mrt_renderer_read_denoised); }
-
-// ---- temporal history (include/mrt.h: mrt_renderer_move_camera) -------------
-int mrt_renderer_move_camera(mrt_renderer* r, const mrt_camera* cam, const mrt_reproject_params* params) {
-  int rc = temporal_usable(r, "mrt_renderer_move_camera");
-  if (rc) return rc;
-  rc = mrt_camera_check(cam);
-  if (rc) return rc;
-  mrt_reproject_params p;
-  if (params) p = *params;
-  else (void)mrt_reproject_params_default(&p);
-  rc = mrt_reproject_params_check(&p);
-  if (rc) return rc;
-  if (r->frame_index == 0 && !r->history_valid) return mrt_renderer_set_camera(r, cam);   // nothing to carry
-  const uint32_t W = r->desc.width, H = r->desc.height;
-  const size_t bytes = (size_t)W * H * 16;
-  HIP_TRY(hipSetDevice(r->scene->device));
-  for (DevBuf* b : {&r->prev_guide_n, &r->prev_guide_p, &r->temporal_prev, &r->history})   // the first move only
-    if (b->bytes != bytes || !b->p) HIP_TRY(b->alloc(bytes));
-  const bool moments = (r->desc.flags & MRT_FLAG_MOMENTS) != 0;
-  if (moments)
-    for (DevBuf* b : {&r->moments_prev, &r->moments_history})
-      if (b->bytes != bytes || !b->p) HIP_TRY(b->alloc(bytes));
-  // what the old camera saw: its guide planes, and everything accumulated
-  // through it (a scratch image: the history itself is replaced last)
-  rc = ensure_guides(r);
-  if (rc) return rc;
-  rc = resolve_into(r, r->temporal_prev);
-  if (rc) return rc;
-  if (moments) {   // the moments travel with the colour, through the same two kernels
-    rc = resolve_moments_into(r, r->moments_prev);
-    if (rc) return rc;
-  }
-  // the new camera, as mrt_renderer_set_camera installs it: failing here
-  // leaves the previous camera in force, nothing reset, the history as it was
-  const mrt_camera old = r->camera;
-  const bool old_moved = r->camera_moved;
-  r->camera = *cam;
-  r->camera_moved = !camera_is_default(*cam);
-  rc = install_camera(r, false);
-  if (rc) {
-    r->camera = old;
-    r->camera_moved = old_moved;
-    return rc;
-  }
-  std::swap(r->guide_n.p, r->prev_guide_n.p);   // equal sizes: the planes of `old` become the previous ones
-  std::swap(r->guide_p.p, r->prev_guide_p.p);
-  r->guides_current = false;
-  r->history_valid = false;     // from here on a failure leaves the new camera without a history, as set_camera would
-  rc = mrt_renderer_reset(r);
-  if (rc) return rc;
-  rc = ensure_guides(r);
-  if (rc) return rc;
-  rc = mrt_reproject(r->temporal_prev.as<float>(), r->prev_guide_n.as<float>(), r->prev_guide_p.as<float>(), &old,
-                     r->guide_n.as<float>(), r->guide_p.as<float>(), r->history.as<float>(), W, H, &p, r->stream);
-  if (rc) return rc;
-  if (moments) {
-    rc = mrt_reproject(r->moments_prev.as<float>(), r->prev_guide_n.as<float>(), r->prev_guide_p.as<float>(), &old,
-                       r->guide_n.as<float>(), r->guide_p.as<float>(), r->moments_history.as<float>(), W, H, &p,
-                       r->stream);
-    if (rc) return rc;
-  }
-  r->history_valid = true;
-  return MRT_OK;
-}
-
-int mrt_renderer_resolve(mrt_renderer* r) {
-  int rc = temporal_usable(r, "mrt_renderer_resolve");
-  if (rc) return rc;
-  if (r->frame_index == 0 && !r->history_valid)
-    return fail(MRT_ERR_STATE, "mrt_renderer_resolve: no frame accumulated and no valid history");
-  HIP_TRY(hipSetDevice(r->scene->device));
-  rc = resolve_into(r, r->resolved);
-  if (rc) return rc;
-  r->resolved_current = true;
-  return MRT_OK;
-}
-
-int mrt_renderer_read_resolved(mrt_renderer* r, float* rgba, size_t count) {
-  return read_plane(r, &mrt_renderer::resolved, &mrt_renderer::resolved_current,
-                    "no resolve has run at the renderer's current size", rgba, count);
-}
-
-int mrt_renderer_save_resolved(mrt_renderer* r, const char* path) { return save_read(r, path, mrt_renderer_read_resolved); }
-
-int mrt_renderer_denoise_resolved(mrt_renderer* r, const mrt_denoise_params* params) {
-  int rc = temporal_usable(r, "mrt_renderer_denoise_resolved");
-  if (rc) return rc;
-  if (r->frame_index == 0 && !r->history_valid)
-    return fail(MRT_ERR_STATE, "mrt_renderer_denoise_resolved: no frame accumulated and no valid history");
-  mrt_denoise_params p;
-  if (params) p = *params;
-  else (void)mrt_denoise_params_default(std::max<uint64_t>(r->frame_index, 1), &p);
-  rc = mrt_denoise_params_check(&p);
-  if (rc) return rc;
-  const uint32_t W = r->desc.width, H = r->desc.height;
-  const size_t bytes = (size_t)W * H * 16;
-  HIP_TRY(hipSetDevice(r->scene->device));
-  for (DevBuf* b : {&r->denoised, &r->denoise_scratch})
-    if (b->bytes != bytes || !b->p) {
-      r->denoised_current = false;
-      HIP_TRY(b->alloc(bytes));
-    }
-  rc = mrt_renderer_resolve(r);
-  if (rc) return rc;
-  rc = ensure_guides(r);
-  if (rc) return rc;
-  rc = mrt_denoise(r->resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(), r->denoised.as<float>(),
-                   r->denoise_scratch.as<float>(), W, H, &p, r->stream);
-  if (rc) return rc;
-  r->denoised_current = true;
-  return MRT_OK;
-}
-
-// ---- variance-guided denoising (include/mrt.h: mrt_renderer_denoise_variance) ----
-int mrt_renderer_read_moments(mrt_renderer* r, float* rgba, size_t count) {
-  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
-  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
-  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
-  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
-    return fail(MRT_ERR_STATE, "mrt_renderer_read_moments: the renderer was created without MRT_FLAG_MOMENTS");
-  const int rc = mrt_renderer_sync(r);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(rgba, r->moments.p, need * 4, hipMemcpyDeviceToHost));
-  return MRT_OK;
-}
-
-int mrt_renderer_moments(mrt_renderer* r, float** device_moments) {
-  if (!r || !device_moments) return fail(MRT_ERR_INVALID, "null argument");
-  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
-    return fail(MRT_ERR_STATE, "mrt_renderer_moments: the renderer was created without MRT_FLAG_MOMENTS");
-  *device_moments = r->moments.as<float>();
-  return MRT_OK;
-}
-
-int mrt_renderer_denoise_variance(mrt_renderer* r, const mrt_svgf_params* params) {
-  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
-  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
-    return fail(MRT_ERR_STATE, "mrt_renderer_denoise_variance: the renderer was created without MRT_FLAG_MOMENTS");
-  if (r->frame_index == 0 && !r->history_valid)
-    return fail(MRT_ERR_STATE, "mrt_renderer_denoise_variance: no frame accumulated and no valid history");
-  mrt_svgf_params p;
-  if (params) p = *params;
-  else (void)mrt_svgf_params_default(&p);
-  int rc = mrt_svgf_params_check(&p);
-  if (rc) return rc;
-  const uint32_t W = r->desc.width, H = r->desc.height;
-  const size_t bytes = (size_t)W * H * 16;
-  HIP_TRY(hipSetDevice(r->scene->device));
-  for (DevBuf* b : {&r->denoised, &r->denoise_scratch})
-    if (b->bytes != bytes || !b->p) {
-      r->denoised_current = false;
-      HIP_TRY(b->alloc(bytes));
-    }
-  if (r->variance.bytes != bytes / 4 || !r->variance.p) {
-    r->variance_current = false;
-    HIP_TRY(r->variance.alloc(bytes / 4));
-  }
-  rc = ensure_guides(r);
-  if (rc) return rc;
-  rc = mrt_renderer_resolve(r);
-  if (rc) return rc;
-  rc = resolve_moments_into(r, r->moments_resolved);
-  if (rc) return rc;
-  const float* filtered = r->resolved.as<float>();
-  if (r->firefly_on) {   // the filter's input is the clamped copy; the resolved buffer stays as it is
-    if (r->clamped.bytes != bytes + 16 || !r->clamped.p) {
-      r->clamped_current = false;
-      HIP_TRY(r->clamped.alloc(bytes + 16));
-    }
-    rc = mrt_firefly_clamp(r->resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
-                           r->clamped.as<float>(), reinterpret_cast<uint32_t*>(r->clamped.as<char>() + bytes), W, H,
-                           &r->firefly, r->stream);
-    if (rc) return rc;
-    r->clamped_current = true;
-    filtered = r->clamped.as<float>();
-  }
-  rc = mrt_variance(r->moments_resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
-                    r->variance.as<float>(), W, H, &p, r->stream);
-  if (rc) return rc;
-  r->variance_current = true;
-  rc = mrt_denoise_variance(filtered, r->variance.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
-                            r->denoised.as<float>(), r->denoise_scratch.as<float>(), nullptr, W, H, &p, r->stream);
-  if (rc) return rc;
-  r->denoised_current = true;
-  return MRT_OK;
-}
-
-// ---- firefly suppression (include/mrt.h: mrt_renderer_set_firefly) ----------
-int mrt_renderer_set_firefly(mrt_renderer* r, const mrt_firefly_params* params) {
-  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
-  if (!(r->desc.flags & MRT_FLAG_MOMENTS))
-    return fail(MRT_ERR_STATE, "mrt_renderer_set_firefly: the renderer was created without MRT_FLAG_MOMENTS");
-  if (!params) {
-    r->firefly_on = false;
-    return MRT_OK;
-  }
-  const int rc = mrt_firefly_params_check(params);
-  if (rc) return rc;
-  r->firefly = *params;
-  r->firefly_on = true;
-  return MRT_OK;
-}
-
-int mrt_renderer_get_firefly(const mrt_renderer* r, mrt_firefly_params* out, uint32_t* enabled) {
-  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
-  if (out) *out = r->firefly;
-  if (enabled) *enabled = r->firefly_on ? 1u : 0u;
-  return MRT_OK;
-}
-
-int mrt_renderer_read_clamped(mrt_renderer* r, float* rgba, size_t count, uint32_t* clamped_pixels) {
-  const int rc = read_plane(r, &mrt_renderer::clamped, &mrt_renderer::clamped_current,
-                            "no firefly clamp has run at the renderer's current size", rgba, count);
-  if (rc) return rc;
-  if (clamped_pixels)
-    HIP_TRY(hipMemcpy(clamped_pixels, r->clamped.as<char>() + (size_t)r->desc.width * r->desc.height * 16, 4,
-                      hipMemcpyDeviceToHost));
-  return MRT_OK;
-}
-
-int mrt_renderer_read_variance(mrt_renderer* r, float* plane, size_t count) {
-  if (!r || !plane) return fail(MRT_ERR_INVALID, "null argument");
-  const size_t need = (size_t)r->desc.width * r->desc.height;
-  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
-  if (!r->variance_current)
-    return fail(MRT_ERR_STATE, "no mrt_renderer_denoise_variance has run at the renderer's current size");
-  const int rc = mrt_renderer_sync(r);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(plane, r->variance.p, need * 4, hipMemcpyDeviceToHost));
-  return MRT_OK;
-}
-
-// ---- adaptive sampling (include/mrt.h: mrt_renderer_refine) -----------------
-int mrt_renderer_draw_tiles(mrt_renderer* r, const uint32_t* tiles, uint32_t count, uint32_t frames) {
-  int rc = refine_usable(r, "mrt_renderer_draw_tiles");
-  if (rc) return rc;
-  const uint32_t T = r->tiles_x * r->tiles_y;
-  if (!tiles || count == 0 || count > T || frames == 0)
-    return fail(MRT_ERR_INVALID, "mrt_renderer_draw_tiles: need a list of 1..tiles_x * tiles_y tiles and frames >= 1");
-  std::vector<bool> seen(T, false);
-  for (uint32_t k = 0; k < count; ++k) {
-    if (tiles[k] >= T) return fail(MRT_ERR_INVALID, "mrt_renderer_draw_tiles: tile " + std::to_string(tiles[k]) + " out of range");
-    if (seen[tiles[k]]) return fail(MRT_ERR_INVALID, "mrt_renderer_draw_tiles: tile " + std::to_string(tiles[k]) + " listed twice");
-    seen[tiles[k]] = true;
-  }
-  rc = ensure_extras(r);
-  if (rc) return rc;
-  return draw_extra(r, tiles, count, frames);
-}
-
-int mrt_renderer_refine(mrt_renderer* r, uint32_t frames, uint32_t tile_count, const mrt_adaptive_params* params) {
-  int rc = refine_usable(r, "mrt_renderer_refine");
-  if (rc) return rc;
-  const uint32_t W = r->desc.width, H = r->desc.height, T = r->tiles_x * r->tiles_y;
-  if (frames == 0 || tile_count == 0 || tile_count > T || T > mrt::kMaxSelectTiles)
-    return fail(MRT_ERR_INVALID, "mrt_renderer_refine: need frames >= 1 and 1 <= tile_count <= tiles_x * tiles_y <= 16384");
-  mrt_adaptive_params p;
-  if (params) p = *params;
-  else (void)mrt_adaptive_params_default(&p);
-  rc = mrt_adaptive_params_check(&p);
-  if (rc) return rc;
-  if (r->frame_index == 0 && !r->history_valid)
-    return fail(MRT_ERR_STATE, "mrt_renderer_refine: no frame accumulated and no valid history");
-  mrt_svgf_params sp;
-  (void)mrt_svgf_params_default(&sp);
-  rc = ensure_extras(r);
-  if (rc) return rc;
-  const size_t bytes = (size_t)W * H * 16;
-  if (r->variance.bytes != bytes / 4 || !r->variance.p) {
-    r->variance_current = false;
-    HIP_TRY(r->variance.alloc(bytes / 4));
-  }
-  rc = ensure_guides(r);
-  if (rc) return rc;
-  rc = mrt_renderer_resolve(r);
-  if (rc) return rc;
-  rc = resolve_moments_into(r, r->moments_resolved);
-  if (rc) return rc;
-  rc = mrt_variance(r->moments_resolved.as<float>(), r->guide_n.as<float>(), r->guide_p.as<float>(),
-                    r->variance.as<float>(), W, H, &sp, r->stream);
-  if (rc) return rc;
-  r->variance_current = true;
-  rc = mrt_tile_priority(r->resolved.as<float>(), r->variance.as<float>(), r->guide_n.as<float>(),
-                         r->tile_priority.as<float>(), W, H, &p, r->desc.flags & MRT_FLAG_PRECISE, r->stream);
-  if (rc) return rc;
-  r->priority_current = true;
-  rc = mrt_tile_select(r->tile_priority.as<float>(), T, tile_count, r->tile_list.as<uint32_t>(), r->stream);
-  if (rc) return rc;
-  return draw_extra(r, nullptr, tile_count, frames);
-}
-
-int mrt_renderer_read_extra(mrt_renderer* r, float* rgba, size_t count) {
-  return r ? read_extra_plane(r, r->extra, rgba, count) : fail(MRT_ERR_INVALID, "null argument");
-}
-
-int mrt_renderer_read_extra_moments(mrt_renderer* r, float* rgba, size_t count) {
-  return r ? read_extra_plane(r, r->extra_moments, rgba, count) : fail(MRT_ERR_INVALID, "null argument");
-}
-
-int mrt_renderer_read_tile_priority(mrt_renderer* r, float* priority, size_t count) {
-  if (!r || !priority) return fail(MRT_ERR_INVALID, "null argument");
-  const size_t T = (size_t)r->tiles_x * r->tiles_y;
-  if (count < T) return fail(MRT_ERR_INVALID, "output buffer too small");
-  if (!r->priority_current) return fail(MRT_ERR_STATE, "no refine has run at the renderer's current size");
-  const int rc = mrt_renderer_sync(r);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(priority, r->tile_priority.p, T * 4, hipMemcpyDeviceToHost));
-  return MRT_OK;
-}
-
-int mrt_renderer_read_tile_list(mrt_renderer* r, uint32_t* tiles, size_t capacity, uint32_t* count) {
-  if (!r || !tiles || !count) return fail(MRT_ERR_INVALID, "null argument");
-  if (r->list_count == 0) return fail(MRT_ERR_STATE, "no refine or draw_tiles has run at the renderer's current size");
-  if (capacity < r->list_count) return fail(MRT_ERR_INVALID, "output buffer too small");
-  const int rc = mrt_renderer_sync(r);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(tiles, r->tile_list.p, (size_t)r->list_count * 4, hipMemcpyDeviceToHost));
-  *count = r->list_count;
-  return MRT_OK;
-}
-
-int mrt_renderer_refine_stats(mrt_renderer* r, mrt_refine_stats* stats) {
-  if (!r || !stats) return fail(MRT_ERR_INVALID, "null argument");
-  const int rc = finalize_pending(r);   // counts the pixels of the lists not yet read back
-  if (rc) return rc;
-  *stats = r->refine_stats;
-  return MRT_OK;
-}
-
-// ---- sampling to a target error (include/mrt.h: mrt_renderer_converge) -------
-namespace {
-// everything an estimate checks, before it changes anything
-int estimate_usable(mrt_renderer* r, const char* what, const mrt_svgf_params& sp, const mrt_adaptive_params& ap,
-                    float threshold) {
-  int rc = refine_usable(r, what);
-  if (rc) return rc;
-  if (r->tiles_x * r->tiles_y > mrt::kMaxSelectTiles)
-    return fail(MRT_ERR_INVALID, std::string(what) + ": more than 16384 tiles");
-  if (!std::isfinite(threshold) || threshold < 0.0f)
-    return fail(MRT_ERR_INVALID, std::string(what) + ": the threshold must be finite and not negative");
-  rc = mrt_svgf_params_check(&sp);
-  if (rc) return rc;
-  rc = mrt_adaptive_params_check(&ap);
-  if (rc) return rc;
-  if (r->frame_index < sp.min_frames && !r->history_valid)
-    return fail(MRT_ERR_STATE, std::string(what) + ": fewer than min_frames frames accumulated and no valid history");
-  return MRT_OK;
-}
-
-// one estimate (estimate_usable has passed): denoise_variance, the per-tile
-// error, the tiles above `threshold` into the tile list, and the summary
-// brought to the host — the one host wait
-int estimate(mrt_renderer* r, const mrt_svgf_params& sp, const mrt_adaptive_params& ap, float threshold,
-             mrt_error_summary* out) {
-  const uint32_t W = r->desc.width, H = r->desc.height, T = r->tiles_x * r->tiles_y;
-  int rc = ensure_extras(r);   // (the tile list lives with E and EM)
-  if (rc) return rc;
-  for (DevBuf* b : {&r->tile_error, &r->tile_pixels})
-    if (b->bytes != (size_t)T * 4 || !b->p) {
-      r->tile_error_current = false;
-      HIP_TRY(b->alloc((size_t)T * 4));
-    }
-  if (!r->error_summary.p) HIP_TRY(r->error_summary.alloc(sizeof(mrt_error_summary)));
-  if (!r->summary_host)
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->summary_host), sizeof(mrt_error_summary), hipHostMallocDefault));
-  rc = mrt_renderer_denoise_variance(r, &sp);
-  if (rc) return rc;
-  rc = mrt_tile_error(r->denoised.as<float>(), r->variance.as<float>(), r->guide_n.as<float>(),
-                      r->tile_error.as<float>(), r->tile_pixels.as<uint32_t>(), W, H, &ap,
-                      r->desc.flags & MRT_FLAG_PRECISE, r->stream);
-  if (rc) return rc;
-  r->tile_error_current = true;
-  r->list_count = 0;   // the list is rewritten: nothing of it is known until the summary is back
-  rc = mrt_tile_threshold(r->tile_error.as<float>(), r->tile_pixels.as<uint32_t>(), T, threshold, T,
-                          r->tile_list.as<uint32_t>(), r->error_summary.as<mrt_error_summary>(), r->stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(r->summary_host, r->error_summary.p, sizeof(mrt_error_summary), hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
-  *out = *r->summary_host;
-  r->list_count = out->tiles_listed;
-  return MRT_OK;
-}
-}  // namespace
-
-int mrt_renderer_error(mrt_renderer* r, const mrt_svgf_params* svgf, float luminance_floor, float threshold,
-                       mrt_error_summary* out) {
-  if (!r || !out) return fail(MRT_ERR_INVALID, "null argument");
-  mrt_svgf_params sp;
-  if (svgf) sp = *svgf;
-  else (void)mrt_svgf_params_default(&sp);
-  mrt_adaptive_params ap;
-  (void)mrt_adaptive_params_default(&ap);
-  if (luminance_floor != 0.0f) ap.luminance_floor = luminance_floor;
-  const int rc = estimate_usable(r, "mrt_renderer_error", sp, ap, threshold);
-  return rc ? rc : estimate(r, sp, ap, threshold, out);
-}
-
-int mrt_renderer_read_tile_error(mrt_renderer* r, float* mean_error, uint32_t* pixels, size_t count) {
-  if (!r || !mean_error || !pixels) return fail(MRT_ERR_INVALID, "null argument");
-  const size_t T = (size_t)r->tiles_x * r->tiles_y;
-  if (count < T) return fail(MRT_ERR_INVALID, "output buffer too small");
-  if (!r->tile_error_current) return fail(MRT_ERR_STATE, "no error estimate has run at the renderer's current size");
-  const int rc = mrt_renderer_sync(r);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(mean_error, r->tile_error.p, T * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(pixels, r->tile_pixels.p, T * 4, hipMemcpyDeviceToHost));
-  return MRT_OK;
-}
-
-int mrt_renderer_converge(mrt_renderer* r, const mrt_converge_params* params, mrt_converge_result* out) {
-  if (!r || !out) return fail(MRT_ERR_INVALID, "null argument");
-  mrt_converge_params p;
-  if (params) p = *params;
-  else (void)mrt_converge_params_default(&p);
-  int rc = mrt_converge_params_check(&p);
-  if (rc) return rc;
-  mrt_svgf_params sp;
-  (void)mrt_svgf_params_default(&sp);
-  mrt_adaptive_params ap;
-  ap.luminance_floor = p.luminance_floor;
-  rc = estimate_usable(r, "mrt_renderer_converge", sp, ap, p.target_error);
-  if (rc) return rc;
-  const uint32_t T = r->tiles_x * r->tiles_y;
-  const uint32_t cap = p.max_tiles ? std::min(p.max_tiles, T) : T;
-  mrt_converge_result res{};
-  for (;;) {
-    mrt_error_summary s;
-    rc = estimate(r, sp, ap, p.target_error, &s);
-    if (rc) return rc;
-    if (res.passes == 0) res.first = s;
-    res.last = s;
-    if (s.tiles_above == 0) {
-      res.converged = 1;
-      break;
-    }
-    uint64_t n = std::min(s.tiles_above, cap);
-    if (p.max_tile_frames) n = std::min<uint64_t>(n, (p.max_tile_frames - res.tile_frames) / p.frames_per_pass);
-    if (n == 0 || res.passes >= p.max_passes) break;
-    rc = draw_extra(r, nullptr, (uint32_t)n, p.frames_per_pass);   // the n worst: the head of the device list
-    if (rc) return rc;
-    res.passes += 1;
-    res.tile_frames += n * p.frames_per_pass;
-  }
-  *out = res;
-  return MRT_OK;
-}
-
-int mrt_renderer_load_reference(mrt_renderer* r, const char* path) {
-  if (!r || !path) return fail(MRT_ERR_INVALID, "null argument");
-  std::vector<float> img;
-  uint32_t W = 0, H = 0;
-  std::string err;
-  if (!mrt::load_exr(path, img, W, H, err)) return fail(MRT_ERR_IO, err);
-  if (W != r->desc.width || H != r->desc.height)
-    return fail(MRT_ERR_INVALID, "reference image is " + std::to_string(W) + "x" + std::to_string(H) + ", renderer " +
-                                     std::to_string(r->desc.width) + "x" + std::to_string(r->desc.height));
-  HIP_TRY(hipSetDevice(r->scene->device));
-  HIP_TRY(hipStreamSynchronize(r->stream));
-  HIP_TRY(upload(r->reference, img.data(), img.size() * 4));
-  return MRT_OK;
-}
-
-int mrt_renderer_display(mrt_renderer* r, uint32_t flags, float compare_scale, float* rgba, size_t count) {
-  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
-  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
-  if (count < need) return fail(MRT_ERR_INVALID, "output buffer too small");
-  if (((flags >> 8) & 0xFFu) && !r->reference.p) return fail(MRT_ERR_STATE, "compare mode without a loaded reference");
-  const bool denoised = (flags & MRT_DISPLAY_DENOISED) != 0;
-  const bool resolved = (flags & MRT_DISPLAY_RESOLVED) != 0;
-  if (denoised && resolved) return fail(MRT_ERR_INVALID, "MRT_DISPLAY_DENOISED and MRT_DISPLAY_RESOLVED are exclusive");
-  if (denoised && !r->denoised_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_DENOISED without a denoise at the current size");
-  if (resolved && !r->resolved_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_RESOLVED without a resolve at the current size");
-  int rc = exchange_flush(r);
-  if (rc) return rc;
-  if (r->display.bytes < need * 4) HIP_TRY(r->display.alloc(need * 4));
-  rc = mrt_display(denoised ? r->denoised.as<float>() : (resolved ? r->resolved.as<float>() : r->image), r->reference.as<float>(), r->display.as<float>(), r->desc.width, r->desc.height, flags,
-                   compare_scale, r->stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(rgba, r->display.p, need * 4, hipMemcpyDeviceToHost, r->stream));
-  return mrt_renderer_sync(r);
-}
-
-int mrt_renderer_display_enqueue(mrt_renderer* r, uint32_t flags, float compare_scale, uint32_t slot) {
-  if (!r) return fail(MRT_ERR_INVALID, "null renderer");
-  if (slot >= MRT_DISPLAY_SLOTS) return fail(MRT_ERR_INVALID, "display slot >= MRT_DISPLAY_SLOTS");
-  if (((flags >> 8) & 0xFFu) && !r->reference.p) return fail(MRT_ERR_STATE, "compare mode without a loaded reference");
-  const size_t need = (size_t)r->desc.width * r->desc.height * 4;
-  const bool denoised = (flags & MRT_DISPLAY_DENOISED) != 0;
-  const bool resolved = (flags & MRT_DISPLAY_RESOLVED) != 0;
-  if (denoised && resolved) return fail(MRT_ERR_INVALID, "MRT_DISPLAY_DENOISED and MRT_DISPLAY_RESOLVED are exclusive");
-  if (denoised && !r->denoised_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_DENOISED without a denoise at the current size");
-  if (resolved && !r->resolved_current) return fail(MRT_ERR_STATE, "MRT_DISPLAY_RESOLVED without a resolve at the current size");
-  auto& ds = r->shown[slot];
-  if (ds.queued) HIP_TRY(hipEventSynchronize(ds.done));   // its previous copy may still be landing
-  if (ds.floats != need) {
-    if (ds.host) HIP_TRY(hipHostFree(ds.host));
-    ds.host = nullptr;
-    ds.floats = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ds.host), need * 4, hipHostMallocDefault));
-    ds.floats = need;
-  }
-  if (!ds.done) HIP_TRY(hipEventCreateWithFlags(&ds.done, hipEventDisableTiming));
-  int rc = exchange_flush(r);
-  if (rc) return rc;
-  // one device blit buffer: the next blit is queued behind this copy
-  if (r->display.bytes < need * 4) HIP_TRY(r->display.alloc(need * 4));
-  rc = mrt_display(denoised ? r->denoised.as<float>() : (resolved ? r->resolved.as<float>() : r->image), r->reference.as<float>(), r->display.as<float>(),
-                   r->desc.width, r->desc.height, flags, compare_scale, r->stream);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(ds.host, r->display.p, need * 4, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipEventRecord(ds.done, r->stream));
-  ds.queued = true;
-  return MRT_OK;
-}
-
-int mrt_renderer_display_map(mrt_renderer* r, uint32_t slot, const float** rgba, size_t* count) {
-  if (!r || !rgba) return fail(MRT_ERR_INVALID, "null argument");
-  if (slot >= MRT_DISPLAY_SLOTS) return fail(MRT_ERR_INVALID, "display slot >= MRT_DISPLAY_SLOTS");
-  auto& ds = r->shown[slot];
-  if (!ds.queued || ds.floats != (size_t)r->desc.width * r->desc.height * 4)
-    return fail(MRT_ERR_STATE, "display slot not enqueued at the current size");
-  HIP_TRY(hipEventSynchronize(ds.done));
-  *rgba = ds.host;
-  if (count) *count = ds.floats;
-  return MRT_OK;
-}
 
 int mrt_renderer_stats(const mrt_renderer* r, mrt_stats* stats) {
   if (!r || !stats) return fail(MRT_ERR_INVALID, "null argument");
@@ -1681,10 +882,7 @@ int mrt_renderer_destroy(mrt_renderer* r) {
   }
   if (r->x.coll_done) (void)hipEventDestroy(r->x.coll_done);
   if (r->own_image && r->image) (void)hipFree(r->image);
-  for (auto& ds : r->shown) {
-    if (ds.done) (void)hipEventDestroy(ds.done);
-    if (ds.host) (void)hipHostFree(ds.host);
-  }
+  post_destroy(r);
   for (FrameSlot& fs : r->slots) {
     if (fs.acc_done) (void)hipEventDestroy(fs.acc_done);
     if (fs.kernel_done) (void)hipEventDestroy(fs.kernel_done);
@@ -1698,11 +896,8 @@ int mrt_renderer_destroy(mrt_renderer* r) {
     if (d.cleared) (void)hipEventDestroy(d.cleared);
     if (d.copied) (void)hipEventDestroy(d.copied);
     if (d.host) (void)hipHostFree(d.host);
-  }
-  if (r->list_ready) (void)hipEventDestroy(r->list_ready);
-  if (r->summary_host) (void)hipHostFree(r->summary_host);
-  for (DrawRecord& d : r->draws)
     if (d.list_host) (void)hipHostFree(d.list_host);
+  }
   r->refine_noise.reset();
   r->noise.reset();   // joins the worker; the draws reading its chunks have finished (stream synchronised above)
   if (r->own_stream) (void)hipStreamDestroy(r->stream);

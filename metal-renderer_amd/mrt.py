@@ -534,6 +534,11 @@ def _check(rc: int, what: str) -> None:
         raise e
 
 
+def _opt(struct):
+    """An optional struct argument: its address, or NULL for None."""
+    return ctypes.byref(struct) if struct is not None else None
+
+
 def scene_path(name: str) -> str:
     """Path of a scene shipped with the package (metal-renderer_amd/scenes: the
     reference's renderer/Media OBJ/MTL data files, unchanged)."""
@@ -727,13 +732,17 @@ class Renderer:
         _check(lib().mrt_renderer_stream(self._h, ctypes.byref(p)), "mrt_renderer_stream")
         return p.value
 
+    def _read(self, what, shape=None, dtype="float32", *more):
+        """A new array ([H, W, 4] unless `shape` is given) filled by the reader
+        `what`, which takes the renderer, the array, its size and then `more`."""
+        import numpy as np
+        a = np.zeros((self.height, self.width, 4) if shape is None else shape, dtype)
+        _check(getattr(lib(), what)(self._h, ctypes.c_void_p(a.ctypes.data), a.size, *more), what)
+        return a
+
     def read_image(self):
         """[H, W, 4] float32, row 0 = bottom (the reference texture orientation)."""
-        import numpy as np
-        img = np.zeros((self.height, self.width, 4), np.float32)
-        _check(lib().mrt_renderer_read_image(self._h, ctypes.c_void_p(img.ctypes.data), img.size),
-               "mrt_renderer_read_image")
-        return img
+        return self._read("mrt_renderer_read_image")
 
     # -saveCurrentImage
     def save_current_image(self, path: str) -> None:
@@ -744,16 +753,12 @@ class Renderer:
         """Filter the accumulation image into the renderer's denoised buffer,
         enqueued behind the draws queued so far (no host wait); params None =
         DenoiseParams.default(frames accumulated).  The image is not written."""
-        _check(lib().mrt_renderer_denoise(self._h, ctypes.byref(params) if params is not None else None),
+        _check(lib().mrt_renderer_denoise(self._h, _opt(params)),
                "mrt_renderer_denoise")
 
     def read_denoised(self):
         """[H, W, 4] float32 denoised image, row 0 = bottom."""
-        import numpy as np
-        img = np.zeros((self.height, self.width, 4), np.float32)
-        _check(lib().mrt_renderer_read_denoised(self._h, ctypes.c_void_p(img.ctypes.data), img.size),
-               "mrt_renderer_read_denoised")
-        return img
+        return self._read("mrt_renderer_read_denoised")
 
     def save_denoised(self, path: str) -> None:
         _check(lib().mrt_renderer_save_denoised(self._h, path.encode()), "mrt_renderer_save_denoised")
@@ -764,7 +769,7 @@ class Renderer:
         view, as a counted history beside the image (no host wait); params
         None = ReprojectParams.default()."""
         _check(lib().mrt_renderer_move_camera(self._h, ctypes.byref(camera),
-                                              ctypes.byref(params) if params is not None else None),
+                                              _opt(params)),
                "mrt_renderer_move_camera")
 
     def resolve(self) -> None:
@@ -775,11 +780,7 @@ class Renderer:
     def read_resolved(self):
         """[H, W, 4] float32 resolved image, row 0 = bottom; the fourth channel
         is the sample count behind the pixel."""
-        import numpy as np
-        img = np.zeros((self.height, self.width, 4), np.float32)
-        _check(lib().mrt_renderer_read_resolved(self._h, ctypes.c_void_p(img.ctypes.data), img.size),
-               "mrt_renderer_read_resolved")
-        return img
+        return self._read("mrt_renderer_read_resolved")
 
     def save_resolved(self, path: str) -> None:
         _check(lib().mrt_renderer_save_resolved(self._h, path.encode()), "mrt_renderer_save_resolved")
@@ -787,17 +788,13 @@ class Renderer:
     def denoise_resolved(self, params: "DenoiseParams | None" = None) -> None:
         """resolve(), then the A-Trous filter of the resolved buffer into the
         denoised buffer; params None = DenoiseParams.default(max(frames, 1))."""
-        _check(lib().mrt_renderer_denoise_resolved(self._h, ctypes.byref(params) if params is not None else None),
+        _check(lib().mrt_renderer_denoise_resolved(self._h, _opt(params)),
                "mrt_renderer_denoise_resolved")
 
     # ---- variance-guided denoising (include/mrt.h: mrt_renderer_denoise_variance) ----
     def read_moments(self):
         """[H, W, 4] float32 moments image (mean l, mean l*l, 0, 1), row 0 = bottom."""
-        import numpy as np
-        img = np.zeros((self.height, self.width, 4), np.float32)
-        _check(lib().mrt_renderer_read_moments(self._h, ctypes.c_void_p(img.ctypes.data), img.size),
-               "mrt_renderer_read_moments")
-        return img
+        return self._read("mrt_renderer_read_moments")
 
     def moments_ptr(self) -> int:
         p = ctypes.c_void_p()
@@ -808,23 +805,19 @@ class Renderer:
         """resolve(), the variance estimate from the resolved moments, then the
         variance-guided filter of the resolved buffer into the denoised buffer
         (no host wait); params None = SvgfParams.default()."""
-        _check(lib().mrt_renderer_denoise_variance(self._h, ctypes.byref(params) if params is not None else None),
+        _check(lib().mrt_renderer_denoise_variance(self._h, _opt(params)),
                "mrt_renderer_denoise_variance")
 
     def read_variance(self):
         """[H, W] float32: the variance plane the last denoise_variance fed to the filter."""
-        import numpy as np
-        v = np.zeros((self.height, self.width), np.float32)
-        _check(lib().mrt_renderer_read_variance(self._h, ctypes.c_void_p(v.ctypes.data), v.size),
-               "mrt_renderer_read_variance")
-        return v
+        return self._read("mrt_renderer_read_variance", (self.height, self.width))
 
     # ---- firefly suppression (include/mrt.h: mrt_renderer_set_firefly) ----
     def set_firefly(self, params: "FireflyParams | None") -> None:
         """Clamp outliers of the resolved buffer ahead of denoise_variance's
         filter (and so of error_estimate and converge); None switches it off.
         Biased: energy is removed, not redistributed."""
-        _check(lib().mrt_renderer_set_firefly(self._h, ctypes.byref(params) if params is not None else None),
+        _check(lib().mrt_renderer_set_firefly(self._h, _opt(params)),
                "mrt_renderer_set_firefly")
 
     @property
@@ -836,12 +829,8 @@ class Renderer:
 
     def read_clamped(self):
         """([H, W, 4] float32, pixels changed): what the last clamp fed to the filter."""
-        import numpy as np
-        img = np.zeros((self.height, self.width, 4), np.float32)
         n = ctypes.c_uint32()
-        _check(lib().mrt_renderer_read_clamped(self._h, ctypes.c_void_p(img.ctypes.data), img.size, ctypes.byref(n)),
-               "mrt_renderer_read_clamped")
-        return img, n.value
+        return self._read("mrt_renderer_read_clamped", None, "float32", ctypes.byref(n)), n.value
 
     # ---- adaptive sampling (include/mrt.h: mrt_renderer_refine) ----
     def tile_count(self) -> int:
@@ -861,39 +850,25 @@ class Renderer:
         a priority per tile, the `tiles` tiles of highest priority chosen on
         the device, and `frames` extra frames of them (no host wait); params
         None = AdaptiveParams.default()."""
-        _check(lib().mrt_renderer_refine(self._h, frames, tiles, ctypes.byref(params) if params is not None else None),
+        _check(lib().mrt_renderer_refine(self._h, frames, tiles, _opt(params)),
                "mrt_renderer_refine")
-
-    def _read_extra(self, fn, what):
-        import numpy as np
-        img = np.zeros((self.height, self.width, 4), np.float32)
-        _check(fn(self._h, ctypes.c_void_p(img.ctypes.data), img.size), what)
-        return img
 
     def read_extra(self):
         """[H, W, 4] float32 extra image E: (r, g, b, extra samples), row 0 = bottom."""
-        return self._read_extra(lib().mrt_renderer_read_extra, "mrt_renderer_read_extra")
+        return self._read("mrt_renderer_read_extra")
 
     def read_extra_moments(self):
         """[H, W, 4] float32 extra moments EM: (mean l, mean l*l, 0, extra samples)."""
-        return self._read_extra(lib().mrt_renderer_read_extra_moments, "mrt_renderer_read_extra_moments")
+        return self._read("mrt_renderer_read_extra_moments")
 
     def read_tile_priority(self):
         """float32 priorities of the last refine, one per tile (row-major)."""
-        import numpy as np
-        p = np.zeros(self.tile_count(), np.float32)
-        _check(lib().mrt_renderer_read_tile_priority(self._h, ctypes.c_void_p(p.ctypes.data), p.size),
-               "mrt_renderer_read_tile_priority")
-        return p
+        return self._read("mrt_renderer_read_tile_priority", self.tile_count())
 
     def read_tile_list(self):
         """uint32 tile indices the last refine or draw_tiles drew, in rank order."""
-        import numpy as np
-        t = np.zeros(self.tile_count(), np.uint32)
         n = ctypes.c_uint32()
-        _check(lib().mrt_renderer_read_tile_list(self._h, ctypes.c_void_p(t.ctypes.data), t.size, ctypes.byref(n)),
-               "mrt_renderer_read_tile_list")
-        return t[:n.value].copy()
+        return self._read("mrt_renderer_read_tile_list", self.tile_count(), "uint32", ctypes.byref(n))[:n.value].copy()
 
     def refine_stats(self) -> dict:
         s = RefineStats()
@@ -908,8 +883,8 @@ class Renderer:
         `threshold` into the tile list; draws nothing.  Returns the summary
         (ErrorSummary.as_dict()).  Waits for the device once."""
         s = ErrorSummary()
-        _check(lib().mrt_renderer_error(self._h, ctypes.byref(svgf) if svgf is not None else None, luminance_floor,
-                                        threshold, ctypes.byref(s)), "mrt_renderer_error")
+        _check(lib().mrt_renderer_error(self._h, _opt(svgf), luminance_floor, threshold, ctypes.byref(s)),
+               "mrt_renderer_error")
         return s.as_dict()
 
     def read_tile_error(self):
@@ -1079,7 +1054,7 @@ def variance(moments_ptr: int, n_ptr: int, p_ptr: int, variance_ptr: int, width:
              params: "SvgfParams | None", stream=None, sync=True) -> None:
     """The per-pixel variance estimate from counted moments (mrt_variance): W*H floats."""
     _check(lib().mrt_variance(moments_ptr, n_ptr, p_ptr, variance_ptr, width, height,
-                              ctypes.byref(params) if params is not None else None, stream), "mrt_variance")
+                              _opt(params), stream), "mrt_variance")
     if sync:
         synchronize(stream)
 
@@ -1089,7 +1064,7 @@ def denoise_variance(image_ptr: int, variance_ptr: int, n_ptr: int, p_ptr: int, 
                      sync=True) -> None:
     """The variance-guided A-Trous filter (mrt_denoise_variance) on device buffers."""
     _check(lib().mrt_denoise_variance(image_ptr, variance_ptr, n_ptr, p_ptr, out_ptr, scratch_ptr, variance_out_ptr,
-                                      width, height, ctypes.byref(params) if params is not None else None, stream),
+                                      width, height, _opt(params), stream),
            "mrt_denoise_variance")
     if sync:
         synchronize(stream)
@@ -1099,7 +1074,7 @@ def firefly_clamp(image_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, clamped_
                   height: int, params: "FireflyParams | None", stream=None, sync=True) -> None:
     """The outlier clamp (mrt_firefly_clamp) on device buffers; clamped_ptr: one uint32 or None."""
     _check(lib().mrt_firefly_clamp(image_ptr, n_ptr, p_ptr, out_ptr, clamped_ptr, width, height,
-                                   ctypes.byref(params) if params is not None else None, stream), "mrt_firefly_clamp")
+                                   _opt(params), stream), "mrt_firefly_clamp")
     if sync:
         synchronize(stream)
 
@@ -1127,7 +1102,7 @@ def tile_priority(image_ptr: int, variance_ptr: int, n_ptr: int, priority_ptr: i
                   params: "AdaptiveParams | None", precise=True, stream=None, sync=True) -> None:
     """One float per 64x64 tile: the relative squared error a further sample buys (mrt_tile_priority)."""
     _check(lib().mrt_tile_priority(image_ptr, variance_ptr, n_ptr, priority_ptr, width, height,
-                                   ctypes.byref(params) if params is not None else None, _flags(precise), stream),
+                                   _opt(params), _flags(precise), stream),
            "mrt_tile_priority")
     if sync:
         synchronize(stream)
@@ -1137,7 +1112,7 @@ def tile_error(image_ptr: int, variance_ptr: int, n_ptr: int, mean_ptr: int, pix
                params: "AdaptiveParams | None", precise=True, stream=None, sync=True) -> None:
     """Per 64x64 tile: the mean of v / (l^2 + eps^2) over the counted pixels, and their number (mrt_tile_error)."""
     _check(lib().mrt_tile_error(image_ptr, variance_ptr, n_ptr, mean_ptr, pixels_ptr, width, height,
-                                ctypes.byref(params) if params is not None else None, _flags(precise), stream),
+                                _opt(params), _flags(precise), stream),
            "mrt_tile_error")
     if sync:
         synchronize(stream)
@@ -1164,7 +1139,7 @@ def guides(scene: Scene, width: int, height: int, n_ptr: int, p_ptr: int, camera
            stream=None, sync=True):
     """First-hit guide planes of the denoiser (mrt_guides): (normal, bits(word))
     and (position, t), W*H float4 each on the device."""
-    _check(lib().mrt_guides(scene.handle, ctypes.byref(camera) if camera is not None else None, width, height,
+    _check(lib().mrt_guides(scene.handle, _opt(camera), width, height,
                             n_ptr, p_ptr, _flags(precise), stream), "mrt_guides")
     if sync:
         synchronize(stream)
@@ -1174,7 +1149,7 @@ def denoise(image_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, scratch_ptr: i
             params: DenoiseParams, stream=None, sync=True):
     """The edge-avoiding A-Trous filter (mrt_denoise) on device buffers."""
     _check(lib().mrt_denoise(image_ptr, n_ptr, p_ptr, out_ptr, scratch_ptr, width, height,
-                             ctypes.byref(params) if params is not None else None, stream), "mrt_denoise")
+                             _opt(params), stream), "mrt_denoise")
     if sync:
         synchronize(stream)
 
@@ -1195,8 +1170,8 @@ def reproject(prev_ptr: int, prev_n_ptr: int, prev_p_ptr: int, prev_camera: "Cam
     """Reproject a counted image through the guide planes of the previous and
     the current camera (mrt_reproject)."""
     _check(lib().mrt_reproject(prev_ptr, prev_n_ptr, prev_p_ptr,
-                               ctypes.byref(prev_camera) if prev_camera is not None else None, cur_n_ptr, cur_p_ptr,
-                               out_ptr, width, height, ctypes.byref(params) if params is not None else None, stream),
+                               _opt(prev_camera), cur_n_ptr, cur_p_ptr,
+                               out_ptr, width, height, _opt(params), stream),
            "mrt_reproject")
     if sync:
         synchronize(stream)

@@ -241,6 +241,41 @@ def test_move_camera_equals_stage_pipeline(gpu, mrt_mod, precise):
 
 
 @pytest.mark.parametrize("precise", [True, False])
+def test_move_then_first_plain_denoise(gpu, mrt_mod, precise):
+    """A renderer that moves before it has a denoised buffer: its first plain
+    denoise filters with the new camera's guide planes, the resolve beside it is
+    that of test_move_camera_equals_stage_pipeline, and the planes the next move
+    takes as the previous ones are the new camera's."""
+    A, D = camera(mrt_mod, "A"), camera(mrt_mod, "D")
+    st = Stage(mrt_mod, precise)
+    gA, gD = st.guides(A), st.guides(D)
+    r = mrt_mod.Renderer(_scene(mrt_mod), W0, H0, L0, precise=precise)
+    r.set_camera(A)
+    r.draw(4)
+    r.move_camera(D)
+    r.draw(2)
+    r.denoise()                    # the renderer's first denoise of any kind
+    r.resolve()
+    den, got, img = r.read_denoised(), r.read_resolved(), r.read_image()
+    assert img.tobytes() == fresh_image(mrt_mod, D, 2, precise).tobytes()
+    d_img, out, scr = to_dev(img), st._buf(), st._buf()
+    mrt_mod.denoise(dev_ptr(d_img), dev_ptr(gD[0]), dev_ptr(gD[1]), dev_ptr(out), dev_ptr(scr), W0, H0,
+                    mrt_mod.DenoiseParams.default(2))
+    assert den.tobytes() == st.host(out).tobytes() and np.abs(den - img).max() > 1e-3
+    want = st.resolve(img, 2, st.reproject(st.resolve(fresh_image(mrt_mod, A, 4, precise), 4), gA, A, gD))
+    assert got.tobytes() == st.host(want).tobytes()
+    r.move_camera(A)
+    r.draw(3)
+    r.resolve()
+    got2, img2 = r.read_resolved(), r.read_image()
+    assert img2.tobytes() == fresh_image(mrt_mod, A, 3, precise).tobytes()
+    want2 = st.resolve(img2, 3, st.reproject(want, gD, D, gA))
+    assert got2.tobytes() == st.host(want2).tobytes()
+    assert abs(got2[..., 3].max() - 9.0) < 1e-4
+    r.close()
+
+
+@pytest.mark.parametrize("precise", [True, False])
 def test_two_moves_without_a_draw(gpu, mrt_mod, precise):
     A, D = camera(mrt_mod, "A"), camera(mrt_mod, "D")
     st = Stage(mrt_mod, precise)
