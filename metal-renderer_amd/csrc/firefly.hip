@@ -13,18 +13,12 @@
 // Compiled once: FMA contraction, IEEE division and sqrt.
 #include "firefly.h"
 
+#include "dev_filter.h"
+
 namespace mrt {
 namespace {
 
 constexpr int kTileW = 32;
-constexpr uint32_t kNotFilterable = 0x80000000u;
-constexpr uint32_t kMissWord = 0xFFFFFFFFu;
-
-__device__ __forceinline__ bool finite1(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return finite1(x) && finite1(y) && finite1(z); }
-__device__ __forceinline__ float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-// a light pixel of the guide planes: not filterable and not a miss
-__device__ __forceinline__ bool is_light(uint32_t word) { return word - kNotFilterable < kMissWord - kNotFilterable; }
 
 // Three planes with contiguous rows, so that a wave's taps read consecutive
 // records: (luminance, word), (normal, position.x), (position.y, position.z).
@@ -95,8 +89,8 @@ __global__ __launch_bounds__(kTileW * TH) void firefly_kernel(FireflyArgs a) {
           if (qw != word) continue;
           const float4 qn = lds_n[k];
           const float2 qp = lds_p[k];
-          const float D = (pn.x * qn.x + pn.y * qn.y) + pn.z * qn.z;
-          const float dist = fabsf((pn.x * (qn.w - pn.w) + pn.y * (qp.x - pp.x)) + pn.z * (qp.y - pp.y));
+          const float D = normal_dot(pn.x, pn.y, pn.z, qn.x, qn.y, qn.z);
+          const float dist = plane_distance(pn.x, pn.y, pn.z, pn.w, pp.x, pp.y, qn.w, qp.x, qp.y);
           if (D >= a.normal_cos_min && dist <= tol) {   // false for a NaN guide value
             ++taps;
             s1 += ql.x;

@@ -115,7 +115,7 @@ __device__ __forceinline__ float ieee_div(float a, float b) { return (float)((do
       const uint32_t y = ty * kTile + r;                                \
       if (y >= a.height) break;                                         \
       const size_t i = (size_t)y * a.width + x;                         \
-      if (fbits(a.guide_n[i].w) >= 0x80000000u) continue;               \
+      if (fbits(a.guide_n[i].w) >= kNotFilterable) continue;            \
       const float4 c = a.image[i];                                      \
       if (!finite_rgb(c)) continue;                                     \
       const float l = luminance(mk(c));                                 \

@@ -1,6 +1,7 @@
 // kern_stage.h — frame accumulation, the stage kernels over the reference's AoS records, first-hit guides,
 // the display blit and the owned-tile pack / unpack
 #pragma once
+#include "dev_filter.h"
 #include "dev_shade.h"
 #include "dev_sweep.h"
 
@@ -152,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DeviceScene sc, const
 // tmin 0 and no tmax.  gn[p] = (hn, bits(word)), gp[p] = (hv, t), with hv, hn
 // and the material index as shade_hit computes them; word = the material
 // index, bit 31 set on a light triangle; a miss writes (0, 0, 0, ~0u) and
-// (0, 0, 0, -1).  A pixel is filterable iff word < 0x80000000.
+// (0, 0, 0, -1).  A pixel is filterable iff word < kNotFilterable (dev_filter.h).
 template <int STACK>
 __global__ __launch_bounds__(kBlock) void guide_kernel(DeviceScene sc, uint32_t W, uint32_t H, CameraBlock cam,
                                                        uint32_t moved, float4* gn, float4* gp, uint32_t* spill) {
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void guide_kernel(DeviceScene sc, uint32_t 
     V3 o, d;
     camera_ray<true>(x, y, W, H, make_float4(0.5f, 0.5f, 0.5f, 0.5f), nullptr, moved ? &cam : nullptr, o, d);
     const Hit h = trace_nearest<STACK, kGlobal>(sc, cx, o, d, 0.0f, __builtin_inff());
-    float4 n = make_float4(0.0f, 0.0f, 0.0f, bitsf(0xFFFFFFFFu)), p = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    float4 n = make_float4(0.0f, 0.0f, 0.0f, bitsf(kMissWord)), p = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
     if (h.found) {
       const float wu = h.u, wv = h.v, ww = (1.0f - h.u) - h.v;   // shade_hit's interpolation
       const float4 P0 = fetch_prim<kGlobal>(sc, cx, h.prim, 0), P1 = fetch_prim<kGlobal>(sc, cx, h.prim, 1);
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void guide_kernel(DeviceScene sc, uint32_t 
       const float4 N2 = fetch_prim<kGlobal>(sc, cx, h.prim, 5);
       const V3 hv = add(add(mul(mk(P0), wu), mul(mk(P1), wv)), mul(mk(P2), ww));
       const V3 hn = normalize(add(add(mul(mk(N0), wu), mul(mk(N1), wv)), mul(mk(N2), ww)));
-      const uint32_t word = fbits(P0.w) | (fbits(P1.w) != 0xFFFFFFFFu ? 0x80000000u : 0u);
+      const uint32_t word = fbits(P0.w) | (fbits(P1.w) != 0xFFFFFFFFu ? kNotFilterable : 0u);
       n = make_float4(hn.x, hn.y, hn.z, bitsf(word));
       p = make_float4(hv.x, hv.y, hv.z, h.t);
     }

@@ -21,6 +21,41 @@ namespace {
 thread_local std::string g_last_error;   // the one string: every unit's fail() writes it, mrt_last_error reads it
 std::atomic<uint32_t> g_denoise_path{mrt::kAtrousAuto};
 
+// A buffer argument of an entry point: n bytes at p (null: an optional buffer
+// that was not given, which overlaps nothing), written by the call or only read.
+struct Span {
+  const void* p;
+  size_t n;
+  bool written = false;
+};
+bool spans_overlap(const Span& a, const Span& b) {
+  const char* p = (const char*)a.p;
+  const char* q = (const char*)b.p;
+  return p && q && p < q + b.n && q < p + a.n;
+}
+// the rule of every entry point: no written span overlaps any other span
+bool written_overlap(std::initializer_list<Span> spans) {
+  for (const Span* a = spans.begin(); a != spans.end(); ++a)
+    for (const Span* b = a + 1; b != spans.end(); ++b)
+      if ((a->written || b->written) && spans_overlap(*a, *b)) return true;
+  return false;
+}
+
+// The iterations of an A-Trous filter from step 2^first_log2 on, ping-pong
+// between scratch and out so that the last one writes `out`:
+// launch(i, src, dst, step) is iteration i of N and returns a status.
+template <class Launch>
+int atrous_iterations(const float* image, float* out, float* scratch, uint32_t N, uint32_t first_log2, Launch launch) {
+  const float* src = image;
+  for (uint32_t i = 0; i < N; ++i) {
+    float* dst = ((N - 1 - i) & 1u) ? scratch : out;
+    const int rc = launch(i, reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), 1u << (i + first_log2));
+    if (rc) return rc;
+    src = dst;
+  }
+  return MRT_OK;
+}
+
 // `iterations` iterations from step 2^first_log2 on, with implementation `path`
 int denoise_run(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,
                 uint32_t W, uint32_t H, const mrt_denoise_params* params, uint32_t iterations, uint32_t first_log2,
@@ -28,20 +63,14 @@ int denoise_run(const float* image, const float* guide_n, const float* guide_p, 
   if (!image || !guide_n || !guide_p || !out || !scratch || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
     return fail(MRT_ERR_INVALID, "mrt_denoise: bad argument");
   const size_t bytes = (size_t)W * H * 16;
-  auto overlap = [bytes](const void* a, const void* b) {
-    const char* p = (const char*)a;
-    const char* q = (const char*)b;
-    return p < q + bytes && q < p + bytes;
-  };
-  if (overlap(image, out) || overlap(image, scratch) || overlap(out, scratch))
+  if (written_overlap({{image, bytes}, {out, bytes, true}, {scratch, bytes, true}}))
     return fail(MRT_ERR_INVALID, "mrt_denoise: image, out and scratch must not overlap");
-  if (overlap(guide_n, out) || overlap(guide_n, scratch) || overlap(guide_p, out) || overlap(guide_p, scratch))
+  if (written_overlap({{guide_n, bytes}, {guide_p, bytes}, {out, bytes, true}, {scratch, bytes, true}}))
     return fail(MRT_ERR_INVALID, "mrt_denoise: the guide planes must not overlap out or scratch");
   const int rc = mrt_denoise_params_check(params);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const uint32_t N = iterations;
-  if (N == 0) {
+  if (iterations == 0) {
     HIP_TRY(hipMemcpyAsync(out, image, bytes, hipMemcpyDeviceToDevice, s));
     return MRT_OK;
   }
@@ -53,22 +82,14 @@ int denoise_run(const float* image, const float* guide_n, const float* guide_p, 
   a.inv_sigma_c2 = params->sigma_color > 0.0f ? (float)(1.0 / ((double)params->sigma_color * params->sigma_color)) : 0.0f;
   a.sigma_plane = params->sigma_plane;
   a.normal_log2_power = params->normal_log2_power;
-  const float* src = image;
-  for (uint32_t i = 0; i < N; ++i) {
-    float* dst = ((N - 1 - i) & 1u) ? scratch : out;   // the last iteration writes `out`
-    a.image = reinterpret_cast<const float4*>(src);
-    a.out = reinterpret_cast<float4*>(dst);
-    a.step = 1u << (i + first_log2);
-    HIP_TRY(mrt::launch_atrous(a, path, s));
-    src = dst;
-  }
-  return MRT_OK;
-}
-
-bool planes_overlap(const void* a, const void* b, size_t bytes) {
-  const char* p = (const char*)a;
-  const char* q = (const char*)b;
-  return p < q + bytes && q < p + bytes;
+  return atrous_iterations(image, out, scratch, iterations, first_log2,
+                           [&](uint32_t, const float4* src, float4* dst, uint32_t step) -> int {
+                             a.image = src;
+                             a.out = dst;
+                             a.step = step;
+                             HIP_TRY(mrt::launch_atrous(a, path, s));
+                             return MRT_OK;
+                           });
 }
 
 // mrt_denoise_variance: `iterations` iterations from step 2^first_log2 on with
@@ -82,19 +103,9 @@ int svgf_run(const float* image, const float* variance, const float* guide_n, co
       H == 0 || W > 32768 || H > 32768)
     return fail(MRT_ERR_INVALID, "mrt_denoise_variance: bad argument");
   const size_t bytes = (size_t)W * H * 16, plane = (size_t)W * H * 4;
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const char* p = (const char*)a;
-    const char* q = (const char*)b;
-    return p < q + nb && q < p + na;
-  };
-  // no written buffer may overlap any other buffer
-  const struct { const void* p; size_t n; bool written; } b[] = {
-      {image, bytes, false}, {variance, plane, false}, {guide_n, bytes, false}, {guide_p, bytes, false},
-      {out, bytes, true},    {scratch, bytes, true},   {variance_out, plane, true}};
-  for (size_t i = 0; i < 7; ++i)
-    for (size_t j = i + 1; j < 7; ++j)
-      if ((b[i].written || b[j].written) && b[i].p && b[j].p && overlap(b[i].p, b[i].n, b[j].p, b[j].n))
-        return fail(MRT_ERR_INVALID, "mrt_denoise_variance: out, scratch and variance_out must not overlap any buffer");
+  if (written_overlap({{image, bytes}, {variance, plane}, {guide_n, bytes}, {guide_p, bytes}, {out, bytes, true},
+                       {scratch, bytes, true}, {variance_out, plane, true}}))
+    return fail(MRT_ERR_INVALID, "mrt_denoise_variance: out, scratch and variance_out must not overlap any buffer");
   const int rc = mrt_svgf_params_check(params);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -112,20 +123,18 @@ int svgf_run(const float* image, const float* variance, const float* guide_n, co
   a.sigma_luminance = params->sigma_luminance;
   a.sigma_plane = params->sigma_plane;
   a.normal_log2_power = params->normal_log2_power;
-  const float* src = image;
-  for (uint32_t i = 0; i < N; ++i) {
-    float* dst = ((N - 1 - i) & 1u) ? scratch : out;   // the last iteration writes `out`
-    const bool final = last && i + 1 == N;
-    a.src = reinterpret_cast<const float4*>(src);
-    a.var_in = i == 0 ? variance : nullptr;
-    a.dst = reinterpret_cast<float4*>(dst);
-    a.alpha = final ? reinterpret_cast<const float4*>(image) : nullptr;
-    a.var_out = final ? variance_out : nullptr;
-    a.step = 1u << (i + first_log2);
-    HIP_TRY(mrt::launch_svgf_atrous(a, path, s));
-    src = dst;
-  }
-  return MRT_OK;
+  return atrous_iterations(image, out, scratch, N, first_log2,
+                           [&](uint32_t i, const float4* src, float4* dst, uint32_t step) -> int {
+                             const bool final = last && i + 1 == N;
+                             a.src = src;
+                             a.var_in = i == 0 ? variance : nullptr;
+                             a.dst = dst;
+                             a.alpha = final ? reinterpret_cast<const float4*>(image) : nullptr;
+                             a.var_out = final ? variance_out : nullptr;
+                             a.step = step;
+                             HIP_TRY(mrt::launch_svgf_atrous(a, path, s));
+                             return MRT_OK;
+                           });
 }
 
 }  // namespace
@@ -472,12 +481,8 @@ int mrt_variance(const float* moments, const float* guide_n, const float* guide_
   if (!moments || !guide_n || !guide_p || !variance || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
     return fail(MRT_ERR_INVALID, "mrt_variance: bad argument");
   const size_t bytes = (size_t)W * H * 16;
-  for (const float* in : {moments, guide_n, guide_p}) {
-    const char* p = (const char*)in;
-    const char* q = (const char*)variance;
-    if (p < q + bytes / 4 && q < p + bytes)
-      return fail(MRT_ERR_INVALID, "mrt_variance: variance must not overlap an input");
-  }
+  if (written_overlap({{moments, bytes}, {guide_n, bytes}, {guide_p, bytes}, {variance, bytes / 4, true}}))
+    return fail(MRT_ERR_INVALID, "mrt_variance: variance must not overlap an input");
   const int rc = mrt_svgf_params_check(params);
   if (rc) return rc;
   mrt::VarianceArgs a{};
@@ -538,15 +543,11 @@ int mrt_firefly_clamp(const float* image, const float* guide_n, const float* gui
   if (!image || !guide_n || !guide_p || !out || !params || W == 0 || H == 0 || W > 32768 || H > 32768)
     return fail(MRT_ERR_INVALID, "mrt_firefly_clamp: bad argument");
   const size_t bytes = (size_t)W * H * 16;
-  auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
-    const char* p = (const char*)a;
-    const char* q = (const char*)b;
-    return p < q + nb && q < p + na;
-  };
+  const Span o{out, bytes, true}, cl{clamped, 4, true};
   for (const float* in : {image, guide_n, guide_p})
-    if (overlap(in, bytes, out, bytes) || (clamped && overlap(in, bytes, clamped, 4)))
+    if (spans_overlap({in, bytes}, o) || spans_overlap({in, bytes}, cl))
       return fail(MRT_ERR_INVALID, "mrt_firefly_clamp: out and clamped must not overlap an input");
-  if (clamped && overlap(out, bytes, clamped, 4))
+  if (spans_overlap(o, cl))
     return fail(MRT_ERR_INVALID, "mrt_firefly_clamp: out and clamped must not overlap each other");
   const int rc = mrt_firefly_params_check(params);
   if (rc) return rc;
@@ -587,7 +588,7 @@ int mrt_counted_merge(const float* a, const float* b, float* out, uint32_t W, ui
   if (!a || !b || !out || W == 0 || H == 0 || W > 32768 || H > 32768)
     return fail(MRT_ERR_INVALID, "mrt_counted_merge: bad argument");
   const size_t bytes = (size_t)W * H * 16;
-  if (planes_overlap(b, out, bytes) || (out != a && planes_overlap(a, out, bytes)))
+  if (spans_overlap({b, bytes}, {out, bytes}) || (out != a && spans_overlap({a, bytes}, {out, bytes})))
     return fail(MRT_ERR_INVALID, "mrt_counted_merge: out may be a itself; any other overlap with an input is invalid");
   mrt::MergeArgs m{};
   m.a = reinterpret_cast<const float4*>(a);
@@ -606,12 +607,8 @@ int mrt_tile_priority(const float* image, const float* variance, const float* gu
   if (rc) return rc;
   const uint32_t tx = (W + mrt::kTile - 1) / mrt::kTile, ty = (H + mrt::kTile - 1) / mrt::kTile;
   const size_t bytes = (size_t)W * H * 16, out_bytes = (size_t)tx * ty * 4;
-  const struct { const float* p; size_t n; } in[] = {{image, bytes}, {variance, bytes / 4}, {guide_n, bytes}};
-  for (const auto& b : in) {
-    const char* p = (const char*)b.p;
-    const char* q = (const char*)priority;
-    if (p < q + out_bytes && q < p + b.n) return fail(MRT_ERR_INVALID, "mrt_tile_priority: priority must not overlap an input");
-  }
+  if (written_overlap({{image, bytes}, {variance, bytes / 4}, {guide_n, bytes}, {priority, out_bytes, true}}))
+    return fail(MRT_ERR_INVALID, "mrt_tile_priority: priority must not overlap an input");
   mrt::PriorityArgs a{};
   a.image = reinterpret_cast<const float4*>(image);
   a.variance = variance;
@@ -629,22 +626,11 @@ int mrt_tile_select(const float* priority, uint32_t tiles, uint32_t count, uint3
   if (!priority || !list) return fail(MRT_ERR_INVALID, "mrt_tile_select: null argument");
   if (count == 0 || count > tiles || tiles > mrt::kMaxSelectTiles)
     return fail(MRT_ERR_INVALID, "mrt_tile_select: need 1 <= count <= tiles <= 16384");
-  const char* p = (const char*)priority;
-  const char* q = (const char*)list;
-  if (p < q + (size_t)count * 4 && q < p + (size_t)tiles * 4)
+  if (spans_overlap({priority, (size_t)tiles * 4}, {list, (size_t)count * 4}))
     return fail(MRT_ERR_INVALID, "mrt_tile_select: list must not overlap priority");
   HIP_TRY(mrt::fast::launch_tile_select(priority, tiles, count, list, (hipStream_t)stream));   // exact: one code in both builds
   return MRT_OK;
 }
-
-namespace {
-struct Span { const void* p; size_t n; };
-bool spans_overlap(const Span& a, const Span& b) {
-  const char* p = (const char*)a.p;
-  const char* q = (const char*)b.p;
-  return p < q + b.n && q < p + a.n;
-}
-}  // namespace
 
 int mrt_tile_error(const float* image, const float* variance, const float* guide_n, float* mean_error, uint32_t* pixels,
                    uint32_t W, uint32_t H, const mrt_adaptive_params* params, uint32_t flags, void* stream) {
@@ -750,7 +736,7 @@ int mrt_temporal_resolve(const float* image, uint64_t frames, const float* histo
   if (!image || !out || W == 0 || H == 0 || W > 32768 || H > 32768)
     return fail(MRT_ERR_INVALID, "mrt_temporal_resolve: bad argument");
   const size_t bytes = (size_t)W * H * 16;
-  if (planes_overlap(image, out, bytes) || (history && planes_overlap(history, out, bytes)))
+  if (written_overlap({{image, bytes}, {history, bytes}, {out, bytes, true}}))
     return fail(MRT_ERR_INVALID, "mrt_temporal_resolve: out must not overlap image or history");
   mrt::ResolveArgs a{};
   a.image = reinterpret_cast<const float4*>(image);
@@ -769,9 +755,9 @@ int mrt_reproject(const float* prev, const float* prev_guide_n, const float* pre
       H < 2 || W > 32768 || H > 32768)
     return fail(MRT_ERR_INVALID, "mrt_reproject: bad argument");
   const size_t bytes = (size_t)W * H * 16;
-  for (const float* in : {prev, prev_guide_n, prev_guide_p, cur_guide_n, cur_guide_p})
-    if (planes_overlap(in, history_out, bytes))
-      return fail(MRT_ERR_INVALID, "mrt_reproject: history_out must not overlap an input");
+  if (written_overlap({{prev, bytes}, {prev_guide_n, bytes}, {prev_guide_p, bytes}, {cur_guide_n, bytes},
+                       {cur_guide_p, bytes}, {history_out, bytes, true}}))
+    return fail(MRT_ERR_INVALID, "mrt_reproject: history_out must not overlap an input");
   int rc = mrt_reproject_params_check(params);
   if (rc) return rc;
   mrt_camera c;

@@ -28,16 +28,12 @@
 // registers).  Compiled once: FMA contraction as the fast build, IEEE division.
 #include "temporal.h"
 
+#include "dev_filter.h"
+
 namespace mrt {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr uint32_t kNotFilterable = 0x80000000u;
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  const uint32_t m = 0x7F800000u;
-  return (__float_as_uint(x) & m) != m && (__float_as_uint(y) & m) != m && (__float_as_uint(z) & m) != m;
-}
 
 // one load-load-store pass
 __global__ __launch_bounds__(kBlock) void temporal_resolve_kernel(ResolveArgs a) {
@@ -60,15 +56,15 @@ __global__ __launch_bounds__(kBlock) void temporal_resolve_kernel(ResolveArgs a)
   a.out[i] = o;
 }
 
-// A block is 64 x 4 pixels, a wave one row of 64 (as atrous_direct_kernel):
-// the current pixel's two loads and the store are 16 B per lane, coalesced.
+// One pixel per lane (pixel_64x4, as atrous_direct_kernel): the current
+// pixel's two loads and the store are 16 B per lane, coalesced.
 // A tap's guide-normal record is read first; its position and its colour only
 // when the word matches and the normals agree.  No clamped address is read.
 __global__ __launch_bounds__(kBlock) void reproject_kernel(ReprojectArgs a) {
   const int W = (int)a.width, H = (int)a.height;
-  const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
-  if (x >= W || y >= H) return;
-  const size_t i = (size_t)y * a.width + (uint32_t)x;
+  int x, y;
+  size_t i;
+  if (!pixel_64x4(a.width, a.height, x, y, i)) return;
   const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   const float4 n = a.cur_n[i];
   const uint32_t word = __float_as_uint(n.w);
@@ -104,12 +100,13 @@ __global__ __launch_bounds__(kBlock) void reproject_kernel(ReprojectArgs a) {
       const size_t q = (size_t)yy * a.width + (uint32_t)xx;
       const float4 qn = a.prev_n[q];
       if (__float_as_uint(qn.w) != word) continue;
-      if (!(((n.x * qn.x + n.y * qn.y) + n.z * qn.z) >= a.normal_cos_min)) continue;
+      if (!(normal_dot(n.x, n.y, n.z, qn.x, qn.y, qn.z) >= a.normal_cos_min)) continue;
       const float4 qp = a.prev_p[q];
-      const float dist = fabsf((n.x * (qp.x - p.x) + n.y * (qp.y - p.y)) + n.z * (qp.z - p.z));
+      const float dist = plane_distance(n.x, n.y, n.z, p.x, p.y, p.z, qp.x, qp.y, qp.z);
       if (!(dist <= tol)) continue;
       const float4 qc = a.prev[q];
-      if (!(qc.w > 0.0f) || !finite3(qc.x, qc.y, qc.z)) continue;
+      // (one test of the whole record, not w first: behind a branch on w the compiler loads rgb separately)
+      if (!((int)(qc.w > 0.0f) & (int)finite3(qc.x, qc.y, qc.z))) continue;
       B += b;
       r += b * qc.x;
       g += b * qc.y;
@@ -133,8 +130,7 @@ hipError_t launch_temporal_resolve(const ResolveArgs& a, hipStream_t s) {
 
 hipError_t launch_reproject(const ReprojectArgs& a, hipStream_t s) {
   if (a.width == 0 || a.height == 0) return hipErrorInvalidValue;
-  const dim3 g((a.width + 63) / 64, (a.height + 3) / 4);
-  reproject_kernel<<<g, dim3(kBlock), 0, s>>>(a);
+  reproject_kernel<<<grid_64x4(a.width, a.height), dim3(kBlock), 0, s>>>(a);
   return hipGetLastError();
 }
 
