@@ -319,7 +319,9 @@ struct mrt_renderer {
   uint32_t slot_next = 0;   // slot of the next batch (rotates across draws)
   double wall_khz = 0.0;    // device wall clock (span timestamps; 0 = spans off, MRT_SPANS=0)
   bool image_foreign = false;   // the image holds pixels this renderer did not render (exchange / tiles_write)
-  uint32_t grid = 0;        // persistent grid of the bounce kernel
+  // the persistent kernel this renderer launches, its LDS stack and its grid
+  // (kernel_plan.h; filled once at create by renderer.cpp plan_kernel)
+  mrt::KernelPlan plan;
   // noise tables in device chunks of 64 frames, generated ahead on a worker
   // thread and uploaded on their own stream (noise_schedule.h)
   std::unique_ptr<mrt::NoiseSchedule> noise;
@@ -336,10 +338,6 @@ struct mrt_renderer {
   uint32_t batch = 1;           // frames per bounce launch (frame batching)
   bool counter_fold = true;     // draw statistics copied + cleared by the last accumulate (MRT_COUNTER_FOLD)
   mrt_stats stats{};
-  uint32_t stack_entries = 32;
-  bool stream_allowed = false;  // streaming wavefront possible for this scene / configuration
-  bool stream_mode = false; // wavefront as one launch per frame batch with per-wave queues (stream_kernel)
-  bool path_mode = true;   // one path-megakernel launch per frame batch (else L bounce launches, MRT_KERNEL=wave)
   uint32_t debug = 0;   // MRT_DEBUG ablation bits (profiling only)
   // camera-ray candidate lists per 8x8 pixel block (primary.h), rebuilt for
   // every frame size; bounce 0 of the wavefront kernels (a wave = one block)

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernel_plan.h"
 #include "mrt_layout.h"
 
 namespace mrt {
@@ -252,24 +253,19 @@ constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_sha
   /* mrt_moments: the luminance moments of the rays' radiance, accumulated as launch_accumulate does */   \
   hipError_t launch_moments(uint32_t W, uint32_t H, uint32_t frame_index, const RefRay* rays,             \
                             float* moments, hipStream_t s);                                               \
-  /* persistent grid size of the fused bounce kernel for this scene */                                    \
-  hipError_t bounce_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t blocks_per_cu,          \
-                         uint32_t* grid);                                                                \
-  /* fused wavefront bounce over `grid` blocks (the same grid for every launch of a renderer);          \
-     stack_entries = LDS stack capacity 8/16/24/32, deeper entries go to a.stack_spill */                 \
-  hipError_t launch_bounce(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries,           \
-                           uint32_t grid, hipStream_t s);                                                 \
-  /* path megakernel: every bounce of a batch of frames in one launch (a.bounce unused, no ray queues) */ \
-  hipError_t launch_paths(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries,            \
-                          uint32_t grid, hipStream_t s);                                                  \
-  hipError_t path_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid);                   \
-  /* wave-local streaming wavefront: all bounces of a batch in one launch, per-wave ray queues     \
-     (whole-scene-in-LDS scenes; hipErrorNotSupported otherwise)     */                          \
-  hipError_t launch_stream(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries,           \
-                           uint32_t grid, hipStream_t s);                                                 \
-  bool stream_supported(const DeviceScene& sc, uint32_t stack_entries);                                   \
-  /* the stream kernel's persistent grid (its LDS has no per-block segment scratch) */                    \
-  hipError_t stream_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid);                  \
+  /* The persistent kernels (kernel_plan.h): Bounce, the fused wavefront bounce (one launch per bounce,   \
+     a.bounce = its index); Path, the path megakernel (every bounce of a batch of frames in one launch,   \
+     no ray queues); Stream, the wave-local streaming wavefront (one launch, per-wave ray queues;        \
+     whole-scene-in-LDS scenes with the whole stack in LDS, paths of at most kStreamMaxL).                \
+     stack_entries: the LDS stack entries of the renderer's plan (stack_rule: 8/12/16/24/32); when the    \
+     scene's max_stack is larger, the kind's spill variant runs and deeper entries go to a.stack_spill */ \
+  bool kernel_supported(KernelKind kind, const DeviceScene& sc, uint32_t stack_entries);                  \
+  /* persistent grid size of the kind's kernel for this scene */                                          \
+  hipError_t kernel_grid(KernelKind kind, const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid); \
+  /* over `grid` blocks (the same grid for every launch of a renderer); the per-bounce kernel has no     \
+     tile-list instantiation (hipErrorNotSupported) */                                                    \
+  hipError_t launch_kernel(KernelKind kind, const DeviceScene& sc, const BounceArgs& a,                   \
+                           uint32_t stack_entries, uint32_t grid, hipStream_t s);                         \
   /* the scene's LDS staging mode is not "whole scene in LDS": the path kernel is the faster one */      \
   bool path_preferred(const DeviceScene& sc);                                                             \
   /* accumulateImage over the owned tiles of a batch of frames (in frame order) */                        \

@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "diag_env.h"
@@ -43,12 +44,6 @@ int choose_mode(const DeviceScene& sc) {
   return sc.lds_nodes > 0 ? kTopLds : kGlobal;
 }
 
-size_t bounce_lds_bytes(const DeviceScene& sc, int mode, uint32_t stack, uint32_t grid) {
-  const size_t scene = (size_t)lds_scene_float4s(mode, sc) * 16;
-  const size_t scratch = ((size_t)2 * grid + 1 + 3) / 4 * 16;   // segment counts per block (2 classes) + sentinel
-  return scene + scratch + (size_t)stack * kBlock * 4;           // stack = LDS entries (|STACK|)
-}
-
 // the current device's CU count: what every persistent grid is sized from
 hipError_t device_cus(uint32_t* cus) {
   int dev = 0;
@@ -60,211 +55,214 @@ hipError_t device_cus(uint32_t* cus) {
   return e;
 }
 
-#if MRT_EMIT_MAIN   // the per-bounce and path kernels' host side (not in the stream unit)
-// kTopLds: stage only as many top BVH nodes as keep the block's LDS within
-// 1/MRT_BOUNCE_WAVES of the CU less a 2-KB margin for allocation granularity
-// (the VGPR budget allows MRT_BOUNCE_WAVES resident blocks of 4 waves); the
-// BFS order makes any prefix the top levels.  Full occupancy beats more
-// staged nodes (at 6 blocks/CU: C4 with 80 nodes 828, ~100 nodes (at the
-// edge) 780, 128 nodes 715 Mpaths/s).
-DeviceScene fit_lds_nodes(const DeviceScene& sc, int mode, uint32_t stack, uint32_t grid) {
-  if (mode != kTopLds) return sc;
-  DeviceScene f = sc;
-  const size_t kLdsPerBlockTarget = 160 * 1024 / MRT_LDS_BLOCKS - 2048;
-  const size_t fixed = bounce_lds_bytes(sc, kGlobal, stack, grid) + 64;   // scratch + stack + static
-  const size_t node_bytes = (size_t)node_float4s(sc.width) * 16;
-  const size_t fit = fixed < kLdsPerBlockTarget ? (kLdsPerBlockTarget - fixed) / node_bytes : 0;
-  f.lds_nodes = (uint32_t)std::min<size_t>(sc.lds_nodes, fit);
-  return f;
-}
+// ---- the persistent kernels' host side: one skeleton for the three kinds of
+// kernel_plan.h.  A unit instantiates a kind's kernels only where it names the
+// kind (the split fast build: the stream kernel in its own unit, below). ----
 
-template <int STACK, int MODE>
-hipError_t grid_for(const DeviceScene& sc, uint32_t blocks_per_cu, uint32_t* grid) {
-  uint32_t cus = 0;
-  const hipError_t e = device_cus(&cus);
-  if (e != hipSuccess) return e;
-  // the LDS scratch (2 segment counts per block) depends on the grid: take
-  // the largest blocks/CU n whose own LDS footprint still allows n resident
-  // blocks (and the VGPR budget allows)
-  const int stack = STACK < 0 ? -STACK : STACK;
-  int n = 1;
-  for (int want = 8; want >= 1; --want) {
-    const uint32_t g = cus * (uint32_t)want;
-    const size_t lds = bounce_lds_bytes(fit_lds_nodes(sc, MODE, stack, g), MODE, stack, g);
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, bounce_kernel<STACK, MODE>, kBlock, lds) != hipSuccess)
-      occ = 0;
-    if (occ >= want) { n = want; break; }
-  }
-  // one launch at a time: every resident block slot (the dynamic work
-  // distribution leaves no tail to fill); with frames in flight the caller
-  // asks for fewer blocks per CU per launch
-  *grid = cus * (blocks_per_cu ? std::min<uint32_t>(n, blocks_per_cu) : (uint32_t)n);
-  return hipSuccess;
-}
-
-// path kernel: LDS = scene image + stack + the per-lane path state; the
-// kTopLds node budget fits MRT_PATH_WAVES resident blocks per CU
-size_t path_lds_bytes(const DeviceScene& sc, int mode, uint32_t stack) {
+// A block's dynamic LDS: the scene image, the stack (`stack` = |STACK| entries
+// per lane) and the kind's own words — path: 16 B and the per-lane path
+// state; bounce: the segment counts of a grid of `grid` blocks (2 classes) +
+// sentinel; stream: the sentinel alone (no segment scratch)
+size_t lds_bytes(KernelKind kind, const DeviceScene& sc, int mode, uint32_t stack, uint32_t grid) {
   const size_t scene = (size_t)lds_scene_float4s(mode, sc) * 16;
-  return scene + 16 + (size_t)stack * kBlock * 4 + (size_t)kPathStateWords * kBlock * 4;
+  const size_t own = kind == KernelKind::Path ? 16 + (size_t)kPathStateWords * kBlock * 4
+                                              : ((size_t)2 * (kind == KernelKind::Bounce ? grid : 0) + 1 + 3) / 4 * 16;
+  return scene + own + (size_t)stack * kBlock * 4;
 }
-DeviceScene fit_path_lds_nodes(const DeviceScene& sc, int mode, uint32_t stack) {
+
+// kTopLds: stage only as many top BVH nodes as keep the block's LDS within
+// 1/n of the CU less a 2-KB margin for allocation granularity (the VGPR budget
+// allows n = MRT_BOUNCE_WAVES resident blocks of 4 waves, the path kernel's
+// MRT_PATH_WAVES); the BFS order makes any prefix the top levels.  Full
+// occupancy beats more staged nodes (at 6 blocks/CU: C4 with 80 nodes 828,
+// ~100 nodes (at the edge) 780, 128 nodes 715 Mpaths/s).
+DeviceScene fit_lds_nodes(KernelKind kind, const DeviceScene& sc, int mode, uint32_t stack, uint32_t grid) {
   if (mode != kTopLds) return sc;
   DeviceScene f = sc;
-  const size_t target = 160 * 1024 / MRT_PATH_WAVES - 2048;
-  const size_t fixed = path_lds_bytes(sc, kGlobal, stack) + 64 + 256;   // + static (s_count, s_closed)
-  const size_t fit = fixed < target ? (target - fixed) / ((size_t)node_float4s(sc.width) * 16) : 0;
+  const bool path = kind == KernelKind::Path;
+  const size_t target = 160 * 1024 / (path ? MRT_PATH_WAVES : MRT_LDS_BLOCKS) - 2048;
+  // own words + stack + static (the path kernel's s_count, s_closed: + 256)
+  const size_t fixed = lds_bytes(kind, sc, kGlobal, stack, grid) + 64 + (path ? 256 : 0);
+  const size_t node_bytes = (size_t)node_float4s(sc.width) * 16;
+  const size_t fit = fixed < target ? (target - fixed) / node_bytes : 0;
   f.lds_nodes = (uint32_t)std::min<size_t>(sc.lds_nodes, fit);
   return f;
 }
 
-template <int STACK, int MODE>
-hipError_t path_grid_t(const DeviceScene& sc, uint32_t* grid) {
+// kind K's kernel; a moved camera runs the CAM instantiation, a tile list the
+// LIST one (same launch bounds and LDS; the per-bounce kernel has no LIST)
+template <KernelKind K, int STACK, int MODE, bool CAM = false, bool LIST = false>
+constexpr auto kernel_of() -> void (*)(DeviceScene, BounceArgs) {
+  if constexpr (K == KernelKind::Path) return path_kernel<STACK, MODE, CAM, LIST>;
+  else if constexpr (K == KernelKind::Stream) return stream_kernel<STACK, MODE, CAM, LIST>;
+  else return bounce_kernel<STACK, MODE, CAM>;
+}
+
+// the instantiation a launch's arguments select; null: there is none
+template <KernelKind K, int STACK, int MODE>
+auto kernel_for(const BounceArgs& a) -> void (*)(DeviceScene, BounceArgs) {
+  if constexpr (K == KernelKind::Bounce) {
+    if (a.tile_list) return nullptr;   // the per-bounce kernel (MRT_DIAG builds of a renderer) has no LIST instantiation
+    return a.camera ? kernel_of<K, STACK, MODE, true>() : kernel_of<K, STACK, MODE>();
+  } else {
+    if (a.tile_list) return a.camera ? kernel_of<K, STACK, MODE, true, true>() : kernel_of<K, STACK, MODE, false, true>();
+    return a.camera ? kernel_of<K, STACK, MODE, true>() : kernel_of<K, STACK, MODE>();
+  }
+}
+
+template <KernelKind K, int STACK, int MODE>
+hipError_t launch_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
+  const uint32_t stack = STACK < 0 ? -STACK : STACK;
+  const DeviceScene f = fit_lds_nodes(K, sc, MODE, stack, grid);
+  const size_t lds = lds_bytes(K, f, MODE, stack, grid);
+  const auto kernel = kernel_for<K, STACK, MODE>(a);
+  if (!kernel) return hipErrorNotSupported;
+  kernel<<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
+  return hipGetLastError();
+}
+
+// Resident blocks per CU of K's <STACK, MODE> kernel at its LDS for a grid of
+// `grid` blocks, taken from the CAM = false, LIST = false instantiation; 0: unknown
+template <KernelKind K, int STACK, int MODE>
+int occupancy(const DeviceScene& sc, uint32_t grid) {
+  const uint32_t stack = STACK < 0 ? -STACK : STACK;
+  const size_t lds = lds_bytes(K, fit_lds_nodes(K, sc, MODE, stack, grid), MODE, stack, grid);
+  int occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel_of<K, STACK, MODE>(), kBlock, lds) != hipSuccess) occ = 0;
+  return occ;
+}
+
+// the persistent grid: every block slot the kernel's LDS and registers leave
+// on a CU, at most 8 (one launch at a time; the dynamic work distribution
+// leaves no tail to fill)
+template <KernelKind K, int STACK, int MODE>
+hipError_t grid_t(const DeviceScene& sc, uint32_t* grid) {
   uint32_t cus = 0;
   const hipError_t e = device_cus(&cus);
   if (e != hipSuccess) return e;
-  const int stack = STACK < 0 ? -STACK : STACK;
-  const size_t lds = path_lds_bytes(fit_path_lds_nodes(sc, MODE, stack), MODE, stack);
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, path_kernel<STACK, MODE>, kBlock, lds) != hipSuccess || occ < 1)
-    occ = 1;
-  *grid = cus * (uint32_t)std::min(occ, 8);
+  if constexpr (K == KernelKind::Bounce) {
+    // the LDS scratch (2 segment counts per block) depends on the grid: take
+    // the largest blocks/CU n whose own LDS footprint still allows n resident
+    // blocks (and the VGPR budget allows)
+    uint32_t n = 1;
+    for (uint32_t want = 8; want >= 1; --want)
+      if (occupancy<K, STACK, MODE>(sc, cus * want) >= (int)want) { n = want; break; }
+    *grid = cus * n;
+  } else {
+    const int occ = std::max(occupancy<K, STACK, MODE>(sc, 0), 1);
+    // stream: one block slot per CU is left to the other render stream's launch
+    // and the accumulate kernel (MRT_STREAM_SPARE): with 6-wave registers the
+    // kernel fits 6 blocks per CU, and 5 of them persistent measured best —
+    // C2 11937 vs 11740 Mpaths/s with all 6 (1344 / 1408 blocks: within
+    // ±0.3 %), per-frame draws 9585 vs 8856 (r5, alternating in one call)
+    const int spare = K == KernelKind::Stream && occ > 1 ? MRT_STREAM_SPARE : 0;
+    *grid = cus * (uint32_t)std::min(occ - spare, 8);
+  }
   return hipSuccess;
 }
 
-template <int STACK, int MODE>
-hipError_t launch_path_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
-  const int stack = STACK < 0 ? -STACK : STACK;
-  const DeviceScene f = fit_path_lds_nodes(sc, MODE, stack);
-  // (a moved camera: the CAM instantiation, a tile list: the LIST one; same launch bounds and LDS)
-  const size_t lds = path_lds_bytes(f, MODE, stack);
-  if (a.tile_list) {
-    if (a.camera) path_kernel<STACK, MODE, true, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
-    else path_kernel<STACK, MODE, false, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
-  } else if (a.camera) path_kernel<STACK, MODE, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
-  else path_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
-  return hipGetLastError();
+// the kind has a kernel for this scene with the plan's stack_entries (the
+// stream kernel: whole-scene-in-LDS scenes, the whole stack in LDS)
+bool variant_ok(KernelKind kind, const DeviceScene& sc, uint32_t stack_entries) {
+  return sc.width == 4 && run_stack(kind, stack_entries, sc.max_stack > stack_entries) != 0 &&
+         (kind != KernelKind::Stream || choose_mode(sc) == kAllLds);
 }
 
-template <int STACK>
-hipError_t path_dispatch_mode(const DeviceScene& sc, const BounceArgs* a, uint32_t grid, uint32_t* grid_out,
-                              hipStream_t s) {
-  switch (choose_mode(sc)) {
-    case kAllLds:
-      return a ? launch_path_t<STACK, kAllLds>(sc, *a, grid, s) : path_grid_t<STACK, kAllLds>(sc, grid_out);
-    case kTopLds:
-      return a ? launch_path_t<STACK, kTopLds>(sc, *a, grid, s) : path_grid_t<STACK, kTopLds>(sc, grid_out);
-    default:
-      return a ? launch_path_t<STACK, kGlobal>(sc, *a, grid, s) : path_grid_t<STACK, kGlobal>(sc, grid_out);
-  }
-}
-
-// LDS stack capacity variants (negative: |STACK| LDS entries + global spill)
-hipError_t path_dispatch(const DeviceScene& sc, const BounceArgs* a, uint32_t stack_entries, uint32_t grid,
-                         uint32_t* grid_out, hipStream_t s) {
-  if (sc.width != 4) return hipErrorInvalidValue;
-  if (sc.max_stack > stack_entries) {
-    if (stack_entries <= 8) return path_dispatch_mode<-8>(sc, a, grid, grid_out, s);
-    if (stack_entries <= 12) return path_dispatch_mode<-12>(sc, a, grid, grid_out, s);
-    if (stack_entries <= 16) return path_dispatch_mode<-16>(sc, a, grid, grid_out, s);
-    return path_dispatch_mode<-32>(sc, a, grid, grid_out, s);
-  }
-  if (stack_entries <= 8) return path_dispatch_mode<8>(sc, a, grid, grid_out, s);
-  if (stack_entries <= 12) return path_dispatch_mode<12>(sc, a, grid, grid_out, s);
-  if (stack_entries <= 16) return path_dispatch_mode<16>(sc, a, grid, grid_out, s);
-  if (stack_entries <= 24) return path_dispatch_mode<24>(sc, a, grid, grid_out, s);
-  return path_dispatch_mode<32>(sc, a, grid, grid_out, s);
-}
-
-template <int STACK, int MODE>
-hipError_t launch_bounce_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
-  const DeviceScene f = fit_lds_nodes(sc, MODE, STACK < 0 ? -STACK : STACK, grid);
-  const size_t lds = bounce_lds_bytes(f, MODE, STACK < 0 ? -STACK : STACK, grid);
-  if (a.tile_list) return hipErrorNotSupported;   // the per-bounce kernel (MRT_DIAG builds of a renderer) has no LIST instantiation
-  if (a.camera) bounce_kernel<STACK, MODE, true><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
-  else bounce_kernel<STACK, MODE><<<dim3(grid), dim3(kBlock), lds, s>>>(f, a);
-  return hipGetLastError();
-}
-
-template <int STACK>
-hipError_t dispatch_mode(const DeviceScene& sc, const BounceArgs* a, uint32_t grid, uint32_t* grid_out,
-                         hipStream_t s) {
-  switch (choose_mode(sc)) {
-    case kAllLds:
-      return a ? launch_bounce_t<STACK, kAllLds>(sc, *a, grid, s) : grid_for<STACK, kAllLds>(sc, grid, grid_out);
-    case kTopLds:
-      return a ? launch_bounce_t<STACK, kTopLds>(sc, *a, grid, s) : grid_for<STACK, kTopLds>(sc, grid, grid_out);
-    default:
-      return a ? launch_bounce_t<STACK, kGlobal>(sc, *a, grid, s) : grid_for<STACK, kGlobal>(sc, grid, grid_out);
-  }
-}
-
-// stack_entries = LDS stack capacity (8/16/24/32); when the BVH's bound is
-// larger, the spill variants (8, 16 or 32 LDS entries + global) are used
-hipError_t dispatch(const DeviceScene& sc, const BounceArgs* a, uint32_t stack_entries, uint32_t grid,
-                    uint32_t* grid_out, hipStream_t s) {
-  if (sc.width != 4) return hipErrorInvalidValue;
-  if (sc.max_stack > stack_entries) {
-    if (stack_entries <= 8) return dispatch_mode<-8>(sc, a, grid, grid_out, s);
-    if (stack_entries <= 16) return dispatch_mode<-16>(sc, a, grid, grid_out, s);
-    return dispatch_mode<-32>(sc, a, grid, grid_out, s);
-  }
-  if (stack_entries <= 8) return dispatch_mode<8>(sc, a, grid, grid_out, s);
-  if (stack_entries <= 12) return dispatch_mode<12>(sc, a, grid, grid_out, s);
-  if (stack_entries <= 16) return dispatch_mode<16>(sc, a, grid, grid_out, s);
-  if (stack_entries <= 24) return dispatch_mode<24>(sc, a, grid, grid_out, s);
-  return dispatch_mode<32>(sc, a, grid, grid_out, s);
-}
-
-#endif  // MRT_EMIT_MAIN
-
-// wave-local streaming wavefront: whole-scene-in-LDS scenes, the stack in LDS
-template <int STACK>
-hipError_t launch_stream_t(const DeviceScene& sc, const BounceArgs& a, uint32_t grid, hipStream_t s) {
-  const size_t lds = bounce_lds_bytes(sc, kAllLds, STACK, 0);
-  if (a.tile_list) {   // the LIST instantiations (dev_shade.h slot_pixel_l)
-    if (a.camera) stream_kernel<STACK, kAllLds, true, true><<<dim3(grid), dim3(kBlock), lds, s>>>(sc, a);
-    else stream_kernel<STACK, kAllLds, false, true><<<dim3(grid), dim3(kBlock), lds, s>>>(sc, a);
-  } else if (a.camera)
-    stream_kernel<STACK, kAllLds, true><<<dim3(grid), dim3(kBlock), lds, s>>>(sc, a);
+// The one turn from run time to template arguments: op.run<STACK, MODE>() for
+// the kernel K runs for this scene with the plan's stack_entries — STACK from
+// the kind's list (kernel_plan.h: every entry is instantiated here, and nothing
+// else), MODE by choose_mode (the stream kernel: whole-scene-in-LDS scenes only)
+template <KernelKind K, int STACK, class Op>
+hipError_t for_mode(int mode, const Op& op) {
+  if (K == KernelKind::Stream || mode == kAllLds) return op.template run<STACK, kAllLds>();
+  if constexpr (K != KernelKind::Stream)
+    return mode == kTopLds ? op.template run<STACK, kTopLds>() : op.template run<STACK, kGlobal>();
   else
-    stream_kernel<STACK, kAllLds><<<dim3(grid), dim3(kBlock), lds, s>>>(sc, a);
-  return hipGetLastError();
+    return hipErrorNotSupported;
 }
-// the stream kernel's own persistent grid: every block slot its LDS (scene
-// image + stack, no segment scratch) and registers leave on a CU
-template <int STACK>
-hipError_t stream_grid_t(const DeviceScene& sc, uint32_t* grid) {
-  uint32_t cus = 0;
-  const hipError_t e = device_cus(&cus);
-  if (e != hipSuccess) return e;
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, stream_kernel<STACK, kAllLds>, kBlock,
-                                                   bounce_lds_bytes(sc, kAllLds, STACK, 0)) != hipSuccess || occ < 1)
-    occ = 1;
-  // one block slot per CU is left to the other render stream's launch and
-  // the accumulate kernel (MRT_STREAM_SPARE): with 6-wave registers the
-  // kernel fits 6 blocks per CU, and 5 of them persistent measured best —
-  // C2 11937 vs 11740 Mpaths/s with all 6 (1344 / 1408 blocks: within
-  // ±0.3 %), per-frame draws 9585 vs 8856 (r5, alternating in one call)
-  const int spare = occ > 1 ? MRT_STREAM_SPARE : 0;
-  *grid = cus * (uint32_t)std::min(occ - spare, 8);
-  return hipSuccess;
+template <KernelKind K, class Op>
+hipError_t for_stack(StackList<>, int, int, const Op&) {
+  return hipErrorInvalidValue;
+}
+template <KernelKind K, class Op, int S0, int... S>
+hipError_t for_stack(StackList<S0, S...>, int stack, int mode, const Op& op) {
+  return stack == S0 ? for_mode<K, S0>(mode, op) : for_stack<K>(StackList<S...>{}, stack, mode, op);
+}
+template <KernelKind K, class Op>
+hipError_t with_variant(const DeviceScene& sc, uint32_t stack_entries, const Op& op) {
+  if (!variant_ok(K, sc, stack_entries)) return K == KernelKind::Stream ? hipErrorNotSupported : hipErrorInvalidValue;
+  return for_stack<K>(stacks_of<K>(), run_stack(K, stack_entries, sc.max_stack > stack_entries), choose_mode(sc), op);
 }
 
-bool stream_ok(const DeviceScene& sc, uint32_t stack_entries) {
-  return sc.width == 4 && choose_mode(sc) == kAllLds && sc.max_stack <= stack_entries && stack_entries <= 32;
+// the two things the host does with an instantiation
+template <KernelKind K>
+struct LaunchOp {
+  const DeviceScene& sc;
+  const BounceArgs& a;
+  uint32_t grid;
+  hipStream_t s;
+  template <int STACK, int MODE> hipError_t run() const { return launch_t<K, STACK, MODE>(sc, a, grid, s); }
+};
+template <KernelKind K>
+struct GridOp {
+  const DeviceScene& sc;
+  uint32_t* grid;
+  template <int STACK, int MODE> hipError_t run() const { return grid_t<K, STACK, MODE>(sc, grid); }
+};
+
+template <KernelKind K>
+hipError_t launch_of(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries, uint32_t grid, hipStream_t s) {
+  if (K == KernelKind::Stream && a.max_path_length > kStreamMaxL) return hipErrorNotSupported;
+  return with_variant<K>(sc, stack_entries, LaunchOp<K>{sc, a, grid, s});
+}
+template <KernelKind K>
+hipError_t grid_of(const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid) {
+  return with_variant<K>(sc, stack_entries, GridOp<K>{sc, grid});
 }
 
 }  // namespace
+
+// the stream kernel's unit (below), which the kind switch of the main unit calls across
+hipError_t stream_unit_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid);
+hipError_t stream_unit_launch(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries, uint32_t grid,
+                              hipStream_t s);
 
 // Translation units (Makefile): MRT_TU 0 = every entry point (precise and
 // diagnostic builds); the fast build is split in two — MRT_TU 1 everything
 // but the stream kernel, MRT_TU 2 the stream kernel alone, compiled with the
 // max-ILP machine scheduler (-amdgpu-sched-strategy=max-ilp: C2 +0.45 %,
 // alternating in one call, while the path kernel loses 0.5 % under it).
+// The persistent kernels' entry points come first, launch before grid and path
+// before bounce (in the stream unit, at the end of the file, grid before
+// launch): a unit's kernels are instantiated, and laid out in its code object,
+// in the order the host code first names them, and this order reproduces the
+// code objects of the dispatch this skeleton replaced byte for byte.
 #if MRT_EMIT_MAIN
+bool kernel_supported(KernelKind kind, const DeviceScene& sc, uint32_t stack_entries) {
+  return variant_ok(kind, sc, stack_entries);
+}
+
+hipError_t launch_kernel(KernelKind kind, const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries,
+                         uint32_t grid, hipStream_t s) {
+  switch (kind) {
+    case KernelKind::Path: return launch_of<KernelKind::Path>(sc, a, stack_entries, grid, s);
+    case KernelKind::Bounce: return launch_of<KernelKind::Bounce>(sc, a, stack_entries, grid, s);
+    case KernelKind::Stream: return stream_unit_launch(sc, a, stack_entries, grid, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t kernel_grid(KernelKind kind, const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid) {
+  switch (kind) {
+    case KernelKind::Path: return grid_of<KernelKind::Path>(sc, stack_entries, grid);
+    case KernelKind::Bounce: return grid_of<KernelKind::Bounce>(sc, stack_entries, grid);
+    case KernelKind::Stream: return stream_unit_grid(sc, stack_entries, grid);
+  }
+  return hipErrorInvalidValue;
+}
+
+bool path_preferred(const DeviceScene& sc) { return choose_mode(sc) != kAllLds; }
+
 hipError_t launch_raygen(uint32_t W, uint32_t H, const float* noise, RefRay* rays, const CameraBlock* cam,
                          hipStream_t s) {
   raygen_kernel<<<dim3(blocks_for(W * H)), dim3(kBlock), 0, s>>>(W, H,
@@ -449,48 +447,15 @@ hipError_t read_stamps(unsigned long long* out8, bool reset) {
 #endif
 }
 
-hipError_t bounce_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t blocks_per_cu, uint32_t* grid) {
-  // (dispatch passes `grid` through as blocks_per_cu when no launch is given)
-  return dispatch(sc, nullptr, stack_entries, blocks_per_cu, grid, nullptr);
-}
-
-hipError_t launch_bounce(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries, uint32_t grid,
-                         hipStream_t s) {
-  return dispatch(sc, &a, stack_entries, grid, nullptr, s);
-}
-
-hipError_t launch_paths(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries, uint32_t grid,
-                        hipStream_t s) {
-  return path_dispatch(sc, &a, stack_entries, grid, nullptr, s);
-}
-
-hipError_t path_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid) {
-  return path_dispatch(sc, nullptr, stack_entries, 0, grid, nullptr);
-}
-
-bool path_preferred(const DeviceScene& sc) { return choose_mode(sc) != kAllLds; }
-
 #endif  // MRT_EMIT_MAIN
 #if MRT_EMIT_STREAM
-bool stream_supported(const DeviceScene& sc, uint32_t stack_entries) { return stream_ok(sc, stack_entries); }
-
-hipError_t stream_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid) {
-  if (!stream_ok(sc, stack_entries)) return hipErrorNotSupported;
-  if (stack_entries <= 8) return stream_grid_t<8>(sc, grid);
-  if (stack_entries <= 12) return stream_grid_t<12>(sc, grid);
-  if (stack_entries <= 16) return stream_grid_t<16>(sc, grid);
-  if (stack_entries <= 24) return stream_grid_t<24>(sc, grid);
-  return stream_grid_t<32>(sc, grid);
+hipError_t stream_unit_grid(const DeviceScene& sc, uint32_t stack_entries, uint32_t* grid) {
+  return grid_of<KernelKind::Stream>(sc, stack_entries, grid);
 }
 
-hipError_t launch_stream(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries, uint32_t grid,
-                         hipStream_t s) {
-  if (!stream_ok(sc, stack_entries) || a.max_path_length > kStreamMaxL) return hipErrorNotSupported;
-  if (stack_entries <= 8) return launch_stream_t<8>(sc, a, grid, s);
-  if (stack_entries <= 12) return launch_stream_t<12>(sc, a, grid, s);
-  if (stack_entries <= 16) return launch_stream_t<16>(sc, a, grid, s);
-  if (stack_entries <= 24) return launch_stream_t<24>(sc, a, grid, s);
-  return launch_stream_t<32>(sc, a, grid, s);
+hipError_t stream_unit_launch(const DeviceScene& sc, const BounceArgs& a, uint32_t stack_entries, uint32_t grid,
+                              hipStream_t s) {
+  return launch_of<KernelKind::Stream>(sc, a, stack_entries, grid, s);
 }
 #endif  // MRT_EMIT_STREAM
 

@@ -55,7 +55,7 @@ int finalize_draw(mrt_renderer* r, DrawRecord& d) {
   r->stats.last_draw_ms = ms;
   const uint64_t paths = d.pixels * d.frames;
   r->stats.mpaths_per_s = ms > 0.0f ? (double)paths / (ms * 1e-3) / 1e6 : 0.0;
-  r->stats.kernel_launches += (uint64_t)lay.batches * (r->path_mode || r->stream_mode ? 1u : lay.L);
+  r->stats.kernel_launches += (uint64_t)lay.batches * mrt::launches_per_batch(r->plan.kind, lay.L);
   for (uint32_t k = 0; k < lay.batches; ++k) {
     unsigned long long sp[2];
     std::memcpy(sp, static_cast<const char*>(d.host) + lay.span(k), 16);
@@ -110,7 +110,7 @@ int install_camera(mrt_renderer* r, bool idle) {
   const mrt::CameraBlock* cbp = r->camera_moved ? &cb : nullptr;
   mrt::PrimaryLists pl;
   const mrt::BvhResult& b = r->scene->bvh;
-  const bool lists_possible = r->primary_allowed && !r->path_mode;
+  const bool lists_possible = r->primary_allowed && r->plan.kind != mrt::KernelKind::Path;
   const bool lists = lists_possible && mrt::build_primary_lists(b.tris.data(), (uint32_t)(b.tris.size() / 12), W, H,
                                                                 r->primary_cap, cbp, pl);
   // capacity: the block and the longest buffer build_primary_lists can return
@@ -194,6 +194,39 @@ int install_camera(mrt_renderer* r, bool idle) {
   return MRT_OK;
 }
 
+// r->plan (kernel_plan.h): the kernel this renderer launches, decided once at
+// create from the scene, and what the frame buffers are sized for
+int plan_kernel(mrt_renderer* r) {
+  using mrt::KernelKind;
+  const mrt::DeviceScene& dev = r->scene->dev;
+  mrt::KernelPlan& p = r->plan;
+  std::optional<uint32_t> cap;   // MRT_STACK overrides the stack rule's cap
+  if (const char* v = mrt::diag_env("MRT_STACK")) cap = (uint32_t)std::strtoul(v, nullptr, 0);
+  // kind: scenes traversed from global memory run the path megakernel (all
+  // bounces of a frame batch in one launch: C3 +15 %, C4 +1.5 % over the
+  // wavefront), scenes staged whole in LDS the wavefront (C2: the path kernel
+  // is 24 % slower); MRT_KERNEL=path|wave overrides.
+  bool path = mrt::fast::path_preferred(dev);
+  if (const char* k = mrt::diag_env("MRT_KERNEL")) path = std::strcmp(k, "path") == 0;
+  p.kind = path ? KernelKind::Path : KernelKind::Bounce;
+  const mrt::StackChoice st = mrt::stack_rule(p.kind, dev.max_stack, cap);   // (entries and spill: the same for every kind)
+  p.stack_entries = st.stack_entries;
+  p.spills = st.spills;
+  // the wavefront streams (one launch per frame batch, per-wave ray queues)
+  // where the stream kernel supports the scene: whole in LDS, no stack spill;
+  // MRT_STREAM=0 keeps one launch per bounce
+  const char* c = mrt::diag_env("MRT_STREAM");
+  if (!path && (!c || std::atoi(c) != 0) && r->desc.max_path_length <= mrt::kStreamMaxL &&
+      mrt::fast::kernel_supported(KernelKind::Stream, dev, p.stack_entries))
+    p.kind = KernelKind::Stream;
+  // persistent grid of that kernel: the stream kernel sizes it by its own LDS
+  // (the per-bounce kernel's segment scratch grows with the grid: sized for
+  // that, a 24-KB scene image + stack left C2 at 4 instead of 5 blocks per CU)
+  HIP_TRY(MRT_BUILD_CALL(r->desc.flags, kernel_grid(p.kind, dev, p.stack_entries, &p.grid)));
+  if (const char* g = mrt::diag_env("MRT_GRID")) p.grid = std::max<uint32_t>(1, (uint32_t)std::strtoul(g, nullptr, 0));
+  return MRT_OK;
+}
+
 int alloc_frame_buffers(mrt_renderer* r) {
   const uint32_t W = r->desc.width, H = r->desc.height;
   const uint32_t S = std::max<uint32_t>(1, r->desc.shard_count);
@@ -223,26 +256,25 @@ int alloc_frame_buffers(mrt_renderer* r) {
   if (owned_slots >= ((size_t)1 << 31)) return fail(MRT_ERR_INVALID, "frame too large");
   // queue capacity: every owned slot of the batch + per-block rounding and
   // slack of the segments (kernels.h)
-  const size_t slots = owned_slots * r->batch + (size_t)r->grid * (256 + mrt::kSegSlack);
-  r->stream_mode = r->stream_allowed;
+  const size_t slots = owned_slots * r->batch + (size_t)r->plan.grid * (256 + mrt::kSegSlack);
+  const bool path = r->plan.kind == mrt::KernelKind::Path, stream = r->plan.kind == mrt::KernelKind::Stream;
   for (FrameSlot& fs : r->slots) {
-    HIP_TRY(fs.segments.alloc(((size_t)4 * r->grid + 2) * 4));   // 2 queues x 2 classes x grid + 2 chunk words
+    HIP_TRY(fs.segments.alloc(((size_t)4 * r->plan.grid + 2) * 4));   // 2 queues x 2 classes x grid + 2 chunk words
     HIP_TRY(hipMemsetAsync(fs.segments.p, 0, fs.segments.bytes, r->stream));
     // the path kernel keeps the path state in LDS: no ray queues; the
     // streaming wavefront needs only its per-wave queues
-    const size_t qslots = r->stream_mode ? mrt::stream_slots(r->desc.max_path_length, r->grid) : slots;
+    const size_t qslots = stream ? mrt::stream_slots(r->desc.max_path_length, r->plan.grid) : slots;
     // (stream mode: queue[1] is unused but for its plane 0, the partial hits
     // of recycled rays — 16 B a slot, as the other planes — where the scene's
     // nearest queries sweep under a cap, kern_bounce.h bounce_wave)
     const mrt::DeviceScene& dev = r->scene->dev;
-    const bool partial = r->stream_mode && dev.sweep_leaves && dev.sweep_cap < mrt::kSweepLeaves;
+    const bool partial = stream && dev.sweep_leaves && dev.sweep_cap < mrt::kSweepLeaves;
     for (int q = 0; q < 2; ++q)
       for (int p = 0; p < mrt::kQueuePlanes; ++p)
-        HIP_TRY(fs.queue[q][p].alloc(r->path_mode || (r->stream_mode && q == 1 && !(partial && p == 0)) ? 0 : qslots * 16));
+        HIP_TRY(fs.queue[q][p].alloc(path || (stream && q == 1 && !(partial && p == 0)) ? 0 : qslots * 16));
     HIP_TRY(fs.radiance.alloc(owned_slots * r->batch * 16));
-    const uint32_t need = r->scene->dev.max_stack;
     // spill rows of max_stack words per lane (dev_lds.h LdsCtx::spill_lane)
-    if (need > r->stack_entries && !fs.spill.p) HIP_TRY(fs.spill.alloc((size_t)need * r->grid * 256 * 4));
+    if (r->plan.spills && !fs.spill.p) HIP_TRY(fs.spill.alloc((size_t)dev.max_stack * r->plan.grid * 256 * 4));
   }
   if (r->own_image) {
     if (r->image) (void)hipFree(r->image);
@@ -259,7 +291,7 @@ int alloc_frame_buffers(mrt_renderer* r) {
   r->stats = mrt_stats{};
   r->noise_base = r->noise->counters();
   r->stats.owned_pixels = r->owned_pixels;
-  r->stats.kernel = r->path_mode ? 1u : (r->stream_mode ? 2u : 0u);
+  r->stats.kernel = (uint32_t)r->plan.kind;
   r->stats.inflight = r->inflight;
   {
     const int rc = install_camera(r, true);
@@ -324,7 +356,7 @@ int bounce_args(const mrt_renderer* r, const DrawSource& src, const DrawRecord& 
   const uint32_t L = r->desc.max_path_length;
   uint32_t* cnt = d.counters.as<uint32_t>();
   uint32_t* seg = fs.segments.as<uint32_t>();
-  uint32_t* meta = seg + 4 * (size_t)r->grid;
+  uint32_t* meta = seg + 4 * (size_t)r->plan.grid;
   a.width = r->desc.width;
   a.height = r->desc.height;
   a.frame_index = (uint32_t)bt.f;
@@ -347,10 +379,10 @@ int bounce_args(const mrt_renderer* r, const DrawSource& src, const DrawRecord& 
     return fail(MRT_ERR_STATE, "draw: a launch divisor's magic multiplier does not divide exactly");
   a.debug = r->debug;
   a.flags = (r->desc.flags & MRT_FLAG_DEBUG_MATERIAL) ? mrt::kShadeDebugMaterial : 0u;
-  a.in_segments = 2 * r->grid;   // two material classes per block
-  a.in_seg_count = seg + (size_t)((b + 1) & 1) * 2 * r->grid;
+  a.in_segments = 2 * r->plan.grid;   // two material classes per block
+  a.in_seg_count = seg + (size_t)((b + 1) & 1) * 2 * r->plan.grid;
   a.in_chunk = meta + ((b + 1) & 1);
-  a.out_seg_count = seg + (size_t)(b & 1) * 2 * r->grid;
+  a.out_seg_count = seg + (size_t)(b & 1) * 2 * r->plan.grid;
   a.out_chunk = meta + (b & 1);
   a.out_total = cnt + d.layout.total(k, b);
   a.grab = cnt + d.layout.grab(k, b);
@@ -485,7 +517,7 @@ int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src) {
   const std::vector<Batch> batches = plan_batches(r, src.f0, n, chunks);
   const uint32_t nb = (uint32_t)batches.size();
   d.layout = CounterLayout(nb, r->desc.max_path_length);   // (the entry's previous draw is read back: nothing reads its layout)
-  const uint32_t launches_per_batch = r->path_mode || r->stream_mode ? 1u : r->desc.max_path_length;
+  const uint32_t launches_per_batch = mrt::launches_per_batch(r->plan.kind, r->desc.max_path_length);
   const bool profile = (r->desc.flags & MRT_FLAG_PROFILE) != 0;
   bool fresh = false;
   rc = size_draw_record(d, profile ? (size_t)2 * nb * launches_per_batch : 0, &fresh);   // at most every batch is timed
@@ -561,12 +593,8 @@ int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src) {
       rc = bounce_args(r, src, d, bt, k, b, fs, cg, a);
       if (rc) return rc;
       if (timed) HIP_TRY(hipEventRecord(d.kernel_events[ev++], fs.stream));
-      if (r->path_mode)
-        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_paths(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
-      else if (r->stream_mode)
-        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_stream(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
-      else
-        HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_bounce(r->scene->dev, a, r->stack_entries, r->grid, fs.stream)));
+      HIP_TRY(MRT_BUILD_CALL(r->desc.flags, launch_kernel(r->plan.kind, r->scene->dev, a, r->plan.stack_entries,
+                                                          r->plan.grid, fs.stream)));
       if (timed) HIP_TRY(hipEventRecord(d.kernel_events[ev++], fs.stream));
     }
     // accumulateImage for frames f .. f+batch-1 on the main stream, in batch
@@ -655,23 +683,6 @@ int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out) {
     HIP_TRY(hipEventCreateWithFlags(&d.cleared, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&d.copied, hipEventDisableTiming));
   }
-  // LDS stack capacity: the BVH's bound rounded up to 8/16 entries when it is
-  // <= 16; deeper BVHs keep 8 entries in LDS and spill the rest to global
-  // memory (MRT_STACK overrides the cap).  LDS per block bounds the resident
-  // blocks per CU, and for global-memory traversal occupancy wins: C4 with
-  // 8 LDS entries + spill ran 1.5x faster than with a 32-entry LDS stack.
-  // r3, with traversal slack: trees deeper than 32 entries (the 1M-triangle
-  // scenes, 48) keep 12 in LDS — C4 +1.9 %; C3 (26) is best at 8 (12: -0.4 %,
-  // C3g -0.9 %), and 16 entries lose everywhere (C4 -0.4 %, C3g -2.4 %)
-  // the deeper of the main and the occluder tree (dev.max_stack): shadow rays
-  // may traverse either
-  const uint32_t need = desc->scene->dev.max_stack;
-  uint32_t cap = need <= 16 ? 16 : (need > 32 ? 12 : 8);
-  if (const char* v = mrt::diag_env("MRT_STACK")) cap = std::max<uint32_t>(8, (uint32_t)std::strtoul(v, nullptr, 0));
-  const uint32_t want = std::min(need, cap);
-  r->stack_entries = want <= 8 ? 8 : want <= 12 ? 12 : want <= 16 ? 16 : want <= 24 ? 24 : 32;
-  if (need > r->stack_entries)   // spill variants: 8 / 12 (path kernel; the wavefront runs 16) / 16 / 32
-    r->stack_entries = r->stack_entries <= 8 ? 8 : r->stack_entries <= 12 ? 12 : r->stack_entries <= 16 ? 16 : 32;
   if (const char* dbg = mrt::diag_env("MRT_DEBUG")) r->debug = (uint32_t)std::strtoul(dbg, nullptr, 0);
   if (const char* v = mrt::diag_env("MRT_COUNTER_FOLD")) r->counter_fold = std::atoi(v) != 0;
   if (const char* v = mrt::diag_env("MRT_PROFILE_EVERY"))
@@ -702,35 +713,13 @@ int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out) {
     HIP_TRY(hipEventCreateWithFlags(&fs.acc_done, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&fs.kernel_done, hipEventDisableTiming));
   }
-  // kernel: scenes traversed from global memory run the path megakernel (all
-  // bounces of a frame batch in one launch: C3 +15 %, C4 +1.5 % over the
-  // wavefront), scenes staged whole in LDS the wavefront of per-bounce
-  // launches (C2: the path kernel is 24 % slower); MRT_KERNEL=path|wave
-  // overrides.
   if (const char* v = mrt::diag_env("MRT_PRIMARY")) r->primary_allowed = std::atoi(v) != 0;
   if (const char* v = mrt::diag_env("MRT_PRIMARY_CAP"))
     r->primary_cap = std::max<uint32_t>(1, std::min<uint32_t>(mrt::kPrimaryFallback - 1, (uint32_t)std::strtoul(v, nullptr, 0)));
-  r->path_mode = mrt::fast::path_preferred(desc->scene->dev);
-  if (const char* k = mrt::diag_env("MRT_KERNEL")) r->path_mode = std::strcmp(k, "path") == 0;
-  // streaming wavefront (one launch per frame batch, per-wave ray queues)
-  // for whole-scene-in-LDS scenes; MRT_STREAM=0 keeps one launch per bounce
   {
-    const char* c = mrt::diag_env("MRT_STREAM");
-    const bool want = !c || std::atoi(c) != 0;
-    r->stream_allowed = want && !r->path_mode && desc->max_path_length <= mrt::kStreamMaxL &&
-                        mrt::fast::stream_supported(desc->scene->dev, r->stack_entries);
+    const int rc = plan_kernel(r.get());
+    if (rc) return rc;
   }
-  // persistent grid of the kernel this renderer launches: the stream kernel
-  // sizes it by its own LDS (the per-bounce kernel's segment scratch grows
-  // with the grid: sized for that, a 24-KB scene image + stack left C2 at 4
-  // instead of 5 blocks per CU)
-  if (r->path_mode)
-    HIP_TRY(MRT_BUILD_CALL(desc->flags, path_grid(r->scene->dev, r->stack_entries, &r->grid)));
-  else if (r->stream_allowed)
-    HIP_TRY(MRT_BUILD_CALL(desc->flags, stream_grid(r->scene->dev, r->stack_entries, &r->grid)));
-  else
-    HIP_TRY(MRT_BUILD_CALL(desc->flags, bounce_grid(r->scene->dev, r->stack_entries, 0u, &r->grid)));
-  if (const char* g = mrt::diag_env("MRT_GRID")) r->grid = std::max<uint32_t>(1, (uint32_t)std::strtoul(g, nullptr, 0));
   // the noise schedule's upload stream, staging buffers and worker on the
   // renderer's device.  Created after the render streams: a process has 4
   // hardware queues and streams share them round-robin in creation order, so

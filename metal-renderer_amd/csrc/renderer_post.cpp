@@ -128,7 +128,7 @@ int refine_usable(const mrt_renderer* r, const char* what) {
   if (r->desc.shard_count > 1) return fail(MRT_ERR_STATE, std::string(what) + ": not on a sharded renderer");
   if (r->desc.flags & MRT_FLAG_STATIC_NOISE)
     return fail(MRT_ERR_STATE, std::string(what) + ": not with MRT_FLAG_STATIC_NOISE (every extra frame would repeat)");
-  if (!r->path_mode && !r->stream_mode)
+  if (r->plan.kind == mrt::KernelKind::Bounce)
     return fail(MRT_ERR_STATE, std::string(what) + ": the per-bounce kernel has no tile-list instantiation");
   return MRT_OK;
 }
