@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "dev_config.h"
 #include "kernels.h"
+#include "tri_accept.h"
 
 namespace mrt { namespace MRT_NS { namespace {
 
@@ -97,7 +98,10 @@ __device__ __forceinline__ bool tri_test(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float 
 // bit for bit), for the leaf loops: the distance range test is left to the
 // caller.  Every operand is needed before the first decision, so the loads of
 // a triangle are all in flight together instead of v0's being issued only
-// after the determinant test passed.
+// after the determinant test passed.  SHORT: the range test without b1 <= 1,
+// which the rest implies (tri_accept.h) — the sweep's and the camera lists'
+// form; the walk keeps the full one, and with it the path kernel its code.
+template <bool SHORT = false>
 __device__ __forceinline__ bool tri_bary(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float& t, float& u, float& v) {
   const V3 p = tcross(d, e2);
   const float det = tdot(e1, p);
@@ -109,6 +113,20 @@ __device__ __forceinline__ bool tri_bary(V3 o, V3 d, V3 v0, V3 e1, V3 e2, float&
   t = tdot(e2, q) * inv;
   u = (1.0f - b1) - b2;
   v = b1;
+  if constexpr (SHORT) {
+#if MRT_PRECISE
+    const float sum = b1 + b2;
+#else
+    // the fast build forms b1 + b2 as one fma, and with which of the two
+    // products depends on the code around it (with b2's in every leaf test
+    // of the walk's form; with b1's once b1 <= 1 was gone: two pixels of C2
+    // changed).  Written out, it is the walk's: fma(d . q, inv, b1).
+    const float sum = __builtin_fmaf(tdot(d, q), inv, b1);
+#endif
+    return bary_inside_short(det, b1, b2, sum);
+  }
+  // (tri_accept.h bary_inside restates it; the text stands here because the
+  // call orders the path kernel's compares differently)
   return (det != 0.0f) & (b1 >= 0.0f) & (b1 <= 1.0f) & (b2 >= 0.0f) & (b1 + b2 <= 1.0f);
 }
 

@@ -75,7 +75,7 @@ __device__ __forceinline__ void sweep_leaf(const DeviceScene& sc, const LdsCtx& 
   LS_ADD(4, 1);
   LS_ADD(5, ls_lanes());
   const uint32_t ka = ref & 0xFFFFu, kb = ref >> 16;
-  tri_pair<MODE>(sc, cx, o, d, tmin, ka, kb, kb != ka, h, false, 0u, nullptr);
+  tri_pair_nearest<MODE>(sc, cx, o, d, tmin, ka, kb, kb != ka, h);
 }
 
 // CAP (the stream kernel's queue levels): a pass makes at most
@@ -105,6 +105,7 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
   // operand, the record id (as a literal the mask costs an instruction of its own per record)
   uint32_t key_mask = 0x7FFFFFE0u;
   asm volatile("" : "+v"(key_mask));
+#if MRT_PRECISE
   for (uint32_t i = 0; i < n; ++i) {
     // (no record loaded ahead: the eight more scalar registers of a second
     // record cost the stream kernel scalar spills inside this loop, and the
@@ -113,7 +114,6 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
     const SweepRec rec = list[i];
     LS_T1_LOADED(42, rec[0], rec[7]);
     float te;
-#if MRT_PRECISE
     const bool hit = sweep_box(make_float4(rec[0], rec[1], rec[2], rec[3]), make_float4(rec[4], rec[5], rec[6], rec[7]),
                                o, rb, tmin, te);
     const uint32_t bit = 1u << (i & 31u);
@@ -129,17 +129,33 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
       key_of[1] = min(key_of[1], mid);
       rest |= bit;
     }
+  }
 #else
-    float tf;
-    sweep_centre(rec, rb, tmin, te, tf);
-    const uint32_t bit = fbits(rec[7]);   // 1 << i, from the record
-    // the same block with no branch: v_cmpx narrows exec to the lanes that hit,
-    // the five instructions run (in no lane, if none hit), exec comes back
-    {
+  // The centre list in groups of kSweepUnroll records, then the rest one by
+  // one (§2.1t): the loop's add, compare and taken branch come once per group.
+  // Still one record in flight, into the same eight scalar registers (a
+  // second record's registers cost scalar spills inside this loop, and the
+  // other resident waves cover the load: measured, §2.1i).  A record is
+  // addressed by a 32-bit byte offset on the list's base; its id and mask bit
+  // come from its own words 3 and 7, so no counter is kept beside the offset;
+  // exec is saved once in front of the loops: their control is wave-uniform, so
+  // every record starts with the exec they were entered with.
+  {
+    typedef const __attribute__((address_space(4))) char* SweepBytes;
+    const SweepBytes base = (SweepBytes)list;
+    uint64_t saved;
+    asm volatile("s_mov_b64 %[sv], exec" : [sv] "=s"(saved));
+    auto record = [&](uint32_t at) {
+      LS_T0();
+      const SweepRec rec = *(SweepList)(base + at);
+      LS_T1_LOADED(42, rec[0], rec[7]);
+      float te, tf;
+      sweep_centre(rec, rb, tmin, te, tf);
+      // the bookkeeping in the lanes that hit only, with no branch: v_cmpx
+      // narrows exec to them, the five instructions run (in no lane, if none
+      // hit), exec comes back
       uint32_t key, mid;
-      uint64_t saved;
       asm volatile(
-          "s_mov_b64 %[sv], exec\n\t"
           "v_cmpx_le_f32_e32 vcc, %[te], %[tf]\n\t"
           "v_and_or_b32 %[key], %[te], %[mask], %[id]\n\t"
           "v_or_b32_e32 %[rest], %[bit], %[rest]\n\t"
@@ -147,13 +163,21 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
           "v_min_u32_e32 %[k0], %[k0], %[key]\n\t"
           "v_min_u32_e32 %[k1], %[k1], %[mid]\n\t"
           "s_mov_b64 exec, %[sv]"
-          : [sv] "=&s"(saved), [key] "=&v"(key), [mid] "=&v"(mid), [k0] "+v"(key_of[0]), [k1] "+v"(key_of[1]),
-            [rest] "+v"(rest)
-          : [te] "v"(te), [tf] "v"(tf), [mask] "v"(key_mask), [id] "s"(i), [bit] "s"(bit)
+          : [key] "=&v"(key), [mid] "=&v"(mid), [k0] "+v"(key_of[0]), [k1] "+v"(key_of[1]), [rest] "+v"(rest)
+          : [te] "v"(te), [tf] "v"(tf), [mask] "v"(key_mask), [id] "s"(fbits(rec[3])), [bit] "s"(fbits(rec[7])),
+            [sv] "s"(saved)
           : "vcc");
+    };
+    constexpr uint32_t kSweepUnroll = 4;   // (2: +1.0 %, 4: +1.1 %; groups filled up with padding records lost, §2.1t)
+    const uint32_t end = (n / kSweepUnroll) * (kSweepUnroll * 32u);
+    uint32_t off = 0;
+    for (; off < end; off += kSweepUnroll * 32u) {
+#pragma unroll
+      for (uint32_t u = 0; u < kSweepUnroll; ++u) record(off + u * 32u);
     }
-#endif
+    for (; off < n * 32u; off += 32u) record(off);
   }
+#endif
   // the keys' records leave the mask (a missing key is kNone, whose id bits name record 31 — not set, or the first key's own)
   rest &= ~((1u << (key_of[0] & 31u)) | (1u << (key_of[1] & 31u)));
   // the lowest masked record leaves the mask: its triangles, and whether its recomputed entry passes the cull
@@ -188,6 +212,7 @@ __device__ __forceinline__ uint32_t sweep_nearest(const DeviceScene& sc, const L
     uint32_t ref;
     if (pop(ref)) sweep_leaf<MODE>(sc, cx, o, d, tmin, ref, h);
   }
+  h.found = h.prim != kNoPrim;   // (not kept up by the leaf tests: tri_pair_nearest)
   return CAP ? rest : 0u;
 }
 

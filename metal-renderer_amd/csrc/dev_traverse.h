@@ -142,7 +142,7 @@ __device__ __forceinline__ bool tri_pair(const DeviceScene& sc, const LdsCtx& cx
     const bool hit = ok[j] & (t[j] >= tmin) & (t[j] <= h.t);
     if (any) {
       if (hit & (prim[j] != target) & ((t[j] < h.t) | (prim[j] < target))) return true;
-    } else if (hit & (!h.found | (t[j] < h.t) | (prim[j] < h.prim))) {
+    } else if (hit & (!h.found | (t[j] < h.t) | (prim[j] < h.prim))) {   // (tri_accept.h nearest_accepts restates it)
       h.found = true;
       h.t = t[j];
       if (uv) {
@@ -156,6 +156,32 @@ __device__ __forceinline__ bool tri_pair(const DeviceScene& sc, const LdsCtx& cx
     }
   }
   return false;
+}
+
+// tri_pair for the nearest queries that keep h.prim == kNoPrim while nothing
+// is found (the sweep, the camera rays' lists): the short predicates of
+// tri_accept.h — no b1 <= 1, no !h.found — and h.found is not kept up; the
+// caller derives it from h.prim when the query is over.
+template <int MODE>
+__device__ __forceinline__ void tri_pair_nearest(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, float tmin,
+                                                 uint32_t ka, uint32_t kb, bool pair, Hit& h) {
+  float4 a0, a1, a2, b0, b1, b2;
+  fetch_tri<MODE>(sc, cx, ka, a0, a1, a2);
+  fetch_tri<MODE>(sc, cx, kb, b0, b1, b2);
+  float t[2], u[2], v[2];
+  bool ok[2];
+  ok[0] = tri_bary<true>(o, d, mk(a0), mk(a1), mk(a2), t[0], u[0], v[0]);
+  ok[1] = tri_bary<true>(o, d, mk(b0), mk(b1), mk(b2), t[1], u[1], v[1]) & pair;
+  const uint32_t prim[2] = {fbits(a0.w), fbits(b0.w)};
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (nearest_accepts_short(ok[j], t[j], tmin, h.t, prim[j], h.prim)) {
+      h.t = t[j];
+      h.u = u[j];
+      h.v = v[j];
+      h.prim = prim[j];
+    }
+  }
 }
 
 template <int MODE>
@@ -183,7 +209,7 @@ __device__ __forceinline__ void primary_nearest(const DeviceScene& sc, const Lds
                                                 uint32_t cnt, V3 o, V3 d, Hit& h) {
   h.t = __builtin_inff();
   h.u = h.v = 0.0f;
-  h.prim = 0xFFFFFFFFu;
+  h.prim = kNoPrim;
   h.found = false;
   for (uint32_t j = 0; j < cnt; j += 2) {
     const uint32_t j1 = min(j + 1, cnt - 1);
@@ -193,8 +219,9 @@ __device__ __forceinline__ void primary_nearest(const DeviceScene& sc, const Lds
     asm volatile("s_waitcnt lgkmcnt(0)" ::"s"(e0_), "s"(e1_) : "memory");
     LS_ADD(38, (uint32_t)(ls_clock() - t0_));
 #endif
-    tri_pair<MODE>(sc, cx, o, d, 0.0f, list[j], list[j1], j1 != j, h, false, 0u, nullptr);
+    tri_pair_nearest<MODE>(sc, cx, o, d, 0.0f, list[j], list[j1], j1 != j, h);
   }
+  h.found = h.prim != kNoPrim;
 }
 
 template <int STACK, int MODE, bool ANY>

@@ -51,6 +51,11 @@ def main(tag="r1", cfg="c2"):
     clk, _ = counters(os.path.join(src, "clk", "run_counter_collection.csv"))
     lanes_csv = os.path.join(src, "lanes", "run_counter_collection.csv")
     lanes = counters(lanes_csv)[0] if os.path.exists(lanes_csv) else {}
+    # the scalar side of the instruction stream (profile.sh passes scalar and issue; absent in older runs)
+    scalar_csv = os.path.join(src, "scalar", "run_counter_collection.csv")
+    issue_csv = os.path.join(src, "issue", "run_counter_collection.csv")
+    scalar = counters(scalar_csv)[0] if os.path.exists(scalar_csv) else {}
+    issue = counters(issue_csv)[0] if os.path.exists(issue_csv) else {}
     # VALUUtilization (rocprofiler-sdk counter_defs.yaml): active lanes per
     # issued VALU instruction / 64 — the share of issued lane-slots doing work
     lane_util = (lanes["SQ_THREAD_CYCLES_VALU"] / (64.0 * lanes["SQ_ACTIVE_INST_VALU"])
@@ -129,6 +134,27 @@ def main(tag="r1", cfg="c2"):
     if lane_util is not None:
         lines.append(f"* VALU lane utilisation = SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU) = {lane_util:.3f} "
                      f"(share of issued lane-slots with an active lane)")
+    # WAVE_CYCLES split: waits (WAIT_ANY), VALU (ACTIVE_INST_VALU), scalar
+    # (ACTIVE_INST_SCA), branch / message (ACTIVE_INST_MISC), and what is left:
+    # cycles a wave neither waits on a counter nor has an instruction of these
+    # classes active - issue stalls (arbitration, instruction fetch,
+    # dependencies) and the LDS / memory instructions' own issue.  Each share
+    # over the SQ_WAVE_CYCLES of its own pass.
+    split = None
+    if scalar.get("SQ_WAVE_CYCLES") and issue.get("SQ_WAVE_CYCLES"):
+        split = {"wait": sq.get("SQ_WAIT_ANY", 0) / wave_cycles,
+                 "valu": sq.get("SQ_ACTIVE_INST_VALU", 0) / wave_cycles,
+                 "scalar": scalar["SQ_ACTIVE_INST_SCA"] / scalar["SQ_WAVE_CYCLES"],
+                 "branch_misc": issue["SQ_ACTIVE_INST_MISC"] / issue["SQ_WAVE_CYCLES"]}
+        split["other"] = 1.0 - sum(split.values())
+        split = {k: round(v, 4) for k, v in split.items()}
+        lines.append(f"* scalar side per launch: branches {scalar['SQ_INSTS_BRANCH']:.3g}, scalar memory "
+                     f"{scalar['SQ_INSTS_SMEM']:.3g}, SALU issue cycles {scalar['SQ_INST_CYCLES_SALU']:.3g}, instruction "
+                     f"fetches {issue['SQ_IFETCH']:.3g}; ACTIVE_INST_ANY / WAVE_CYCLES = "
+                     f"{issue['SQ_ACTIVE_INST_ANY'] / issue['SQ_WAVE_CYCLES']:.2f}, WAIT_INST_ANY / WAVE_CYCLES = "
+                     f"{issue['SQ_WAIT_INST_ANY'] / issue['SQ_WAVE_CYCLES']:.2f}")
+        lines.append(f"* WAVE_CYCLES split: waits {split['wait']:.2f}, VALU {split['valu']:.2f}, scalar {split['scalar']:.2f}, "
+                     f"branch / message {split['branch_misc']:.2f}, issue stalls and the rest {split['other']:.2f}")
     md5_path = os.path.join(src, "lib.md5")
     lib_md5 = open(md5_path).read().strip() if os.path.exists(md5_path) else None
     m = re.search(r"(bounce_\w*kernel|path_kernel|stream_kernel)<[^>]*>", bounce["Name"])
@@ -147,7 +173,8 @@ def main(tag="r1", cfg="c2"):
                    "valu_issue_frac": None if valu_frac is None else round(valu_frac, 4),
                    "wait_any_frac": round(sq.get("SQ_WAIT_ANY", 0) / wave_cycles, 4),
                    "valu_active_frac": round(sq.get("SQ_ACTIVE_INST_VALU", 0) / wave_cycles, 4),
-                   "valu_lane_util": None if lane_util is None else round(lane_util, 4), "lanes": lanes},
+                   "valu_lane_util": None if lane_util is None else round(lane_util, 4), "lanes": lanes,
+                   "scalar": scalar, "issue": issue, "wave_cycles_split": split},
                   f, indent=1)
     print("\n".join(lines))
 

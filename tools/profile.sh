@@ -1,8 +1,12 @@
 #!/bin/bash
 # rocprofv3 passes for one bench config (run on the GPU box from the repo root).
 # usage: tools/profile.sh <tag> <config> [extra bench args]
-# pass 1: kernel trace + stats; passes 2-6: PMC counters, each in its own run
-# (FETCH_SIZE and WRITE_SIZE cannot share a pass on gfx950).
+# pass 1: kernel trace + stats; passes 2-8: PMC counters, each in its own run
+# (FETCH_SIZE and WRITE_SIZE cannot share a pass on gfx950), never combined
+# with tracing.  The last two count the scalar side of the instruction stream
+# (DESIGN §2.1t): branches, scalar memory, SALU issue cycles, and the cycles
+# with a scalar / branch-or-message / any instruction active or waiting;
+# each carries SQ_WAVE_CYCLES as its own denominator.
 TAG=${1:-r1}; CFG=${2:-c2}; shift 2
 export TMPDIR=/tmp
 # one render stream: the renderer's default two frame batches in flight
@@ -40,3 +44,5 @@ step write 400 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex 'bounce_|path_k
 step sq 400 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_SALU --kernel-include-regex 'bounce_|path_kernel|stream_kernel' -d $OUT/sq -o run -f csv -- $BENCH
 step lanes 400 rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU --kernel-include-regex 'bounce_|path_kernel|stream_kernel' -d $OUT/lanes -o run -f csv -- $BENCH
 step clk 400 rocprofv3 --pmc GRBM_GUI_ACTIVE GRBM_COUNT --kernel-include-regex 'bounce_|path_kernel|stream_kernel' -d $OUT/clk -o run -f csv -- $BENCH
+step scalar 400 rocprofv3 --pmc SQ_INSTS_BRANCH SQ_INSTS_SMEM SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_SCA SQ_WAVE_CYCLES --kernel-include-regex 'bounce_|path_kernel|stream_kernel' -d $OUT/scalar -o run -f csv -- $BENCH
+step issue 400 rocprofv3 --pmc SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_IFETCH SQ_WAVE_CYCLES --kernel-include-regex 'bounce_|path_kernel|stream_kernel' -d $OUT/issue -o run -f csv -- $BENCH

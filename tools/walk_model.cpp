@@ -36,6 +36,9 @@
 //      adversarial set extended by directions with components 0, -0, +-1e-20;
 //      no record holding a triangle the ray hits may be missed, and no key may
 //      lie beyond that triangle's cull bound.
+//   7. the leaf tests' acceptance predicates in the walk's form and in the
+//      sweep's short one (tri_accept.h), in both builds'
+//      arithmetic, on part 6's adversarial rays against every triangle.
 // The sweep's (found, t, prim) is compared with the walk's for every ray, and
 // so is every recycled ray's once it finishes; no queue may pass kStreamCap.
 //
@@ -53,6 +56,7 @@
 #include "bvh.h"
 #include "scene.h"
 #include "sweep_pairs.h"
+#include "tri_accept.h"
 
 using namespace mrt;
 
@@ -546,7 +550,7 @@ void adversarial(double& rays, double& mismatches) {
 // direction components replaced by 0, -0, 1e-20 or -1e-20 (safe_inv's +-1e20:
 // the axis' planes at +-infinity or, from an origin on a face, at 0 * 1e20),
 // phase 1's zero entries as they come and forced to -0
-void adversarial_phase1(Phase1Stats& st) {
+std::vector<Ray> adversarial_set_with_zeros() {
   std::vector<Ray> set = adversarial_set();
   const size_t base = set.size();
   const float tiny[4] = {0.0f, -0.0f, 1e-20f, -1e-20f};
@@ -561,6 +565,10 @@ void adversarial_phase1(Phase1Stats& st) {
     for (int c = 0, first = 1; c < 3; ++c) if (c != a && c != b) { r.d[c] = len > 0.0f ? r.d[c] / len : (float)first; first = 0; }
     set.push_back(r);
   }
+  return set;
+}
+void adversarial_phase1(Phase1Stats& st) {
+  const std::vector<Ray> set = adversarial_set_with_zeros();
   WalkStats scratch;
   Hit ref[kWave], tmp[kWave];
   for (size_t at = 0; at < set.size(); at += kWave) {
@@ -573,6 +581,46 @@ void adversarial_phase1(Phase1Stats& st) {
       if (nz == 0) { st.rays += one.rays; st.boxes += one.boxes; st.extra += one.extra; }
       st.missed += one.missed; st.missed_with_hit += one.missed_with_hit; st.late_keys += one.late_keys;
       st.mismatches += one.mismatches;
+    }
+  }
+}
+
+// 7. the acceptance predicates' two forms on part 6's adversarial rays
+struct AcceptStats { double rays = 0, tests = 0, bary = 0, nearest = 0; };
+void adversarial_accept(AcceptStats& st) {
+  const std::vector<Ray> set = adversarial_set_with_zeros();
+  const uint32_t T = (uint32_t)(g_bvh.tris.size() / 12);
+  struct H { float t, u, v; uint32_t prim; bool found; };
+  for (const Ray& r : set) {
+    st.rays += 1;
+    for (int fma = 0; fma < 2; ++fma) {   // the precise build's arithmetic, then the fast build's contractions
+      auto mad = [&](float a, float b, float c) { return fma ? std::fmaf(a, b, c) : a * b + c; };
+      auto dot = [&](const float* a, const float* b) { return mad(a[2], b[2], mad(a[1], b[1], a[0] * b[0])); };
+      auto cross = [&](const float* a, const float* b, float* c) {
+        c[0] = mad(a[1], b[2], -(a[2] * b[1]));
+        c[1] = mad(a[2], b[0], -(a[0] * b[2]));
+        c[2] = mad(a[0], b[1], -(a[1] * b[0]));
+      };
+      H full{kInf, 0.0f, 0.0f, kNoPrim, false}, brief = full;
+      for (uint32_t k = 0; k < T; ++k) {
+        const float* tri = &g_bvh.tris[12 * (size_t)k];
+        float p[3], s[3], q[3];
+        cross(r.d, tri + 8, p);
+        const float det = dot(tri + 4, p), inv = 1.0f / det;
+        for (int a = 0; a < 3; ++a) s[a] = r.o[a] - tri[a];
+        const float b1 = dot(s, p) * inv;
+        cross(s, tri + 4, q);
+        const float dq = dot(r.d, q), b2 = dq * inv, t = dot(tri + 8, q) * inv;
+        const float sum = fma ? std::fmaf(dq, inv, b1) : b1 + b2;
+        const bool ok = bary_inside(det, b1, b2, sum), ok_s = bary_inside_short(det, b1, b2, sum);
+        const uint32_t prim = fb(tri[3]);
+        st.tests += 1;
+        st.bary += ok != ok_s;
+        if (nearest_accepts(ok, t, 0.0f, full.t, full.found, prim, full.prim)) full = H{t, (1.0f - b1) - b2, b1, prim, true};
+        if (nearest_accepts_short(ok_s, t, 0.0f, brief.t, prim, brief.prim)) brief = H{t, (1.0f - b1) - b2, b1, prim, false};
+        st.nearest += fb(full.t) != fb(brief.t) || fb(full.u) != fb(brief.u) || fb(full.v) != fb(brief.v) ||
+                      full.prim != brief.prim || full.found != (brief.prim != kNoPrim);
+      }
     }
   }
 }
@@ -877,6 +925,10 @@ int main(int argc, char** argv) {
   std::printf("phase 1 vs walk: rays %.0f mismatches %.0f ; adversarial rays %.0f mismatches %.0f ; missed records %.0f "
               "holding a hit triangle %.0f ; late keys %.0f\n", p1.rays, p1.mismatches, adv.rays, adv.mismatches,
               p1.missed + adv.missed, p1.missed_with_hit + adv.missed_with_hit, p1.late_keys + adv.late_keys);
-  const bool p1_ok = p1.mismatches + adv.mismatches + p1.missed_with_hit + adv.missed_with_hit + p1.late_keys + adv.late_keys == 0;
+  // 7. the acceptance predicates' short forms
+  AcceptStats ac;
+  adversarial_accept(ac);
+  std::printf("accept forms: adversarial rays %.0f tests %.0f bary %.0f nearest %.0f\n", ac.rays, ac.tests, ac.bary, ac.nearest);
+  const bool p1_ok = ac.bary + ac.nearest == 0 && p1.mismatches + adv.mismatches + p1.missed_with_hit + adv.missed_with_hit + p1.late_keys + adv.late_keys == 0;
   return s.mismatches == 0 && bad == 0 && max_queue <= (uint32_t)kStreamCap && p1_ok ? 0 : 2;
 }
