@@ -24,6 +24,8 @@
 #include <cstdint>
 #include <string>
 
+#include "hip_handles.h"
+
 namespace mrt {
 
 enum class GpuBvhAlgo {
@@ -32,9 +34,8 @@ enum class GpuBvhAlgo {
 };
 
 struct GpuBvhResult {
-  float* nodes = nullptr;      // hipMalloc'd, 32 floats per BVH4 node (caller frees)
-  float* tris = nullptr;       // hipMalloc'd, 12 floats per triangle, leaf order (caller frees)
-  size_t nodes_bytes = 0, tris_bytes = 0;
+  host::DevBuf nodes;          // 32 floats per BVH4 node
+  host::DevBuf tris;           // 12 floats per triangle, leaf order (.bytes: of the triangles, 0 for an empty scene)
   int32_t root = 0;            // node index, or a leaf ref for scenes of <= max_leaf triangles
   uint32_t num_nodes = 0;
   uint32_t num_leaves = 0;

@@ -383,12 +383,7 @@ __global__ __launch_bounds__(kB) void k_collapse_level(LevelArgs a) {
   for (int k = 28; k < 32; ++k) o[k] = 0.0f;
 }
 
-struct Tmp {
-  void* p = nullptr;
-  ~Tmp() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, std::max<size_t>(n, 16)); }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
+using host::DevBuf;
 
 #define GB_TRY(x)                                                   \
   do {                                                              \
@@ -406,27 +401,27 @@ hipError_t build_bvh_gpu(const float* positions, uint32_t stride_bytes, const ui
   out = GpuBvhResult{};
   max_leaf = std::max<uint32_t>(1, std::min<uint32_t>(max_leaf ? max_leaf : 2, (uint32_t)kMaxLeafSize));
   if (T >= (1u << (32 - kLeafCountBits - 1))) { error = "too many triangles for the leaf encoding"; return hipErrorInvalidValue; }
-  hipEvent_t e0, e1;
-  GB_TRY(hipEventCreate(&e0));
-  GB_TRY(hipEventCreate(&e1));
+  host::Event e0, e1;
+  GB_TRY(e0.create(0));
+  GB_TRY(e1.create(0));
   GB_TRY(hipEventRecord(e0, s));
   const uint8_t* pos = reinterpret_cast<const uint8_t*>(positions);
   const uint32_t blocks = (std::max<uint32_t>(T, 1) + kB - 1) / kB;
   auto grid = [](uint32_t n) { return (std::max<uint32_t>(n, 1) + kB - 1) / kB; };
 
-  GB_TRY(hipMalloc(&out.tris, std::max<size_t>(16, (size_t)T * 48)));
-  out.tris_bytes = (size_t)T * 48;
+  GB_TRY(out.tris.alloc(std::max<size_t>(16, (size_t)T * 48)));
+  out.tris.bytes = (size_t)T * 48;
   if (T <= max_leaf) {
     // tiny scene: one node whose single child is the leaf of every triangle
     // (or no child at all for an empty scene)
-    Tmp order, lbox;
+    DevBuf order, lbox;
     GB_TRY(order.alloc((size_t)T * 4));
     GB_TRY(lbox.alloc((size_t)T * 32));
     std::vector<uint32_t> ho(T);
     for (uint32_t t = 0; t < T; ++t) ho[t] = t;
     if (T) {
       GB_TRY(hipMemcpyAsync(order.p, ho.data(), (size_t)T * 4, hipMemcpyHostToDevice, s));
-      k_tris_in_order<<<blocks, kB, 0, s>>>(pos, stride_bytes, indices, T, reinterpret_cast<float4*>(out.tris));
+      k_tris_in_order<<<blocks, kB, 0, s>>>(pos, stride_bytes, indices, T, out.tris.as<float4>());
       GB_TRY(hipGetLastError());
       k_leaves_refit<<<blocks, kB, 0, s>>>(pos, stride_bytes, indices, order.as<uint32_t>(), T, nullptr, nullptr,
                                            nullptr, lbox.as<float4>(), nullptr, nullptr, false);
@@ -456,15 +451,14 @@ hipError_t build_bvh_gpu(const float* positions, uint32_t stride_bytes, const ui
       out.num_leaves = 1;
       out.max_stack = 0;
     }
-    GB_TRY(hipMalloc(&out.nodes, 128));
-    out.nodes_bytes = 128;
-    GB_TRY(hipMemcpyAsync(out.nodes, node.data(), 128, hipMemcpyHostToDevice, s));
+    GB_TRY(out.nodes.alloc(128));
+    GB_TRY(hipMemcpyAsync(out.nodes.p, node.data(), 128, hipMemcpyHostToDevice, s));
     out.root = 0;
     out.num_nodes = 1;
     out.levels = 1;
   } else {
     // 1. Morton order of the triangle centroids
-    Tmp bounds, keys, keys_sorted, vals, order, child, rcount, lbox, nbox, sort_tmp;
+    DevBuf bounds, keys, keys_sorted, vals, order, child, rcount, lbox, nbox, sort_tmp;
     GB_TRY(bounds.alloc(24));
     const uint32_t init[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u};
     GB_TRY(hipMemcpyAsync(bounds.p, init, 24, hipMemcpyHostToDevice, s));
@@ -493,7 +487,7 @@ hipError_t build_bvh_gpu(const float* positions, uint32_t stride_bytes, const ui
     GB_TRY(nbox.alloc((size_t)(T - 1) * 32));
     int32_t root_bin = 0;
     if (algo == GpuBvhAlgo::kLbvh) {
-      Tmp pint, pleaf, rfirst, arr;
+      DevBuf pint, pleaf, rfirst, arr;
       GB_TRY(pint.alloc((size_t)(T - 1) * 4));
       GB_TRY(pleaf.alloc((size_t)T * 4));
       GB_TRY(rfirst.alloc((size_t)(T - 1) * 4));
@@ -513,7 +507,7 @@ hipError_t build_bvh_gpu(const float* positions, uint32_t stride_bytes, const ui
       k_leaves_refit<<<blocks, kB, 0, s>>>(pos, stride_bytes, indices, order.as<uint32_t>(), T, nullptr, nullptr,
                                            nullptr, lbox.as<float4>(), nullptr, nullptr, false);
       GB_TRY(hipGetLastError());
-      Tmp cid[2], cb[2], nn, mflag, mscan, keep, kscan;
+      DevBuf cid[2], cb[2], nn, mflag, mscan, keep, kscan;
       for (int k = 0; k < 2; ++k) {
         GB_TRY(cid[k].alloc((size_t)T * 4));
         GB_TRY(cb[k].alloc((size_t)T * 32));
@@ -562,7 +556,7 @@ hipError_t build_bvh_gpu(const float* positions, uint32_t stride_bytes, const ui
       out.build_iterations = iters;
     }
     // 3. level-synchronous collapse into BVH4 nodes (breadth-first order)
-    Tmp nodes_ub, fr_node[2], fr_need[2], fr_first[2], counters;
+    DevBuf nodes_ub, fr_node[2], fr_need[2], fr_first[2], counters;
     GB_TRY(nodes_ub.alloc((size_t)(T - 1) * 128));
     for (int k = 0; k < 2; ++k) {
       GB_TRY(fr_node[k].alloc((size_t)T * 4));
@@ -601,7 +595,7 @@ hipError_t build_bvh_gpu(const float* positions, uint32_t stride_bytes, const ui
       la.stride = stride_bytes;
       la.idx = indices;
       la.order = order.as<uint32_t>();
-      la.tris = reinterpret_cast<float4*>(out.tris);
+      la.tris = out.tris.as<float4>();
       k_collapse_level<<<grid(count), kB, 0, s>>>(la);
       GB_TRY(hipGetLastError());
       uint32_t next = 0;
@@ -620,9 +614,8 @@ hipError_t build_bvh_gpu(const float* positions, uint32_t stride_bytes, const ui
     out.max_stack = stats[1];
     out.levels = levels;
     out.root = 0;
-    out.nodes_bytes = (size_t)base * 128;
-    GB_TRY(hipMalloc(&out.nodes, out.nodes_bytes));
-    GB_TRY(hipMemcpyAsync(out.nodes, nodes_ub.p, out.nodes_bytes, hipMemcpyDeviceToDevice, s));
+    GB_TRY(out.nodes.alloc((size_t)base * 128));
+    GB_TRY(hipMemcpyAsync(out.nodes.p, nodes_ub.p, out.nodes.bytes, hipMemcpyDeviceToDevice, s));
     GB_TRY(hipStreamSynchronize(s));
   }
   GB_TRY(hipEventRecord(e1, s));
@@ -630,8 +623,6 @@ hipError_t build_bvh_gpu(const float* positions, uint32_t stride_bytes, const ui
   float ms = 0.0f;
   GB_TRY(hipEventElapsedTime(&ms, e0, e1));
   out.build_ms = ms;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   return hipSuccess;
 }
 

@@ -20,8 +20,8 @@ int exchange_buffers(mrt_renderer* r, const mrt_comm* c) {
   for (int i = 0; i < 2; ++i) {
     HIP_TRY(x.packed[i].alloc(floats * 4));
     HIP_TRY(hipMemsetAsync(x.packed[i].p, 0, floats * 4, r->stream));   // ranks with fewer tiles send zero padding
-    if (!x.pack_done[i]) HIP_TRY(hipEventCreateWithFlags(&x.pack_done[i], hipEventDisableTiming));
-    if (!x.gather_done[i]) HIP_TRY(hipEventCreateWithFlags(&x.gather_done[i], hipEventDisableTiming));
+    HIP_TRY(x.pack_done[i].ensure(hipEventDisableTiming));
+    HIP_TRY(x.gather_done[i].ensure(hipEventDisableTiming));
     x.gather_recorded[i] = false;
   }
   if (c->rank == 0) HIP_TRY(x.gathered.alloc(floats * 4 * c->nranks));
@@ -141,6 +141,19 @@ int exchange_flush(mrt_renderer* r) {
 }  // namespace host
 }  // namespace mrt
 
+// Waits first, then the members (the stream): also what a failed
+// mrt_comm_create leaves through, with no communicator and perhaps no stream
+mrt_comm::~mrt_comm() {
+  (void)hipSetDevice(device);
+  {
+    std::lock_guard<std::mutex> lk(health->m);
+    if (health->aborted) comm = nullptr;   // ncclCommAbort already freed it
+    health->comm = nullptr;                // renderers holding the health no longer touch it
+  }
+  if (stream && comm) (void)hipStreamSynchronize(stream);
+  if (comm) (void)ncclCommDestroy(comm);
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------------------
@@ -163,12 +176,12 @@ int mrt_comm_create(const void* id, uint32_t nranks, uint32_t rank, int device, 
   c->rank = rank;
   c->device = device;
   HIP_TRY(hipSetDevice(device));
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(c->stream.create());
   ncclUniqueId u;
   std::memcpy(&u, id, sizeof(u));
   const ncclResult_t e = ncclCommInitRank(&c->comm, (int)nranks, u, (int)rank);
   if (e != ncclSuccess) {
-    (void)hipStreamDestroy(c->stream);
+    c->comm = nullptr;   // (nothing for ~mrt_comm to destroy)
     return fail(MRT_ERR_HIP, std::string("ncclCommInitRank: ") + ncclGetErrorString(e));
   }
   c->health->comm = c->comm;
@@ -178,15 +191,6 @@ int mrt_comm_create(const void* id, uint32_t nranks, uint32_t rank, int device, 
 
 int mrt_comm_destroy(mrt_comm* c) {
   if (!c) return MRT_OK;
-  (void)hipSetDevice(c->device);
-  {
-    std::lock_guard<std::mutex> lk(c->health->m);
-    if (c->health->aborted) c->comm = nullptr;   // ncclCommAbort already freed it
-    c->health->comm = nullptr;                   // renderers holding the health no longer touch it
-  }
-  if (c->stream && c->comm) (void)hipStreamSynchronize(c->stream);
-  if (c->comm) (void)ncclCommDestroy(c->comm);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return MRT_OK;
 }
@@ -233,7 +237,7 @@ int mrt_renderer_exchange(mrt_renderer* r, mrt_comm* c, uint32_t mode) {
   if (rc) return rc;
   const uint32_t W = r->desc.width, H = r->desc.height;
   if (c->rank == 0 && c->nranks > 1) r->image_foreign = true;   // other ranks' tiles land in rank 0's image
-  if (!r->x.coll_done) HIP_TRY(hipEventCreateWithFlags(&r->x.coll_done, hipEventDisableTiming));
+  HIP_TRY(r->x.coll_done.ensure(hipEventDisableTiming));
   r->x.health = c->health;
   if (kind == MRT_EXCHANGE_REDUCE) {   // one in-place SUM reduce of the RGBA32F image to rank 0
     NCCL_TRY(ncclReduce(r->image, r->image, (size_t)W * H * 4, ncclFloat, ncclSum, 0, c->comm, r->stream));
@@ -264,7 +268,7 @@ int mrt_renderer_exchange(mrt_renderer* r, mrt_comm* c, uint32_t mode) {
     // stays on the main stream: a process has 4 hardware queues by default,
     // and a stream sharing one with a render stream would hold that stream's
     // launches behind the collective.
-    hipStream_t gs = r->inflight > 1 ? r->stream : c->stream;
+    hipStream_t gs = r->inflight > 1 ? r->stream.get() : c->stream.get();
     if (gs != r->stream) {
       HIP_TRY(hipEventRecord(x.pack_done[i], r->stream));
       HIP_TRY(hipStreamWaitEvent(gs, x.pack_done[i], 0));

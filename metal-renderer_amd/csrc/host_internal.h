@@ -22,6 +22,7 @@
 
 #include "../../include/mrt.h"
 #include "bvh.h"
+#include "hip_handles.h"
 #include "kernels.h"
 #include "noise_schedule.h"
 #include "scene.h"
@@ -46,18 +47,6 @@ int fail(int code, const std::string& msg);
 
 inline float bitsf(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 inline uint32_t fbits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    bytes = n;
-    return n ? hipMalloc(&p, n) : hipSuccess;
-  }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 // traversal-stack spill of the stage intersect and guide kernels (trees deeper
 // than their kMaxStack-entry LDS stack): one row of max_stack words per lane of
@@ -107,13 +96,11 @@ struct CounterLayout {
 struct DrawRecord {
   DevBuf counters;                          // per (batch, bounce) survivor totals, then the launches' grab
                                             // counters (one buffer: one memset per draw)
-  hipEvent_t start = nullptr, stop = nullptr;
-  hipEvent_t cleared = nullptr;             // the counters' memset (other render streams of the draw wait on it)
-  hipEvent_t copied = nullptr;              // the counters' copy to `host` (read-back stream) is done
-  void* host = nullptr;                     // pinned (device-mapped) copy of `counters`, written behind the draw
-  void* host_dev = nullptr;                 // its device address
-  size_t host_bytes = 0;
-  std::vector<hipEvent_t> kernel_events;    // MRT_FLAG_PROFILE: 2 per timed bounce launch
+  Event start, stop;
+  Event cleared;                            // the counters' memset (other render streams of the draw wait on it)
+  Event copied;                             // the counters' copy to `host` (read-back stream) is done
+  PinnedBuf host;                           // pinned (device-mapped) copy of `counters`, written behind the draw
+  std::vector<Event> kernel_events;         // MRT_FLAG_PROFILE: 2 per timed bounce launch
   uint32_t frames = 0;
   CounterLayout layout;                     // of `counters` as this draw uses it (bounce launches = batches * L)
   size_t events = 0;
@@ -128,8 +115,7 @@ struct DrawRecord {
   // behind the draw; its pixels are counted when the draw is read back
   uint64_t pixels = 0;
   uint32_t listed = 0;
-  uint32_t* list_host = nullptr;
-  size_t list_cap = 0;                      // entries
+  PinnedBuf list_host;                      // (one entry per tile of the frame)
 };
 constexpr int kDrawRing = 3;
 
@@ -167,14 +153,13 @@ struct ReadSpec {
 // renderer/Renderer.mm:16,593-600); their accumulations run in order on the
 // main stream because the running mean is order-dependent.
 struct FrameSlot {
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  Stream stream;            // its own, or (one slot) the main stream, borrowed
   DevBuf queue[2][mrt::kQueuePlanes];   // ray queues (the streaming wavefront: queue[0] holds the per-wave queues)
   DevBuf segments;          // 2 queues x 2 classes x grid per-block survivor counts + 2 chunk words
   DevBuf radiance;          // W*H float4, written once per owned pixel per frame
   DevBuf spill;             // traversal stack entries beyond the LDS capacity (deep BVHs)
-  hipEvent_t acc_done = nullptr;      // on the main stream: the accumulate that last read `radiance`
-  hipEvent_t kernel_done = nullptr;   // on `stream`: its last render launch
+  Event acc_done;           // on the main stream: the accumulate that last read `radiance`
+  Event kernel_done;        // on `stream`: its last render launch
   bool acc_recorded = false;
 };
 
@@ -188,21 +173,15 @@ struct FrameSlot {
 // follow every render launch of the earlier draws — has completed.
 struct CameraGen {
   DevBuf dev;                     // [CameraBlock, 64 B][candidate-list words]
-  void* host = nullptr;           // pinned staging of the same bytes
-  size_t host_bytes = 0;
-  hipEvent_t ready = nullptr;     // the upload, on the render stream that carried it
-  hipEvent_t retired = nullptr;
+  PinnedBuf host;                 // pinned staging of the same bytes
+  Event ready;                    // the upload, on the render stream that carried it
+  Event retired;
   bool busy = false;              // replaced, `retired` not yet seen complete
   bool async = false;             // uploaded asynchronously (`ready` is recorded)
   uint32_t waited_streams = 0;    // render streams (slots) ordered behind `ready`
   bool moved = false;             // not the reference's camera: launches get the block's address
   bool has_lists = false;
   uint32_t primary_bx = 0;
-  ~CameraGen() {
-    if (ready) (void)hipEventDestroy(ready);
-    if (retired) (void)hipEventDestroy(retired);
-    if (host) (void)hipHostFree(host);
-  }
 };
 constexpr size_t kCameraGens = 5;   // the one in force + four replaced ones whose draws may still execute
 
@@ -229,7 +208,7 @@ struct CommHealth {
 // the gathered slabs of every rank.
 struct Exchange {
   DevBuf packed[2], gathered, staging;
-  hipEvent_t pack_done[2] = {nullptr, nullptr}, gather_done[2] = {nullptr, nullptr};
+  Event pack_done[2], gather_done[2];
   bool gather_recorded[2] = {false, false};
   uint64_t slab_floats = 0;   // packed floats per rank (rank 0 owns the most tiles)
   int pending = -1;           // buffer whose gather awaits rank 0's unpack (overlap mode)
@@ -242,7 +221,7 @@ struct Exchange {
   // the last collective enqueued (on whichever stream it ran) and the health
   // of its communicator: mrt_renderer_sync / _exchange_flush wait for it with
   // a bound instead of blocking on a stream a stuck peer never releases
-  hipEvent_t coll_done = nullptr;
+  Event coll_done;
   bool coll_pending = false;
   std::shared_ptr<CommHealth> health;
 };
@@ -293,17 +272,25 @@ struct mrt_comm {
   ncclComm_t comm = nullptr;
   uint32_t nranks = 0, rank = 0;
   int device = 0;
-  hipStream_t stream = nullptr;
+  mrt::host::Stream stream;
   std::shared_ptr<mrt::host::CommHealth> health = std::make_shared<mrt::host::CommHealth>();
+  // the health handshake, the wait for the stream's collectives and
+  // ncclCommDestroy; then the members (exchange.cpp)
+  ~mrt_comm();
 };
 
 struct mrt_renderer {
+  // Destruction (renderer.cpp): first the waits for everything this renderer
+  // enqueued, then the two noise schedules (which joins their workers), then
+  // the members, last declared first.  After the waits no order among the
+  // members matters to the device; they are declared so that the main stream,
+  // first here, goes last, and the slots' streams after the noise schedules'.
+  ~mrt_renderer();
+  mrt::host::Stream stream;       // main stream (the caller's, borrowed, or its own); slot 0 runs on it
   const mrt_scene* scene = nullptr;
   mrt_renderer_desc desc{};
-  hipStream_t stream = nullptr;   // main stream (external or own); slot 0 runs on it
-  bool own_stream = false;
-  float* image = nullptr;
-  bool own_image = false;
+  float* image = nullptr;         // the accumulation image in use: the caller's (desc.image) or image_buf
+  mrt::host::DevBuf image_buf;    // the image where the caller gave none (re-made by resize)
   uint32_t tiles_x = 0, tiles_y = 0, owned_tiles = 0;
   uint64_t owned_pixels = 0;
   std::vector<mrt::host::FrameSlot> slots;
@@ -388,7 +375,7 @@ struct mrt_renderer {
   // MRT_REFINE_SEED_XOR) and the extra-frame counter are never reset.
   mrt::host::DevBuf extra, extra_moments, tile_list, tile_priority;
   std::unique_ptr<mrt::NoiseSchedule> refine_noise;
-  hipEvent_t list_ready = nullptr; // on the main stream: the list's upload or selection (render streams wait on it)
+  mrt::host::Event list_ready;     // on the main stream: the list's upload or selection (render streams wait on it)
   bool extras_current = false;     // E / EM exist at the current size (zero unless extras_valid)
   bool extras_valid = false;       // E holds samples: resolves merge it
   bool priority_current = false;   // a refine has run at the current size
@@ -398,12 +385,12 @@ struct mrt_renderer {
   // per-tile planes of mrt_tile_error, the device summary and its pinned host
   // copy; made at the first estimate, the planes re-made by resize
   mrt::host::DevBuf tile_error, tile_pixels, error_summary;
-  mrt_error_summary* summary_host = nullptr;
+  mrt::host::PinnedBuf summary_host;
   bool tile_error_current = false;   // an estimate has run at the current size
   struct DisplaySlot {          // mrt_renderer_display_enqueue / _map: pinned copies of the blit
-    float* host = nullptr;
-    size_t floats = 0;
-    hipEvent_t done = nullptr;
+    mrt::host::PinnedBuf host;
+    size_t floats = 0;          // of the frame it was last enqueued for
+    mrt::host::Event done;
     bool queued = false;
   } shown[MRT_DISPLAY_SLOTS];
 };
@@ -426,10 +413,9 @@ int swap_camera(mrt_renderer* r, const mrt_camera& cam);
 int read_back(mrt_renderer* r, void* out, size_t count, ReadSpec (*spec)(const mrt_renderer*), void* out2 = nullptr);
 int save_read(mrt_renderer* r, const char* path, int (*read)(mrt_renderer*, float*, size_t));
 
-// renderer_post.cpp: what resize, reset and destroy do about the derived images
+// renderer_post.cpp: what resize and reset do about the derived images
 int post_resize(mrt_renderer* r);
 int post_reset(mrt_renderer* r);
-void post_destroy(mrt_renderer* r);
 
 // exchange.cpp: what the renderer's resize / reset, sync / destroy and image
 // readers do about its pending collective and deferred unpack

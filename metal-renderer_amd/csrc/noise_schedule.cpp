@@ -20,26 +20,16 @@ NoiseSchedule::~NoiseSchedule() {
   cv_.notify_all();
   if (worker_.joinable()) worker_.join();
   if (stream_) (void)hipStreamSynchronize(stream_);   // pending uploads read the pinned stages
-  for (auto& c : chunks_) {
-    if (c->dev) (void)hipFree(c->dev);
-    if (c->ready) (void)hipEventDestroy(c->ready);
-    if (c->last_use) (void)hipEventDestroy(c->last_use);
-  }
-  for (Stage& s : stage_) {
-    if (s.host) (void)hipHostFree(s.host);
-    if (s.copied) (void)hipEventDestroy(s.copied);
-  }
-  if (stream_) (void)hipStreamDestroy(stream_);
 }
 
 hipError_t NoiseSchedule::init() {
   if (inited_) return hipSuccess;
   // the uploads' own stream: a render stream waits for a chunk's `ready`
   // event only, never for the copy queue as a whole
-  hipError_t e = hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking);
+  hipError_t e = stream_.create();
   for (Stage& s : stage_) {
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&s.host), kChunkBytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s.copied, hipEventDisableTiming);
+    if (e == hipSuccess) e = s.host.reserve(kChunkBytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = s.copied.create(hipEventDisableTiming);
   }
   if (e != hipSuccess) return e;
   worker_ = std::thread([this] { worker_main(); });
@@ -75,7 +65,7 @@ void NoiseSchedule::worker_main() {
     // wait on the copy engine, on this thread only
     if (wait_copy) (void)hipEventSynchronize(s.copied);
     const auto t0 = std::chrono::steady_clock::now();
-    generate(k, s.host);
+    generate(k, s.host.host<float>());
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     lk.lock();
     job_ms_ = ms;
@@ -104,14 +94,10 @@ hipError_t NoiseSchedule::slot_for(int64_t k, uint64_t seq, Chunk** out, int64_t
   }
   if (!best) {
     auto c = std::make_unique<Chunk>();
-    hipError_t e = hipMalloc(&c->dev, kChunkBytes);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ready, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->last_use, hipEventDisableTiming);
-    if (e != hipSuccess) {
-      if (c->dev) (void)hipFree(c->dev);
-      if (c->ready) (void)hipEventDestroy(c->ready);
-      return e;
-    }
+    hipError_t e = c->dev.alloc(kChunkBytes);
+    if (e == hipSuccess) e = c->ready.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = c->last_use.create(hipEventDisableTiming);
+    if (e != hipSuccess) return e;
     best = c.get();
     chunks_.push_back(std::move(c));
   }
@@ -128,7 +114,7 @@ hipError_t NoiseSchedule::upload_done_job(Chunk** out, uint64_t seq, int64_t kee
   hipError_t e = slot_for(job_chunk_, seq, &c, keep_lo, keep_hi);
   if (e != hipSuccess) return e;
   Stage& s = stage_[job_stage_];
-  e = hipMemcpyAsync(c->dev, s.host, kChunkBytes, hipMemcpyHostToDevice, stream_);
+  e = hipMemcpyAsync(c->dev.p, s.host.host(), kChunkBytes, hipMemcpyHostToDevice, stream_);
   if (e == hipSuccess) e = hipEventRecord(s.copied, stream_);
   if (e == hipSuccess) e = hipEventRecord(c->ready, stream_);
   if (e != hipSuccess) return e;

@@ -30,6 +30,8 @@
 #include <thread>
 #include <vector>
 
+#include "hip_handles.h"
+
 namespace mrt {
 
 class NoiseSchedule {
@@ -39,9 +41,9 @@ class NoiseSchedule {
 
   struct Chunk {
     int64_t index = -1;                   // chunk k: frames [64k - 2, 64k + 64); -1 = empty
-    void* dev = nullptr;                  // kChunkTables x kNoiseFloats floats
-    hipEvent_t ready = nullptr;           // upload complete (recorded on the schedule's stream)
-    hipEvent_t last_use = nullptr;        // recorded on the renderer's main stream after each draw that read it
+    host::DevBuf dev;                     // kChunkTables x kNoiseFloats floats
+    host::Event ready;                    // upload complete (recorded on the schedule's stream)
+    host::Event last_use;                 // recorded on the renderer's main stream after each draw that read it
     bool uploaded = false, used = false;
     uint32_t waited_streams = 0;          // render slots whose stream already waits on `ready` (bit per slot)
     uint64_t lru = 0;
@@ -83,8 +85,8 @@ class NoiseSchedule {
  private:
   enum JobState { kIdle, kQueued, kRunning, kDone };
   struct Stage {
-    float* host = nullptr;                // pinned, kChunkTables x kNoiseFloats
-    hipEvent_t copied = nullptr;          // the last upload from it
+    host::PinnedBuf host;                 // kChunkTables x kNoiseFloats
+    host::Event copied;                   // the last upload from it
     bool copy_recorded = false;
   };
   void worker_main();
@@ -97,7 +99,7 @@ class NoiseSchedule {
   uint64_t seed_;
   bool static_;
   bool inited_ = false;
-  hipStream_t stream_ = nullptr;
+  host::Stream stream_;                          // (destroyed after the chunks and stages its copies touch)
   std::vector<std::unique_ptr<Chunk>> chunks_;   // stable addresses: a draw holds Chunk pointers
   uint64_t tick_ = 0;
   Stage stage_[2];

@@ -42,10 +42,10 @@ int finalize_draw(mrt_renderer* r, DrawRecord& d) {
   // copied to pinned memory on the main stream behind the draw: no
   // synchronous copy, so the host never waits for work queued after it
   HIP_TRY(hipEventSynchronize(d.copied));
-  const uint32_t* cnt = static_cast<const uint32_t*>(d.host);
+  const uint32_t* cnt = d.host.host<uint32_t>();
   if (d.listed) {   // a refine draw: its list is on the host by now (uploaded from there, or copied back behind the draw)
     d.pixels = 0;
-    for (uint32_t k = 0; k < d.listed; ++k) d.pixels += pixels_of_tile(r, d.list_host[k]);
+    for (uint32_t k = 0; k < d.listed; ++k) d.pixels += pixels_of_tile(r, d.list_host.host<uint32_t>()[k]);
     r->refine_stats.paths += d.pixels * d.frames;
   }
   uint64_t active = d.pixels * d.frames;   // bounce 0: every rendered pixel's camera ray
@@ -58,7 +58,7 @@ int finalize_draw(mrt_renderer* r, DrawRecord& d) {
   r->stats.kernel_launches += (uint64_t)lay.batches * mrt::launches_per_batch(r->plan.kind, lay.L);
   for (uint32_t k = 0; k < lay.batches; ++k) {
     unsigned long long sp[2];
-    std::memcpy(sp, static_cast<const char*>(d.host) + lay.span(k), 16);
+    std::memcpy(sp, d.host.host<char>() + lay.span(k), 16);
     const unsigned long long t0 = ~sp[0], t1 = sp[1];
     if (sp[0] && t1 >= t0 && r->wall_khz > 0.0) {
       r->stats.span_ms += (double)(t1 - t0) / r->wall_khz;
@@ -122,21 +122,15 @@ int install_camera(mrt_renderer* r, bool idle) {
   if (bytes > cap_bytes) return fail(MRT_ERR_STATE, "camera: candidate lists exceed their bound");
   auto size_gen = [&](CameraGen* c) -> int {
     if (c->dev.bytes < cap_bytes) HIP_TRY(c->dev.alloc(cap_bytes));
-    if (c->host_bytes < cap_bytes) {
-      if (c->host) HIP_TRY(hipHostFree(c->host));
-      c->host = nullptr;
-      c->host_bytes = 0;
-      HIP_TRY(hipHostMalloc(&c->host, cap_bytes, hipHostMallocDefault));
-      c->host_bytes = cap_bytes;
-    }
+    HIP_TRY(c->host.reserve(cap_bytes, hipHostMallocDefault));
     return MRT_OK;
   };
   CameraGen* g = nullptr;
   while (idle && r->cams.size() < kCameraGens) {   // all generations exist from create on
     r->cams.emplace_back(new CameraGen());
     CameraGen* c = r->cams.back().get();
-    HIP_TRY(hipEventCreateWithFlags(&c->ready, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->retired, hipEventDisableTiming));
+    HIP_TRY(c->ready.create(hipEventDisableTiming));
+    HIP_TRY(c->retired.create(hipEventDisableTiming));
   }
   for (auto& c : r->cams) {
     if (idle) {
@@ -163,17 +157,17 @@ int install_camera(mrt_renderer* r, bool idle) {
     HIP_TRY(hipEventSynchronize(g->retired));
     g->busy = false;
   }
-  if (g->dev.bytes < cap_bytes || g->host_bytes < cap_bytes)   // sized in the idle path for this frame size
+  if (g->dev.bytes < cap_bytes || g->host.bytes() < cap_bytes)   // sized in the idle path for this frame size
     return fail(MRT_ERR_STATE, "camera: generation smaller than the frame's bound");
-  std::memcpy(g->host, &cb, sizeof(cb));
-  if (lists) std::memcpy(static_cast<char*>(g->host) + sizeof(cb), pl.words.data(), pl.words.size() * 4);
+  std::memcpy(g->host.host(), &cb, sizeof(cb));
+  if (lists) std::memcpy(g->host.host<char>() + sizeof(cb), pl.words.data(), pl.words.size() * 4);
   if (idle) {
-    HIP_TRY(hipMemcpy(g->dev.p, g->host, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g->dev.p, g->host.host(), bytes, hipMemcpyHostToDevice));
     g->async = false;
     g->waited_streams = ~0u;
   } else {
     const uint32_t slot = r->slot_next;
-    HIP_TRY(hipMemcpyAsync(g->dev.p, g->host, bytes, hipMemcpyHostToDevice, r->slots[slot].stream));
+    HIP_TRY(hipMemcpyAsync(g->dev.p, g->host.host(), bytes, hipMemcpyHostToDevice, r->slots[slot].stream));
     HIP_TRY(hipEventRecord(g->ready, r->slots[slot].stream));
     g->async = true;
     g->waited_streams = 1u << slot;
@@ -276,10 +270,10 @@ int alloc_frame_buffers(mrt_renderer* r) {
     // spill rows of max_stack words per lane (dev_lds.h LdsCtx::spill_lane)
     if (r->plan.spills && !fs.spill.p) HIP_TRY(fs.spill.alloc((size_t)dev.max_stack * r->plan.grid * 256 * 4));
   }
-  if (r->own_image) {
-    if (r->image) (void)hipFree(r->image);
+  if (!r->desc.image) {
     r->image = nullptr;
-    HIP_TRY(hipMalloc(&r->image, (size_t)W * H * 16));
+    HIP_TRY(r->image_buf.alloc((size_t)W * H * 16));
+    r->image = r->image_buf.as<float>();
   }
   HIP_TRY(hipMemsetAsync(r->image, 0, (size_t)W * H * 16, r->stream));
   if (r->desc.flags & MRT_FLAG_MOMENTS) {
@@ -332,18 +326,11 @@ int size_draw_record(DrawRecord& d, size_t timed_events, bool* fresh) {
     HIP_TRY(d.counters.alloc(counter_bytes));
     *fresh = true;
   }
-  if (d.host_bytes < counter_bytes) {
-    if (d.host) HIP_TRY(hipHostFree(d.host));
-    d.host = d.host_dev = nullptr;
-    d.host_bytes = 0;
-    HIP_TRY(hipHostMalloc(&d.host, counter_bytes, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(&d.host_dev, d.host, 0));
-    d.host_bytes = counter_bytes;
-  }
+  HIP_TRY(d.host.reserve(counter_bytes, hipHostMallocMapped));
   while (d.kernel_events.size() < timed_events) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreate(&e));
-    d.kernel_events.push_back(e);
+    Event e;
+    HIP_TRY(e.create(0));
+    d.kernel_events.push_back(std::move(e));
   }
   return MRT_OK;
 }
@@ -390,7 +377,7 @@ int bounce_args(const mrt_renderer* r, const DrawSource& src, const DrawRecord& 
     a.in_q.plane[p] = fs.queue[b & 1][p].as<float4>();
     a.out_q.plane[p] = fs.queue[(b + 1) & 1][p].as<float4>();
   }
-  a.noise_window = static_cast<const float4*>(bt.noise->dev);
+  a.noise_window = bt.noise->dev.as<const float4>();
   a.noise_offset = (uint32_t)((int64_t)bt.f - mrt::NoiseSchedule::first_frame(mrt::NoiseSchedule::chunk_of((int64_t)bt.f)));
   a.radiance = fs.radiance.as<float4>();
   a.stack_spill = fs.spill.as<uint32_t>();
@@ -428,7 +415,7 @@ mrt::AccumArgs accum_args(const mrt_renderer* r, const DrawSource& src, const Dr
   acc.tile_list = src.list;
   if (fold) {
     acc.counters = d.counters.as<uint32_t>();
-    acc.host_counters = static_cast<uint32_t*>(d.host_dev);
+    acc.host_counters = static_cast<uint32_t*>(d.host.device());
     acc.copy_words = d.layout.batches * d.layout.L;
     acc.span_word = (uint32_t)(d.layout.span_off / 4);
     acc.span_words = d.layout.batches * 4;
@@ -528,18 +515,12 @@ int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src) {
     // counts its pixels).  On the main stream, which follows every launch that
     // read the previous list; the render streams wait for it through the event
     const uint32_t T = r->tiles_x * r->tiles_y;
-    if (d.list_cap < T) {
-      if (d.list_host) HIP_TRY(hipHostFree(d.list_host));
-      d.list_host = nullptr;
-      d.list_cap = 0;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d.list_host), (size_t)T * 4, hipHostMallocDefault));
-      d.list_cap = T;
-    }
+    HIP_TRY(d.list_host.reserve((size_t)T * 4, hipHostMallocDefault));
     if (src.host_list) {
-      std::memcpy(d.list_host, src.host_list, (size_t)src.tiles * 4);
-      HIP_TRY(hipMemcpyAsync(src.list, d.list_host, (size_t)src.tiles * 4, hipMemcpyHostToDevice, r->stream));
+      std::memcpy(d.list_host.host(), src.host_list, (size_t)src.tiles * 4);
+      HIP_TRY(hipMemcpyAsync(src.list, d.list_host.host(), (size_t)src.tiles * 4, hipMemcpyHostToDevice, r->stream));
     } else {
-      HIP_TRY(hipMemcpyAsync(d.list_host, src.list, (size_t)src.tiles * 4, hipMemcpyDeviceToHost, r->stream));
+      HIP_TRY(hipMemcpyAsync(d.list_host.host(), src.list, (size_t)src.tiles * 4, hipMemcpyDeviceToHost, r->stream));
     }
     HIP_TRY(hipEventRecord(r->list_ready, r->stream));
   }
@@ -627,7 +608,7 @@ int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src) {
   // (no stream of its own: a process has few hardware queues — 4 by
   // default — and two streams sharing one serialise their launches)
   if (!r->counter_fold)
-    HIP_TRY(hipMemcpyAsync(d.host, d.counters.p, d.layout.bytes, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipMemcpyAsync(d.host.host(), d.counters.p, d.layout.bytes, hipMemcpyDeviceToHost, r->stream));
   HIP_TRY(hipEventRecord(d.copied, r->stream));
   d.pending = true;
   d.frames = n;
@@ -668,20 +649,18 @@ int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out) {
   r->desc = *desc;
   r->desc.shard_count = S;
   HIP_TRY(hipSetDevice(desc->scene->device));
-  if (desc->stream) {
-    r->stream = (hipStream_t)desc->stream;
-  } else {
-    HIP_TRY(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-    r->own_stream = true;
-  }
-  r->own_image = desc->image == nullptr;
-  r->image = desc->image;
+  // (a failure from here on leaves through ~mrt_renderer: nothing made so far leaks)
+  if (desc->stream)
+    r->stream.borrow((hipStream_t)desc->stream);
+  else
+    HIP_TRY(r->stream.create());
+  r->image = desc->image;   // (null: alloc_frame_buffers makes image_buf)
   r->noise = std::make_unique<mrt::NoiseSchedule>(desc->seed, (desc->flags & MRT_FLAG_STATIC_NOISE) != 0);
   for (DrawRecord& d : r->draws) {
-    HIP_TRY(hipEventCreate(&d.start));
-    HIP_TRY(hipEventCreate(&d.stop));
-    HIP_TRY(hipEventCreateWithFlags(&d.cleared, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&d.copied, hipEventDisableTiming));
+    HIP_TRY(d.start.create(0));
+    HIP_TRY(d.stop.create(0));
+    HIP_TRY(d.cleared.create(hipEventDisableTiming));
+    HIP_TRY(d.copied.create(hipEventDisableTiming));
   }
   if (const char* dbg = mrt::diag_env("MRT_DEBUG")) r->debug = (uint32_t)std::strtoul(dbg, nullptr, 0);
   if (const char* v = mrt::diag_env("MRT_COUNTER_FOLD")) r->counter_fold = std::atoi(v) != 0;
@@ -704,14 +683,12 @@ int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out) {
   r->slots.resize(r->inflight);
   for (uint32_t k = 0; k < r->inflight; ++k) {
     FrameSlot& fs = r->slots[k];
-    if (r->inflight == 1) {   // one slot: everything in order on the main stream
-      fs.stream = r->stream;
-    } else {
-      HIP_TRY(hipStreamCreateWithFlags(&fs.stream, hipStreamNonBlocking));
-      fs.own_stream = true;
-    }
-    HIP_TRY(hipEventCreateWithFlags(&fs.acc_done, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&fs.kernel_done, hipEventDisableTiming));
+    if (r->inflight == 1)   // one slot: everything in order on the main stream
+      fs.stream.borrow(r->stream);
+    else
+      HIP_TRY(fs.stream.create());
+    HIP_TRY(fs.acc_done.create(hipEventDisableTiming));
+    HIP_TRY(fs.kernel_done.create(hipEventDisableTiming));
   }
   if (const char* v = mrt::diag_env("MRT_PRIMARY")) r->primary_allowed = std::atoi(v) != 0;
   if (const char* v = mrt::diag_env("MRT_PRIMARY_CAP"))
@@ -724,7 +701,9 @@ int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out) {
   // renderer's device.  Created after the render streams: a process has 4
   // hardware queues and streams share them round-robin in creation order, so
   // a stream created before the render streams pushed a render stream onto a
-  // queue another stream's work serialises with (C2 -10 %, C4 -7 %, measured r6)
+  // queue another stream's work serialises with (C2 -10 %, C4 -7 %, measured r6).
+  // So the order of creation is fixed, whatever type holds a stream: the main
+  // stream, the slots' streams, this one, then refine_noise's at the first refine
   HIP_TRY(r->noise->init());
   (void)mrt_camera_default(&r->camera);
   int rc = alloc_frame_buffers(r.get());
@@ -736,7 +715,7 @@ int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out) {
 int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   if (!r) return fail(MRT_ERR_INVALID, "null renderer");
   if (width < 2 || height < 2 || width > 32768 || height > 32768) return fail(MRT_ERR_INVALID, "bad size");
-  if (!r->own_image) return fail(MRT_ERR_STATE, "cannot resize an externally owned image");
+  if (r->desc.image) return fail(MRT_ERR_STATE, "cannot resize an externally owned image");
   int rc = finalize_pending(r);
   if (rc) return rc;
   rc = exchange_drop(r, true);   // a pending gather was packed for the old size: never unpack it into the new image
@@ -757,7 +736,7 @@ int mrt_renderer_reset(mrt_renderer* r) {
   // pixels it does not own stay 0 — unless an exchange wrote other ranks'
   // tiles into the image: only then is it cleared (stream-ordered after
   // the pending draws).  An external image is always cleared.
-  if (r->image_foreign || !r->own_image) {
+  if (r->image_foreign || r->desc.image) {
     HIP_TRY(hipMemsetAsync(r->image, 0, (size_t)r->desc.width * r->desc.height * 16, r->stream));
     r->image_foreign = false;
   }
@@ -861,37 +840,21 @@ int mrt_renderer_stats(const mrt_renderer* r, mrt_stats* stats) {
 
 int mrt_renderer_destroy(mrt_renderer* r) {
   if (!r) return MRT_OK;
-  (void)exchange_wait(r);   // bounded: a failed communicator is aborted, not waited for
-  (void)finalize_pending(r);
-  if (r->stream) (void)hipStreamSynchronize(r->stream);
-  for (int i = 0; i < 2; ++i) {   // an overlapped gather may still read the packed tiles
-    if (r->x.gather_recorded[i]) (void)hipEventSynchronize(r->x.gather_done[i]);
-    if (r->x.pack_done[i]) (void)hipEventDestroy(r->x.pack_done[i]);
-    if (r->x.gather_done[i]) (void)hipEventDestroy(r->x.gather_done[i]);
-  }
-  if (r->x.coll_done) (void)hipEventDestroy(r->x.coll_done);
-  if (r->own_image && r->image) (void)hipFree(r->image);
-  post_destroy(r);
-  for (FrameSlot& fs : r->slots) {
-    if (fs.acc_done) (void)hipEventDestroy(fs.acc_done);
-    if (fs.kernel_done) (void)hipEventDestroy(fs.kernel_done);
-    if (fs.own_stream) (void)hipStreamDestroy(fs.stream);
-  }
-  r->slots.clear();
-  for (DrawRecord& d : r->draws) {
-    for (hipEvent_t e : d.kernel_events) (void)hipEventDestroy(e);
-    if (d.start) (void)hipEventDestroy(d.start);
-    if (d.stop) (void)hipEventDestroy(d.stop);
-    if (d.cleared) (void)hipEventDestroy(d.cleared);
-    if (d.copied) (void)hipEventDestroy(d.copied);
-    if (d.host) (void)hipHostFree(d.host);
-    if (d.list_host) (void)hipHostFree(d.list_host);
-  }
-  r->refine_noise.reset();
-  r->noise.reset();   // joins the worker; the draws reading its chunks have finished (stream synchronised above)
-  if (r->own_stream) (void)hipStreamDestroy(r->stream);
   delete r;
   return MRT_OK;
 }
 
 }  // extern "C"
+
+// Waits first, then the members (host_internal.h).  Also what a failed
+// mrt_renderer_create leaves through, on a renderer built by half: no draw
+// pending, no collective, perhaps no stream yet.
+mrt_renderer::~mrt_renderer() {
+  (void)exchange_wait(this);   // bounded: a failed communicator is aborted, not waited for
+  (void)finalize_pending(this);
+  if (stream) (void)hipStreamSynchronize(stream);
+  for (int i = 0; i < 2; ++i)   // an overlapped gather may still read the packed tiles
+    if (x.gather_recorded[i]) (void)hipEventSynchronize(x.gather_done[i]);
+  refine_noise.reset();
+  noise.reset();   // joins the worker; the draws reading its chunks have finished (stream synchronised above)
+}

@@ -138,7 +138,7 @@ int refine_usable(const mrt_renderer* r, const char* what) {
 int ensure_extras(mrt_renderer* r) {
   HIP_TRY(hipSetDevice(r->scene->device));
   const size_t bytes = image_bytes(r);
-  if (!r->list_ready) HIP_TRY(hipEventCreateWithFlags(&r->list_ready, hipEventDisableTiming));
+  HIP_TRY(r->list_ready.ensure(hipEventDisableTiming));
   if (!r->refine_noise) {
     r->refine_noise = std::make_unique<mrt::NoiseSchedule>(r->desc.seed ^ MRT_REFINE_SEED_XOR, false);
     HIP_TRY(r->refine_noise->init());
@@ -212,8 +212,7 @@ int estimate(mrt_renderer* r, const mrt_svgf_params& sp, const mrt_adaptive_para
   rc = size_group({&r->tile_error, &r->tile_pixels}, (size_t)T * 4, &r->tile_error_current);
   if (rc) return rc;
   if (!r->error_summary.p) HIP_TRY(r->error_summary.alloc(sizeof(mrt_error_summary)));
-  if (!r->summary_host)
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->summary_host), sizeof(mrt_error_summary), hipHostMallocDefault));
+  HIP_TRY(r->summary_host.reserve(sizeof(mrt_error_summary), hipHostMallocDefault));
   rc = mrt_renderer_denoise_variance(r, &sp);
   if (rc) return rc;
   rc = mrt_tile_error(r->denoised.as<float>(), r->variance.as<float>(), r->guide_n.as<float>(),
@@ -225,9 +224,9 @@ int estimate(mrt_renderer* r, const mrt_svgf_params& sp, const mrt_adaptive_para
   rc = mrt_tile_threshold(r->tile_error.as<float>(), r->tile_pixels.as<uint32_t>(), T, threshold, T,
                           r->tile_list.as<uint32_t>(), r->error_summary.as<mrt_error_summary>(), r->stream);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(r->summary_host, r->error_summary.p, sizeof(mrt_error_summary), hipMemcpyDeviceToHost, r->stream));
+  HIP_TRY(hipMemcpyAsync(r->summary_host.host(), r->error_summary.p, sizeof(mrt_error_summary), hipMemcpyDeviceToHost, r->stream));
   HIP_TRY(hipStreamSynchronize(r->stream));
-  *out = *r->summary_host;
+  *out = *r->summary_host.host<mrt_error_summary>();
   r->list_count = out->tiles_listed;
   return MRT_OK;
 }
@@ -295,16 +294,6 @@ int post_reset(mrt_renderer* r) {
   HIP_TRY(hipMemsetAsync(r->extra_moments.p, 0, image_bytes(r), r->stream));
   r->extras_valid = false;
   return MRT_OK;
-}
-
-// mrt_renderer_destroy: what is not a DevBuf (the renderer's work has finished)
-void post_destroy(mrt_renderer* r) {
-  for (auto& ds : r->shown) {
-    if (ds.done) (void)hipEventDestroy(ds.done);
-    if (ds.host) (void)hipHostFree(ds.host);
-  }
-  if (r->list_ready) (void)hipEventDestroy(r->list_ready);
-  if (r->summary_host) (void)hipHostFree(r->summary_host);
 }
 
 }  // namespace host
@@ -663,15 +652,13 @@ int mrt_renderer_display_enqueue(mrt_renderer* r, uint32_t flags, float compare_
   const size_t need = image_bytes(r) / 4;
   auto& ds = r->shown[slot];
   if (ds.queued) HIP_TRY(hipEventSynchronize(ds.done));   // its previous copy may still be landing
-  if (ds.floats != need) {
-    if (ds.host) HIP_TRY(hipHostFree(ds.host));
-    ds.host = nullptr;
+  if (ds.floats != need) {   // (the pinned block only grows: a smaller frame uses its front)
     ds.floats = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ds.host), need * 4, hipHostMallocDefault));
+    HIP_TRY(ds.host.reserve(need * 4, hipHostMallocDefault));
     ds.floats = need;
   }
-  if (!ds.done) HIP_TRY(hipEventCreateWithFlags(&ds.done, hipEventDisableTiming));
-  rc = display_to(r, src, flags, compare_scale, ds.host);
+  HIP_TRY(ds.done.ensure(hipEventDisableTiming));
+  rc = display_to(r, src, flags, compare_scale, ds.host.host<float>());
   if (rc) return rc;
   HIP_TRY(hipEventRecord(ds.done, r->stream));
   ds.queued = true;
@@ -684,7 +671,7 @@ int mrt_renderer_display_map(mrt_renderer* r, uint32_t slot, const float** rgba,
   auto& ds = r->shown[slot];
   if (!ds.queued || ds.floats != image_bytes(r) / 4) return fail(MRT_ERR_STATE, "display slot not enqueued at the current size");
   HIP_TRY(hipEventSynchronize(ds.done));
-  *rgba = ds.host;
+  *rgba = ds.host.host<float>();
   if (count) *count = ds.floats;
   return MRT_OK;
 }

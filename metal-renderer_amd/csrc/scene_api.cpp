@@ -103,15 +103,15 @@ int build_main_tree(SceneBuild& b) {
                            b.builder == MRT_BVH_DEVICE_PLOC ? mrt::GpuBvhAlgo::kPloc : mrt::GpuBvhAlgo::kLbvh, nullptr, g,
                            err) != hipSuccess)
       return fail(MRT_ERR_HIP, "device BVH build failed: " + err);
-    s->nodes.p = g.nodes; s->nodes.bytes = g.nodes_bytes;
-    s->tris.p = g.tris; s->tris.bytes = g.tris_bytes;
+    s->nodes = std::move(g.nodes);
+    s->tris = std::move(g.tris);
     b.build_ms = g.build_ms;
     // host copy of the tree for mrt_scene_check_bvh / info
     mrt::BvhResult& t = s->bvh;
-    t.nodes.resize(g.nodes_bytes / 4);
-    t.tris.resize(g.tris_bytes / 4);
-    HIP_TRY(hipMemcpy(t.nodes.data(), g.nodes, g.nodes_bytes, hipMemcpyDeviceToHost));
-    if (g.tris_bytes) HIP_TRY(hipMemcpy(t.tris.data(), g.tris, g.tris_bytes, hipMemcpyDeviceToHost));
+    t.nodes.resize(s->nodes.bytes / 4);
+    t.tris.resize(s->tris.bytes / 4);
+    HIP_TRY(hipMemcpy(t.nodes.data(), s->nodes.p, s->nodes.bytes, hipMemcpyDeviceToHost));
+    if (s->tris.bytes) HIP_TRY(hipMemcpy(t.tris.data(), s->tris.p, s->tris.bytes, hipMemcpyDeviceToHost));
     t.root = g.root;
     t.num_nodes = g.num_nodes;
     t.num_leaves = g.num_leaves;
@@ -516,10 +516,8 @@ int accel_build(mrt_accel* a) {
                            a->info.builder == MRT_BVH_DEVICE_PLOC ? mrt::GpuBvhAlgo::kPloc : mrt::GpuBvhAlgo::kLbvh,
                            s, g, err) != hipSuccess)
       return fail(MRT_ERR_HIP, "device BVH build failed: " + err);
-    (void)a->nodes.alloc(0);
-    (void)a->tris.alloc(0);
-    a->nodes.p = g.nodes; a->nodes.bytes = g.nodes_bytes;
-    a->tris.p = g.tris; a->tris.bytes = g.tris_bytes;
+    a->nodes = std::move(g.nodes);   // (a rebuild: the previous tree is freed)
+    a->tris = std::move(g.tris);
     a->dev.root = g.root;
     a->dev.num_nodes = g.num_nodes;
     a->dev.max_stack = g.max_stack;
