@@ -1,26 +1,20 @@
 """Host side of adaptive sampling (include/mrt.h "adaptive sampling", DESIGN.md
-§2.1q): the parameters and their check and the exported symbols (libmrt, no
-device), the numpy models of merge, priority and selection
-(tests/adaptive_model.py) on hand-built cases, and the equal-budget quality
+§2.1q): the parameters and their check (libmrt, no device), the numpy models
+of merge, priority and selection (tests/adaptive_model.py) on hand-built cases, and the equal-budget quality
 study of the definitions on oracle renders."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
-from adaptive_model import TILE, accumulate64, counted_merge, tile_mask, tile_pixels, tile_priority, tile_select, tiles_of
+from adaptive_model import accumulate64, counted_merge, tile_mask, tile_pixels, tile_priority, tile_select, tiles_of
 from denoise_model import rel_mse
 from helpers import SEED, host_threads
 from test_denoise_host import oracle_guides
 from variance_model import lum, variance
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MISS = np.uint32(0xFFFFFFFF).view(np.float32)
 
 
-# ---- parameters and symbols ------------------------------------------------------
+# ---- parameters ------------------------------------------------------
 def test_default_params(mrt_mod):
     p = mrt_mod.AdaptiveParams.default()
     assert p.luminance_floor == np.float32(0.01)
@@ -36,29 +30,6 @@ def test_check_rejects_bad_floor(mrt_mod, value):
     mrt_mod.AdaptiveParams(1e-30).check()
     assert mrt_mod.lib().mrt_adaptive_params_check(None) == -1
     assert mrt_mod.lib().mrt_adaptive_params_default(None) == -1
-
-
-def test_library_exports_the_adaptive_symbols(mrt_mod):
-    header = open(os.path.join(ROOT, "include", "mrt.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|const char\*)\s+(mrt_\w+)\s*\(", header, re.M))
-    want = {"mrt_adaptive_params_default", "mrt_adaptive_params_check", "mrt_counted_merge", "mrt_tile_priority",
-            "mrt_tile_select", "mrt_renderer_draw_tiles", "mrt_renderer_refine", "mrt_renderer_read_extra",
-            "mrt_renderer_read_extra_moments", "mrt_renderer_read_tile_priority", "mrt_renderer_read_tile_list",
-            "mrt_renderer_refine_stats"}
-    assert want <= declared and want <= set(mrt_mod.EXPORTED)
-    lib = ctypes.CDLL(mrt_mod.LIB_PATH)
-    assert not [n for n in sorted(want) if not hasattr(lib, n)]
-    for n in want:
-        assert getattr(mrt_mod.lib(), n).argtypes is not None, n      # bound with a signature
-    m = re.search(r"#define\s+MRT_REFINE_SEED_XOR\s+0x([0-9A-Fa-f]+)ull", header)
-    assert m and int(m.group(1), 16) == mrt_mod.REFINE_SEED_XOR == 0x9E3779B97F4A7C15
-    assert mrt_mod.lib().mrt_abi_version() == 9
-    for cls, c_name in ((mrt_mod.AdaptiveParams, "mrt_adaptive_params"), (mrt_mod.RefineStats, "mrt_refine_stats")):
-        body = re.search(r"typedef struct " + c_name + r" \{(.*?)\} " + c_name + ";", header, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        fields = [f for decl in re.findall(r"(?:float|uint64_t|uint32_t)\s+([^;]+);", body) for f in re.split(r"\s*,\s*", decl.strip())]
-        assert fields == [k for k, _ in cls._fields_], c_name
-    assert mrt_mod.TILE == TILE == 64
 
 
 # ---- the models on hand-built cases ---------------------------------------------

@@ -1,12 +1,10 @@
 """Host side of sampling to a target error (include/mrt.h "adaptive sampling",
-DESIGN.md §2.1r): the parameters, their check and the exported symbols (libmrt,
-no device); the numpy models of the estimate (tests/converge_model.py) on
-hand-built cases; the calibration of the estimate against oracle renders, which
+DESIGN.md §2.1r): the parameters and their check (libmrt, no device); the
+numpy models of the estimate (tests/converge_model.py) on hand-built cases;
+the calibration of the estimate against oracle renders, which
 is why it is built on the denoised image; and the stop rule's loop through the
 models."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -17,13 +15,10 @@ from helpers import SEED, host_threads
 from test_denoise_host import oracle_guides
 from variance_model import lum, svgf_atrous, variance
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MISS = np.uint32(0xFFFFFFFF).view(np.float32)
-NEW_SYMBOLS = {"mrt_tile_error", "mrt_tile_threshold", "mrt_converge_params_default", "mrt_converge_params_check",
-               "mrt_renderer_error", "mrt_renderer_read_tile_error", "mrt_renderer_converge"}
 
 
-# ---- parameters and symbols ------------------------------------------------------
+# ---- parameters ------------------------------------------------------
 def test_default_params(mrt_mod):
     p = mrt_mod.ConvergeParams.default()
     assert p.as_dict() == {"target_error": np.float32(1e-3), "frames_per_pass": 8, "max_passes": 64, "max_tiles": 0,
@@ -59,33 +54,6 @@ def test_check_accepts_the_edges_and_rejects_null(mrt_mod):
     assert L.mrt_renderer_error(None, None, 0.0, 0.0, ctypes.byref(s)) == -1
     assert L.mrt_renderer_converge(None, None, ctypes.byref(res)) == -1
     assert L.mrt_renderer_read_tile_error(None, None, None, 0) == -1
-
-
-def _header_fields(header, c_name):
-    body = re.search(r"typedef struct " + c_name + r" \{(.*?)\} " + c_name + ";", header, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    decls = re.findall(r"(?:float|uint64_t|uint32_t|mrt_error_summary)\s+([^;]+);", body)
-    return [re.sub(r"\[\d+\]", "", f) for decl in decls for f in re.split(r"\s*,\s*", decl.strip())]
-
-
-def test_library_exports_the_converge_symbols(mrt_mod):
-    header = open(os.path.join(ROOT, "include", "mrt.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|const char\*)\s+(mrt_\w+)\s*\(", header, re.M))
-    assert NEW_SYMBOLS <= declared and NEW_SYMBOLS <= set(mrt_mod.EXPORTED)
-    lib = ctypes.CDLL(mrt_mod.LIB_PATH)
-    assert not [n for n in sorted(NEW_SYMBOLS) if not hasattr(lib, n)]
-    for n in NEW_SYMBOLS:
-        assert getattr(mrt_mod.lib(), n).argtypes is not None, n      # bound with a signature
-    assert mrt_mod.lib().mrt_abi_version() == 9
-    assert re.search(r"#define\s+MRT_ABI_VERSION\s+9\b", header)
-    for cls, c_name in ((mrt_mod.ConvergeParams, "mrt_converge_params"), (mrt_mod.ErrorSummary, "mrt_error_summary"),
-                        (mrt_mod.ConvergeResult, "mrt_converge_result")):
-        assert _header_fields(header, c_name) == [k for k, _ in cls._fields_], c_name
-    assert ctypes.sizeof(mrt_mod.ErrorSummary) == 32 and ctypes.sizeof(mrt_mod.ConvergeResult) == 80
-    assert ctypes.sizeof(mrt_mod.ConvergeParams) == 32
-    for name in ("error_estimate", "converge", "read_tile_error"):
-        assert callable(getattr(mrt_mod.Renderer, name))
-    assert callable(mrt_mod.tile_error) and callable(mrt_mod.tile_threshold)
 
 
 # ---- the models on hand-built cases ---------------------------------------------

@@ -1,6 +1,7 @@
 """CPU: the product's host side (libmrt.so without a device).
 
-* the C-ABI library loads and exports every symbol include/mrt.h declares;
+* the Objective-C facade calls only what include/mrt.h declares (the Python
+  binding is held against the header in test_abi_host.py);
 * scene import + flattening (renderer/Renderer.mm:255-454) is byte-identical
   to the oracle's independent restatement on every shipped scene;
 * the BVH builder's output passes its structural check (every primitive in
@@ -19,17 +20,6 @@ from helpers import SEED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES = ["cornellbox", "white-box", "CornellBox-Water-plastic", "CornellBox-Water-mirror", "CornellBox-Water"]
-
-
-def test_library_exports_every_declared_symbol(mrt_mod):
-    header = open(os.path.join(ROOT, "include", "mrt.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|const char\*)\s+(mrt_\w+)\s*\(", header, re.M))
-    assert len(declared) >= 25
-    lib = ctypes.CDLL(mrt_mod.LIB_PATH)
-    missing = [n for n in sorted(declared) if not hasattr(lib, n)]
-    assert not missing, missing
-    assert set(mrt_mod.EXPORTED) == declared
-    assert mrt_mod.lib().mrt_abi_version() == 9
 
 
 def test_objc_facade_binds_only_declared_symbols(mrt_mod):

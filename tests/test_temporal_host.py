@@ -44,11 +44,6 @@ def test_null_params_rejected(mrt_mod):
     assert mrt_mod.lib().mrt_reproject_params_default(None) == -1
 
 
-def test_abi_version_unchanged(mrt_mod):
-    assert mrt_mod.lib().mrt_abi_version() == 9
-    assert mrt_mod.DISPLAY_RESOLVED == 8
-
-
 # ---- model identities --------------------------------------------------------
 def test_resolve_branches():
     rng = np.random.default_rng(3)

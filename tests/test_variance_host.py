@@ -3,10 +3,6 @@ check (libmrt, no device), the model's temporal estimate against numpy's sample
 variance, and the quality gate of the definitions — the numpy model
 (tests/variance_model.py) on oracle renders, moments from the model's
 recurrence over the oracle's per-frame radiance."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
@@ -14,8 +10,6 @@ from denoise_model import NOT_FILTERABLE, atrous, rel_mse, words
 from helpers import SEED, host_threads
 from test_denoise_host import oracle_guides
 from variance_model import lum, moments_accumulate32, svgf_atrous, variance
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_params(mrt_mod):
@@ -45,19 +39,6 @@ def test_check_rejects_bad_fields(mrt_mod, field, value):
 def test_null_params_rejected(mrt_mod):
     assert mrt_mod.lib().mrt_svgf_params_check(None) == -1
     assert mrt_mod.lib().mrt_svgf_params_default(None) == -1
-
-
-def test_library_exports_the_variance_symbols(mrt_mod):
-    header = open(os.path.join(ROOT, "include", "mrt.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|const char\*)\s+(mrt_\w+)\s*\(", header, re.M))
-    want = {"mrt_moments", "mrt_svgf_params_default", "mrt_svgf_params_check", "mrt_variance", "mrt_denoise_variance",
-            "mrt_renderer_read_moments", "mrt_renderer_moments", "mrt_renderer_denoise_variance",
-            "mrt_renderer_read_variance", "mrt_debug_denoise_variance_step"}
-    assert want <= declared and want <= set(mrt_mod.EXPORTED)
-    lib = ctypes.CDLL(mrt_mod.LIB_PATH)
-    assert not [n for n in sorted(want) if not hasattr(lib, n)]
-    assert re.search(r"#define\s+MRT_FLAG_MOMENTS\s+32u", header) and mrt_mod.FLAG_MOMENTS == 32
-    assert mrt_mod.lib().mrt_abi_version() == 9
 
 
 def test_temporal_estimate_is_the_sample_variance_of_the_mean():
