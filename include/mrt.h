@@ -149,6 +149,17 @@ int mrt_scene_destroy(mrt_scene* scene);
  * leaf, every child box contains its subtree's triangles, depth within the
  * traversal stack.  0 = valid. */
 int mrt_scene_check_bvh(const mrt_scene* scene);
+/* Host only (works on device = -1 scenes).  Two scenes are MOTION-COMPATIBLE —
+ * two poses of one mesh, for mrt_guides_motion and mrt_renderer_move_scene —
+ * iff they have the same number of triangles and of materials and, for every
+ * primitive index k, references[k].materialIndex is equal in both and
+ * references[k].lightTriangleIndex is 0xFFFFFFFF in both or in neither.
+ * Positions, normals, material values, the BVH, its builder and leaf size may
+ * differ; a scene is compatible with itself.  MRT_OK, or MRT_ERR_INVALID with a
+ * message that names the first difference.  Constant time for a compatible
+ * pair: the counts and a 64-bit digest of the compared words, folded when the
+ * scene is created, are what is compared; only a pair that differs is walked. */
+int mrt_scene_motion_compatible(const mrt_scene* a, const mrt_scene* b);
 
 /* ---- acceleration structure over raw buffers (the MPS interface) --------
  * MPSTriangleAccelerationStructure (Renderer.mm:456-462): vertexBuffer with
@@ -349,12 +360,48 @@ int mrt_temporal_resolve(const float* image, uint64_t frames, const float* histo
  *   rgb = sum b prev_q.rgb / B, h = min(max_history, sum b prev_q.w / B)
  *   (a count of 0, possible only with max_history = 0, goes with rgb 0).
  * The inputs are only read.  params == NULL, W < 2, H < 2, or history_out
- * overlapping an input, is MRT_ERR_INVALID.  Static geometry only (no motion
- * vectors). */
+ * overlapping an input, is MRT_ERR_INVALID.  With the guide planes of the
+ * current view in cur_guide_n / cur_guide_p the geometry is taken as static;
+ * with the motion planes of mrt_guides_motion in their place it moves (below). */
 int mrt_reproject(const float* prev, const float* prev_guide_n, const float* prev_guide_p,
                   const mrt_camera* prev_cam /* NULL = default */, const float* cur_guide_n, const float* cur_guide_p,
                   float* history_out, uint32_t width, uint32_t height, const mrt_reproject_params* params,
                   void* stream);
+
+/* Moving geometry.  mrt_guides of `scene` and, beside its
+ * planes, two MOTION PLANES: for the surface point each pixel sees now, where
+ * that point was in prev_scene — another pose of the same mesh
+ * (mrt_scene_motion_compatible), on the same device.  guide_n and guide_p are
+ * bitwise what mrt_guides(scene, cam, ...) writes.  For a pixel whose guide ray
+ * hits primitive k of `scene` at barycentrics (u, v) and distance t, with guide
+ * word `word`:
+ *   motion_p[p] = (position of that point in prev_scene, t)
+ *   motion_n[p] = (shading normal of that point in prev_scene, bits(word))
+ * both interpolated from prev_scene's primitive k with the weights (u, v,
+ * (1 - u) - v) and the expressions mrt_shade uses; a miss writes the miss
+ * record of mrt_guides to all four planes.  prev_scene == scene gives motion
+ * planes bitwise equal to the guide planes.
+ * Passed to mrt_reproject as cur_guide_n / cur_guide_p, with prev_scene's guide
+ * planes and camera as the previous ones, the motion planes make it a
+ * motion-vector reprojection: the point's OLD position is projected through
+ * the old camera, and each tap condition compares the old frame with itself —
+ *   word_q == word_p: the old frame showed the same material there (the word
+ *     of a primitive is the same in both poses);
+ *   n_p.n_q >= normal_cos_min: the old frame's normal at the tap against the
+ *     point's own normal as it was then, so a rotating surface keeps its taps;
+ *   |n_p.(x_q - x_p)| <= plane_tolerance t_p: the surface the old frame showed
+ *     at the tap lies in the point's old tangent plane — the point was visible
+ *     then, not hidden behind something else (the disocclusion test), within a
+ *     tolerance scaled by the point's distance now;
+ *   prev_q.w > 0 and finite: the old frame had samples there.
+ * MRT_ERR_INVALID (nothing is written) for scenes that are not
+ * motion-compatible, scenes on different devices, a host-only scene, any two of
+ * the four planes overlapping, and mrt_guides' own argument errors.  Both
+ * scenes must stay alive until the stream has run the call; the stack-spill
+ * rule of mrt_guides applies to `scene`.  flags: MRT_FLAG_PRECISE. */
+int mrt_guides_motion(const mrt_scene* scene, const mrt_scene* prev_scene, const mrt_camera* cam /* NULL = default */,
+                      uint32_t width, uint32_t height, float* guide_n, float* guide_p, float* motion_n,
+                      float* motion_p /* W*H*4 floats each, device */, uint32_t flags, void* stream);
 
 /* ---- variance-guided denoising ----------------------------------------------
  * The spatial half of SVGF (Schied et al., HPG 2017): a
@@ -627,6 +674,22 @@ typedef struct mrt_stats {         /* counters are cumulative since create/resiz
 int mrt_renderer_create(const mrt_renderer_desc* desc, mrt_renderer** out);
 /* drawableSizeWillChange: reallocate, frameIndex = 0 (Renderer.mm:640-657) */
 int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height);
+/* mrt_renderer_resize to the same size with another scene (any scene on the
+ * renderer's device: no condition on its topology) in the old one's place.
+ * Waits for the renderer's queued work, as resize does; plans the kernel again
+ * (kind, stack variant and grid may all change, mrt_stats.kernel with them);
+ * re-makes what is sized by the scene (frame queues, stack spill, the guide
+ * pass's spill); rebuilds the camera's candidate lists; restarts accumulation at
+ * frame 0 and the counters of mrt_stats as resize does; invalidates every
+ * derived buffer, the history and the extra images; drops a pending exchange;
+ * clears an external image.  The camera, the firefly setting, the flags and
+ * both noise schedules persist (the refine schedule's counter is never reset).
+ * After set_scene(S); draw(n) the image and the moments are bitwise those of a
+ * fresh renderer created on S with the same desc and camera after draw(n).  A
+ * failure before the swap (a null, host-only or other-device scene, a kernel
+ * that cannot be planned) leaves the renderer as it was.  The old scene may be
+ * destroyed once the call returns. */
+int mrt_renderer_set_scene(mrt_renderer* r, const mrt_scene* scene);
 /* frameIndex = 0 without reallocating: the next frame overwrites every pixel
  * the renderer owns (until then the image keeps its content; pixels written
  * by an exchange or mrt_renderer_tiles_write, and an external image, are
@@ -711,10 +774,33 @@ int mrt_renderer_save_denoised(mrt_renderer* r, const char* path);   /* .pfm / .
  * new camera in force with the history dropped, as after set_camera.  With no
  * frame accumulated and no valid
  * history there is nothing to carry: the call is set_camera.
- * mrt_renderer_set_camera, _reset and _resize invalidate the history.
+ * mrt_renderer_set_camera, _reset, _resize and _set_scene invalidate the history.
  * MRT_ERR_STATE on a sharded renderer (shard_count > 1): its image is whole
  * only on rank 0 after an exchange, and a sharded history is not supported. */
 int mrt_renderer_move_camera(mrt_renderer* r, const mrt_camera* cam, const mrt_reproject_params* params);
+/* Moving geometry: mrt_renderer_move_camera across a scene change.  `scene` is
+ * another pose of the scene in force (mrt_scene_motion_compatible) on the same
+ * device; cam NULL keeps the camera.  In order: the checks (MRT_ERR_STATE on a
+ * sharded renderer; the camera; the params; motion compatibility) — a failed
+ * check changes nothing; with no frame accumulated and no valid history the
+ * call is set_scene, plus set_camera when cam is given.  Otherwise, in stream
+ * order: the old camera's guide planes are traced if they are not current;
+ * prev = resolve(image, frames accumulated, history if valid), the extra images
+ * merged in, and the same for the moments, exactly as move_camera; the call's
+ * one host wait; the swap of mrt_renderer_set_scene, which keeps prev, the
+ * previous guide planes and the history buffers; the new camera, if any;
+ * mrt_guides_motion(scene, old scene, camera in force) into the guide planes and
+ * two motion planes (32 B per pixel, allocated at the first move_scene, re-made
+ * by resize); history = mrt_reproject(prev, previous guides, old camera,
+ * motion_n, motion_p, params), and likewise the moments history.  The extra
+ * images are cleared, as move_camera clears them.  After move_scene(S, C);
+ * draw(n) the image is bitwise that of a fresh renderer on S with camera C after
+ * draw(n).  A failure after the swap leaves the new scene in force without a
+ * history, as set_scene would.  The OLD scene must stay alive until the renderer
+ * next synchronises (mrt_renderer_sync, a read, resize, set_scene): the motion
+ * pass reads it on the stream. */
+int mrt_renderer_move_scene(mrt_renderer* r, const mrt_scene* scene, const mrt_camera* cam /* NULL = keep */,
+                            const mrt_reproject_params* params /* NULL = default */);
 /* resolved = resolve(image, frames accumulated, history if valid), into a
  * buffer the renderer owns, enqueued without a host wait.  With a valid history
  * and no new frame it is the pure reprojection: the zero-latency frame after a

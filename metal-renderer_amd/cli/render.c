@@ -32,6 +32,7 @@
  *                   [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]
  *                   [--firefly [K]]
  *                   [--orbit-steps K --orbit-degrees D]
+ *                   [--then-scene NAME|PATH.obj [--then-mtl PATH]]
  *                   [--refine-passes P --refine-frames F --refine-tiles K]
  *                   [--target-error E [--converge-frames F] [--converge-max-passes P]
  *                    [--converge-budget N]]
@@ -61,6 +62,13 @@
  * and --spp frames are drawn.  --out then receives the resolved image
  * (mrt_renderer_resolve / _save_resolved), or with --denoise the image of
  * mrt_renderer_denoise_resolved.
+ * --then-scene OBJ [--then-mtl MTL] (single rank only, not with --orbit-steps):
+ * moving geometry.  OBJ is another pose of --scene (the same triangles and
+ * materials in the same order, mrt_scene_motion_compatible; --procedural applies
+ * to both).  After the first --spp frames mrt_renderer_move_scene puts it in the
+ * first scene's place, carrying the accumulated history through the motion, and
+ * --spp more frames are drawn.  --out then receives the resolved image, or what
+ * --denoise / --denoise-variance make of it.
  * --denoise: after the last draw (and the exchange: only rank 0, which holds
  * the whole image, denoises) mrt_renderer_denoise with the defaults for --spp
  * frames, and --out receives the denoised image (mrt_renderer_save_denoised);
@@ -97,6 +105,8 @@
 typedef struct {
   const char* scene;
   const char* mtl;
+  const char* then_scene;   /* moving geometry (mrt_renderer_move_scene) */
+  const char* then_mtl;
   const char* out;
   const char* exchange;
   uint32_t procedural, width, height, spp, max_path_length, gpus, flags;
@@ -153,12 +163,16 @@ static void usage(void) {
           "                  [--denoise-variance] [--svgf-iterations N] [--svgf-sigma-luminance X]\n"
           "                  [--firefly [K]]\n"
           "                  [--orbit-steps K --orbit-degrees D]\n"
+          "                  [--then-scene NAME|PATH.obj [--then-mtl PATH]]\n"
           "                  [--refine-passes P --refine-frames F --refine-tiles K]\n"
           "                  [--target-error E [--converge-frames F] [--converge-max-passes P] [--converge-budget N]]\n"
           "  --orbit-steps K --orbit-degrees D (one rank): after the first --spp frames, K times: turn the eye by D\n"
           "  degrees about the world's vertical (y) axis through the target, whatever --up says, move the camera\n"
           "  keeping the accumulated history, draw --spp frames; --out gets the resolved image.  --orbit-degrees\n"
           "  alone is an error.\n"
+          "  --then-scene OBJ [--then-mtl MTL] (one rank, not with --orbit-steps): OBJ is another pose of --scene;\n"
+          "  after the first --spp frames it takes the scene's place, the accumulated history carried through the\n"
+          "  motion, and --spp more frames are drawn; --out gets the resolved image.\n"
           "  --refine-passes P --refine-frames F --refine-tiles K (one rank): after the draws, P times F extra frames\n"
           "  of the K 64x64 tiles whose variance says they need them most; --out gets an image that holds them.\n"
           "  --target-error E (one rank, not with --refine-*): after the draws, F extra frames per pass of the tiles\n"
@@ -196,6 +210,8 @@ static int parse(int argc, char** argv, options* o) {
 #define VAL(name) (strcmp(a, name) == 0 && v && ++i)
     if (VAL("--scene")) o->scene = v;
     else if (VAL("--mtl")) o->mtl = v;
+    else if (VAL("--then-scene")) o->then_scene = v;
+    else if (VAL("--then-mtl")) o->then_mtl = v;
     else if (VAL("--out")) o->out = v;
     else if (VAL("--exchange")) o->exchange = v;
     else if (VAL("--procedural")) o->procedural = (uint32_t)strtoul(v, NULL, 0);
@@ -253,6 +269,14 @@ static int parse(int argc, char** argv, options* o) {
   }
   if (o->orbit_steps && o->gpus > 1) {
     fprintf(stderr, "mrt_render: --orbit-steps is single rank only (a sharded renderer keeps no temporal history)\n");
+    return -1;
+  }
+  if (o->then_mtl && !o->then_scene) {
+    fprintf(stderr, "mrt_render: --then-mtl needs --then-scene OBJ\n");
+    return -1;
+  }
+  if (o->then_scene && (o->gpus > 1 || o->orbit_steps)) {
+    fprintf(stderr, "mrt_render: --then-scene is single rank only and excludes --orbit-steps\n");
     return -1;
   }
   if (o->denoise_variance && o->denoise) {
@@ -421,6 +445,23 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
     if (mrt_renderer_move_camera(r, &cam, NULL)) return die("mrt_renderer_move_camera");
     if (mrt_renderer_draw_n(r, o->spp)) return die("mrt_renderer_draw_n");
   }
+  mrt_scene* first_scene = NULL;
+  if (o->then_scene) {   /* (single rank) waits for the GPU once, inside the move */
+    char obj2[PATH_MAX];
+    if (resolve_scene(o->then_scene, obj2, sizeof obj2)) {
+      fprintf(stderr, "mrt_render: cannot resolve scene %s\n", o->then_scene);
+      return 1;
+    }
+    mrt_scene_desc sd2 = sd;
+    sd2.obj_path = obj2;
+    sd2.mtl_override = o->then_mtl;
+    mrt_scene* next = NULL;
+    if (mrt_scene_create(&sd2, &next)) return die("mrt_scene_create (--then-scene)");
+    if (mrt_renderer_move_scene(r, next, NULL, NULL)) return die("mrt_renderer_move_scene");
+    first_scene = scene;   /* read by the motion pass until the renderer has synchronised */
+    scene = next;
+    if (mrt_renderer_draw_n(r, o->spp)) return die("mrt_renderer_draw_n");
+  }
   for (uint32_t k = 0; k < o->refine_passes; ++k)   /* (single rank) nor does this */
     if (mrt_renderer_refine(r, o->refine_frames, o->refine_tiles, NULL)) return die("mrt_renderer_refine");
   if (o->target_set) {   /* (single rank) this waits for the GPU once per estimate */
@@ -476,13 +517,13 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
       if (mrt_denoise_params_default(st.frame_index, &dp)) return die("mrt_denoise_params_default");
       if (o->denoise_iterations_set) dp.iterations = o->denoise_iterations;
       if (o->denoise_sigma_set) dp.sigma_color = o->denoise_sigma_color;
-      if (o->orbit_steps || o->refine_set) {
+      if (o->orbit_steps || o->refine_set || o->then_scene) {
         if (mrt_renderer_denoise_resolved(r, &dp)) return die("mrt_renderer_denoise_resolved");
       } else if (mrt_renderer_denoise(r, &dp)) {
         return die("mrt_renderer_denoise");
       }
       if (mrt_renderer_save_denoised(r, o->out)) return die("mrt_renderer_save_denoised");
-    } else if (o->orbit_steps || o->refine_set) {
+    } else if (o->orbit_steps || o->refine_set || o->then_scene) {
       if (mrt_renderer_resolve(r)) return die("mrt_renderer_resolve");
       if (mrt_renderer_save_resolved(r, o->out)) return die("mrt_renderer_save_resolved");
     } else if (mrt_renderer_save_image(r, o->out)) {
@@ -499,6 +540,7 @@ static int run_rank(const options* o, uint32_t rank, const int* to_peer, int fro
   }
   mrt_renderer_destroy(r);
   mrt_scene_destroy(scene);
+  if (first_scene) mrt_scene_destroy(first_scene);
   if (comm) mrt_comm_destroy(comm);
   return 0;
 }

@@ -242,6 +242,10 @@ struct mrt_scene {
   int device = 0;
   mrt::host::DevBuf isect_spill;       // stage intersect stack spill for trees deeper than kMaxStack
   mrt::HostScene host;
+  // what motion compatibility compares, folded when the scene is flattened: the
+  // material index and light status of every primitive, in order (FNV-1a, 64
+  // bits), so that a per-pose call compares two words instead of two arrays
+  uint64_t motion_digest = 0;
   mrt::BvhResult bvh;
   // the shadow-ray occluder tree (occluders.h) as uploaded after the main
   // tree: node refs rebased by bvh.num_nodes, leaf records by the triangle
@@ -307,7 +311,7 @@ struct mrt_renderer {
   double wall_khz = 0.0;    // device wall clock (span timestamps; 0 = spans off, MRT_SPANS=0)
   bool image_foreign = false;   // the image holds pixels this renderer did not render (exchange / tiles_write)
   // the persistent kernel this renderer launches, its LDS stack and its grid
-  // (kernel_plan.h; filled once at create by renderer.cpp plan_kernel)
+  // (kernel_plan.h; filled by renderer.cpp plan_kernel at create and again by a scene swap)
   mrt::KernelPlan plan;
   // noise tables in device chunks of 64 frames, generated ahead on a worker
   // thread and uploaded on their own stream (noise_schedule.h)
@@ -353,6 +357,10 @@ struct mrt_renderer {
   // counted image beside the accumulation image, in the view of `camera`.
   mrt::host::DevBuf prev_guide_n, prev_guide_p, temporal_prev, history, resolved;
   bool history_valid = false;      // `history` holds the reprojection into the camera in force
+  // moving geometry (mrt_renderer_move_scene): where each pixel's surface point
+  // was in the previous scene (mrt_guides_motion), 32 B per pixel; allocated at
+  // the first move_scene, re-made by resize
+  mrt::host::DevBuf motion_n, motion_p;
   bool resolved_current = false;   // a resolve has run at the current size
   // variance-guided denoising (MRT_FLAG_MOMENTS): the moments image lives with
   // the image (create, resize); its scratch and history are allocated at the
@@ -404,18 +412,25 @@ mrt::CameraBlock camera_block(const mrt_camera& c);
 bool camera_is_default(const mrt_camera& c);
 int guides_with_spill(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, float* guide_n,
                       float* guide_p, uint32_t flags, uint32_t* spill, void* stream);
+int guides_motion_with_spill(const mrt_scene* scene, const mrt_scene* prev_scene, const mrt_camera* cam, uint32_t W,
+                             uint32_t H, float* guide_n, float* guide_p, float* motion_n, float* motion_p,
+                             uint32_t flags, uint32_t* spill, void* stream);
 
 // renderer.cpp: the draw loop and its statistics; `cam` put in force, or the
-// renderer left as it was; a reader's checks, wait and copy; an image to a file
+// renderer left as it was; `scene` (and `cam`, unless null) put in force at
+// frame 0 behind a wait for the renderer's work, or the renderer left as it
+// was; a reader's checks, wait and copy; an image to a file
 int draw_frames(mrt_renderer* r, uint32_t n, const DrawSource& src);
 int finalize_pending(mrt_renderer* r);
 int swap_camera(mrt_renderer* r, const mrt_camera& cam);
+int swap_scene(mrt_renderer* r, const mrt_scene* scene, const mrt_camera* cam);
 int read_back(mrt_renderer* r, void* out, size_t count, ReadSpec (*spec)(const mrt_renderer*), void* out2 = nullptr);
 int save_read(mrt_renderer* r, const char* path, int (*read)(mrt_renderer*, float*, size_t));
 
-// renderer_post.cpp: what resize and reset do about the derived images
+// renderer_post.cpp: what resize, reset and a scene swap do about the derived images
 int post_resize(mrt_renderer* r);
 int post_reset(mrt_renderer* r);
+int post_set_scene(mrt_renderer* r);
 
 // exchange.cpp: what the renderer's resize / reset, sync / destroy and image
 // readers do about its pending collective and deferred unpack

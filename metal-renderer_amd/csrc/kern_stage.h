@@ -182,6 +182,59 @@ __global__ __launch_bounds__(kBlock) void guide_kernel(DeviceScene sc, uint32_t 
   }
 }
 
+// guide_kernel's interpolation of one scene's six shading records at (wu, wv, ww)
+__device__ __forceinline__ void guide_point(const float4 (&R)[6], float wu, float wv, float ww, V3& hv, V3& hn) {
+  hv = add(add(mul(mk(R[0]), wu), mul(mk(R[1]), wv)), mul(mk(R[2]), ww));
+  hn = normalize(add(add(mul(mk(R[3]), wu), mul(mk(R[4]), wv)), mul(mk(R[5]), ww)));
+}
+
+// guide_kernel across a scene change (mrt_guides_motion): gn / gp exactly as
+// guide_kernel writes them for `sc`, and in mn / mp the same surface point —
+// primitive h.prim at the hit's barycentrics — as it lies in the previous scene,
+// interpolated from `prev_prims` (that scene's shading records, 6 float4 per
+// primitive, the same primitive order and count: the host checks it) with the
+// same expressions: mp[p] = (previous position, t), mn[p] = (previous shading
+// normal, bits(word)), word and t the current hit's.  A miss writes the miss
+// record to all four planes.  The previous records are addressed only behind
+// the trace (their base is a kernel argument, held in SGPRs): the traversal
+// loop carries nothing for them, and the twelve loads of a hit go out together.
+template <int STACK>
+__global__ __launch_bounds__(kBlock) void guide_motion_kernel(DeviceScene sc, const float4* __restrict__ prev_prims,
+                                                              uint32_t W, uint32_t H, CameraBlock cam, uint32_t moved,
+                                                              float4* gn, float4* gp, float4* mn, float4* mp,
+                                                              uint32_t* spill) {
+  const LdsCtx cx = stage_lds<kGlobal>(sc, 0, spill);
+  const uint32_t count = W * H;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) {
+    const uint32_t x = i % W, y = i / W;
+    V3 o, d;
+    camera_ray<true>(x, y, W, H, make_float4(0.5f, 0.5f, 0.5f, 0.5f), nullptr, moved ? &cam : nullptr, o, d);
+    const Hit h = trace_nearest<STACK, kGlobal>(sc, cx, o, d, 0.0f, __builtin_inff());
+    float4 n = make_float4(0.0f, 0.0f, 0.0f, bitsf(kMissWord)), p = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    float4 qn = n, qp = p;
+    if (h.found && h.prim < sc.num_triangles) {   // (always: the bound keeps a bad record inside both buffers)
+      const float wu = h.u, wv = h.v, ww = (1.0f - h.u) - h.v;   // shade_hit's interpolation
+      float4 C[6], Q[6];
+#pragma unroll
+      for (uint32_t k = 0; k < 6; ++k) C[k] = fetch_prim<kGlobal>(sc, cx, h.prim, k);
+#pragma unroll
+      for (uint32_t k = 0; k < 6; ++k) Q[k] = prev_prims[6 * (size_t)h.prim + k];
+      const float w = bitsf(fbits(C[0].w) | (fbits(C[1].w) != 0xFFFFFFFFu ? kNotFilterable : 0u));
+      V3 hv, hn;
+      guide_point(C, wu, wv, ww, hv, hn);
+      n = make_float4(hn.x, hn.y, hn.z, w);
+      p = make_float4(hv.x, hv.y, hv.z, h.t);
+      guide_point(Q, wu, wv, ww, hv, hn);
+      qn = make_float4(hn.x, hn.y, hn.z, w);
+      qp = make_float4(hv.x, hv.y, hv.z, h.t);
+    }
+    gn[i] = n;
+    gp[i] = p;
+    mn[i] = qn;
+    mp[i] = qp;
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void shade_kernel(DeviceScene sc, uint32_t W, uint32_t H, uint32_t f,
                                                        uint32_t L, const float4* noise,
                                                        const RefIntersection* isect, RefRay* rays,

@@ -243,6 +243,12 @@ constexpr uint32_t kShadeDebugMaterial = 1u;   // BounceArgs::flags / launch_sha
      null = the reference's camera; spill as launch_intersect */                                          \
   hipError_t launch_guides(const DeviceScene& sc, uint32_t W, uint32_t H, const CameraBlock* cam,         \
                            float* guide_n, float* guide_p, uint32_t* spill, hipStream_t s);               \
+  /* launch_guides of `sc` and, in motion_n / motion_p, each pixel's surface point as it lies in the      \
+     previous scene, whose shading records (6 float4 per primitive, sc.num_triangles of them) are         \
+     prev_prims (kern_stage.h guide_motion_kernel) */                                                     \
+  hipError_t launch_guides_motion(const DeviceScene& sc, const float* prev_prims, uint32_t W, uint32_t H, \
+                                  const CameraBlock* cam, float* guide_n, float* guide_p, float* motion_n, \
+                                  float* motion_p, uint32_t* spill, hipStream_t s);                       \
   hipError_t launch_shade(const DeviceScene& sc, uint32_t W, uint32_t H, uint32_t frame_index,            \
                           uint32_t max_path_length, const float* noise, const RefIntersection* isect,     \
                           RefRay* rays, RefShadowRay* srays, uint32_t flags, hipStream_t s);              \

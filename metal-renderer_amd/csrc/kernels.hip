@@ -396,6 +396,31 @@ hipError_t launch_tiles_move(const float4* src, float4* dst, uint32_t W, uint32_
   return hipGetLastError();
 }
 
+// (behind every older launcher: the unit's other kernels keep their place in its code object)
+hipError_t launch_guides_motion(const DeviceScene& sc, const float* prev_prims, uint32_t W, uint32_t H,
+                                const CameraBlock* cam, float* guide_n, float* guide_p, float* motion_n,
+                                float* motion_p, uint32_t* spill, hipStream_t s) {
+  if (sc.width != 4 || !prev_prims || (cam && cam->lens_radius != 0.0f)) return hipErrorInvalidValue;
+  float4* gn = reinterpret_cast<float4*>(guide_n);
+  float4* gp = reinterpret_cast<float4*>(guide_p);
+  float4* mn = reinterpret_cast<float4*>(motion_n);
+  float4* mp = reinterpret_cast<float4*>(motion_p);
+  const float4* pp = reinterpret_cast<const float4*>(prev_prims);
+  const CameraBlock cb = cam ? *cam : CameraBlock{};
+  const uint32_t moved = cam ? 1u : 0u, count = W * H;
+  if (sc.max_stack <= (uint32_t)kMaxStack) {   // the two variants of launch_guides, chosen as it chooses them
+    const size_t lds = (size_t)kMaxStack * kBlock * 4;
+    guide_motion_kernel<kMaxStack><<<dim3(blocks_for(count)), dim3(kBlock), lds, s>>>(sc, pp, W, H, cb, moved, gn, gp,
+                                                                                      mn, mp, nullptr);
+  } else {
+    if (!spill) return hipErrorInvalidValue;
+    const size_t lds = (size_t)32 * kBlock * 4;
+    const dim3 g(std::min<uint32_t>(blocks_for(count), kIntersectSpillGrid));
+    guide_motion_kernel<-32><<<g, dim3(kBlock), lds, s>>>(sc, pp, W, H, cb, moved, gn, gp, mn, mp, spill);
+  }
+  return hipGetLastError();
+}
+
 hipError_t read_wave_times(unsigned long long* out, size_t n) {
 #if MRT_STAMPS
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_t), std::min(n, (size_t)4 * kStampWaves * kStampFields) * sizeof(unsigned long long));

@@ -188,8 +188,9 @@ int install_camera(mrt_renderer* r, bool idle) {
   return MRT_OK;
 }
 
-// r->plan (kernel_plan.h): the kernel this renderer launches, decided once at
-// create from the scene, and what the frame buffers are sized for
+// r->plan (kernel_plan.h): the kernel this renderer launches, decided from the
+// scene (at create, and again when the scene is swapped), and what the frame
+// buffers are sized for
 int plan_kernel(mrt_renderer* r) {
   using mrt::KernelKind;
   const mrt::DeviceScene& dev = r->scene->dev;
@@ -252,8 +253,11 @@ int alloc_frame_buffers(mrt_renderer* r) {
   // slack of the segments (kernels.h)
   const size_t slots = owned_slots * r->batch + (size_t)r->plan.grid * (256 + mrt::kSegSlack);
   const bool path = r->plan.kind == mrt::KernelKind::Path, stream = r->plan.kind == mrt::KernelKind::Stream;
+  // (a buffer that already has its size is kept: a scene swap, which comes here at
+  // an unchanged frame size, neither frees nor allocates the radiance rows)
+  auto sized = [](DevBuf& b, size_t n) { return b.bytes == n && (b.p || !n) ? hipSuccess : b.alloc(n); };
   for (FrameSlot& fs : r->slots) {
-    HIP_TRY(fs.segments.alloc(((size_t)4 * r->plan.grid + 2) * 4));   // 2 queues x 2 classes x grid + 2 chunk words
+    HIP_TRY(sized(fs.segments, ((size_t)4 * r->plan.grid + 2) * 4));   // 2 queues x 2 classes x grid + 2 chunk words
     HIP_TRY(hipMemsetAsync(fs.segments.p, 0, fs.segments.bytes, r->stream));
     // the path kernel keeps the path state in LDS: no ray queues; the
     // streaming wavefront needs only its per-wave queues
@@ -265,19 +269,19 @@ int alloc_frame_buffers(mrt_renderer* r) {
     const bool partial = stream && dev.sweep_leaves && dev.sweep_cap < mrt::kSweepLeaves;
     for (int q = 0; q < 2; ++q)
       for (int p = 0; p < mrt::kQueuePlanes; ++p)
-        HIP_TRY(fs.queue[q][p].alloc(path || (stream && q == 1 && !(partial && p == 0)) ? 0 : qslots * 16));
-    HIP_TRY(fs.radiance.alloc(owned_slots * r->batch * 16));
+        HIP_TRY(sized(fs.queue[q][p], path || (stream && q == 1 && !(partial && p == 0)) ? 0 : qslots * 16));
+    HIP_TRY(sized(fs.radiance, owned_slots * r->batch * 16));
     // spill rows of max_stack words per lane (dev_lds.h LdsCtx::spill_lane)
-    if (r->plan.spills && !fs.spill.p) HIP_TRY(fs.spill.alloc((size_t)dev.max_stack * r->plan.grid * 256 * 4));
+    HIP_TRY(sized(fs.spill, r->plan.spills ? (size_t)dev.max_stack * r->plan.grid * 256 * 4 : 0));
   }
   if (!r->desc.image) {
     r->image = nullptr;
-    HIP_TRY(r->image_buf.alloc((size_t)W * H * 16));
+    HIP_TRY(sized(r->image_buf, (size_t)W * H * 16));
     r->image = r->image_buf.as<float>();
   }
   HIP_TRY(hipMemsetAsync(r->image, 0, (size_t)W * H * 16, r->stream));
   if (r->desc.flags & MRT_FLAG_MOMENTS) {
-    HIP_TRY(r->moments.alloc((size_t)W * H * 16));
+    HIP_TRY(sized(r->moments, (size_t)W * H * 16));
     HIP_TRY(hipMemsetAsync(r->moments.p, 0, (size_t)W * H * 16, r->stream));
   }
   r->image_foreign = false;
@@ -484,6 +488,38 @@ int swap_camera(mrt_renderer* r, const mrt_camera& cam) {
   }
   r->guides_current = false;   // the guide planes were traced with the previous camera
   return MRT_OK;
+}
+
+// mrt_renderer_set_scene / _move_scene: mrt_renderer_resize to the same size
+// with `scene` in the old one's place.  Behind the wait for the renderer's work
+// the kernel is planned again for the new scene (kind, stack variant and grid
+// may all change); a scene it cannot be planned for leaves the renderer as it
+// was.  Then, with `cam` (checked) as the camera unless null, everything sized by
+// the scene is re-made: frame queues, stack spill, the camera's candidate lists
+int swap_scene(mrt_renderer* r, const mrt_scene* scene, const mrt_camera* cam) {
+  HIP_TRY(hipSetDevice(r->scene->device));
+  int rc = finalize_pending(r);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  const mrt_scene* old = r->scene;
+  const mrt::KernelPlan old_plan = r->plan;
+  r->scene = scene;
+  rc = plan_kernel(r);
+  // as resize: a pending gather holds the old scene's pixels and is never unpacked
+  // into the new image; dropped only once the new scene's kernel is planned
+  if (!rc) rc = exchange_drop(r, true);
+  if (rc) {
+    r->scene = old;
+    r->plan = old_plan;
+    return rc;
+  }
+  r->desc.scene = scene;
+  if (cam) {
+    r->camera = *cam;
+    r->camera_moved = !camera_is_default(*cam);
+  }
+  rc = post_set_scene(r);   // everything derived from the image: stale
+  return rc ? rc : alloc_frame_buffers(r);
 }
 
 // Enqueue n frames of `src` (host_internal.h DrawSource): the draw loop of
@@ -726,6 +762,14 @@ int mrt_renderer_resize(mrt_renderer* r, uint32_t width, uint32_t height) {
   r->x.slab_floats = 0;    // the exchange buffers are re-sized for the new image at the next exchange
   rc = post_resize(r);     // everything derived from the image: stale, its buffers re-made at the new size
   return rc ? rc : alloc_frame_buffers(r);
+}
+
+int mrt_renderer_set_scene(mrt_renderer* r, const mrt_scene* scene) {
+  if (!r || !scene) return fail(MRT_ERR_INVALID, "mrt_renderer_set_scene: null argument");
+  if (scene->device != r->scene->device)
+    return fail(MRT_ERR_INVALID, scene->device < 0 ? "mrt_renderer_set_scene: a host-only scene has nothing on a device"
+                                                   : "mrt_renderer_set_scene: the scene is on another device than the renderer");
+  return swap_scene(r, scene, nullptr);
 }
 
 int mrt_renderer_reset(mrt_renderer* r) {

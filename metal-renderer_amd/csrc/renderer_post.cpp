@@ -258,6 +258,14 @@ int display_to(mrt_renderer* r, const float* src, uint32_t flags, float compare_
   return MRT_OK;
 }
 
+// no derived plane, history or extra image describes what the renderer holds (resize, a scene swap)
+void stale_all(mrt_renderer* r) {
+  r->guides_current = r->denoised_current = r->history_valid = r->resolved_current = false;
+  r->variance_current = r->clamped_current = r->priority_current = r->tile_error_current = false;
+  r->extras_current = r->extras_valid = false;   // re-made (and zeroed) by the next refine / draw_tiles
+  r->list_count = 0;
+}
+
 const char kNoExtras[] = "no refine or draw_tiles has run at the renderer's current size";
 
 }  // namespace
@@ -268,10 +276,7 @@ namespace host {
 // mrt_renderer_resize: no derived plane is of the new size, and each buffer
 // that exists is re-made for it (one that does not is made by its first use)
 int post_resize(mrt_renderer* r) {
-  r->guides_current = r->denoised_current = r->history_valid = r->resolved_current = false;
-  r->variance_current = r->clamped_current = r->priority_current = r->tile_error_current = false;
-  r->extras_current = r->extras_valid = false;   // re-made (and zeroed) by the next refine / draw_tiles
-  r->list_count = 0;
+  stale_all(r);
   const size_t px = image_bytes(r);
   const size_t tiles = (size_t)((r->desc.width + mrt::kTile - 1) / mrt::kTile) *   // (tiles_x / _y are still the old size's)
                        ((r->desc.height + mrt::kTile - 1) / mrt::kTile) * 4;
@@ -280,9 +285,23 @@ int post_resize(mrt_renderer* r) {
       {&r->prev_guide_n, px},   {&r->prev_guide_p, px},    {&r->temporal_prev, px},    {&r->history, px},
       {&r->resolved, px},       {&r->moments_prev, px},    {&r->moments_history, px},  {&r->moments_resolved, px},
       {&r->variance, px / 4},   {&r->clamped, px + 16},    {&r->extra, px},            {&r->extra_moments, px},
-      {&r->tile_list, tiles},   {&r->tile_priority, tiles}, {&r->tile_error, tiles},   {&r->tile_pixels, tiles}};
+      {&r->tile_list, tiles},   {&r->tile_priority, tiles}, {&r->tile_error, tiles},   {&r->tile_pixels, tiles},
+      {&r->motion_n, px},       {&r->motion_p, px}};
   for (const auto& e : all)
     if (e.b->p && e.b->bytes != e.bytes) HIP_TRY(e.b->alloc(e.bytes));
+  return MRT_OK;
+}
+
+// mrt_renderer_set_scene / _move_scene: nothing derived from the old scene's
+// image describes the new one; the buffers keep their size, but for the guide
+// pass's stack spill where its rows were of another tree's depth (ensure_guides
+// makes it again; one of the right size is kept)
+int post_set_scene(mrt_renderer* r) {
+  stale_all(r);
+  const uint32_t depth = r->scene->dev.max_stack;
+  const size_t want =   // (alloc_isect_spill's rule)
+      depth <= (uint32_t)mrt::kMaxStack ? 0 : (size_t)depth * mrt::kIntersectSpillGrid * 256 * 4;
+  if (r->guide_spill.bytes != want) HIP_TRY(r->guide_spill.alloc(0));
   return MRT_OK;
 }
 
@@ -366,6 +385,77 @@ int mrt_renderer_move_camera(mrt_renderer* r, const mrt_camera* cam, const mrt_r
   if (moments) {
     rc = mrt_reproject(r->moments_prev.as<float>(), r->prev_guide_n.as<float>(), r->prev_guide_p.as<float>(), &old,
                        r->guide_n.as<float>(), r->guide_p.as<float>(), r->moments_history.as<float>(), W, H, &p,
+                       r->stream);
+    if (rc) return rc;
+  }
+  r->history_valid = true;
+  return MRT_OK;
+}
+
+// ---- moving geometry (include/mrt.h: mrt_renderer_move_scene) ----------------
+int mrt_renderer_move_scene(mrt_renderer* r, const mrt_scene* scene, const mrt_camera* cam,
+                            const mrt_reproject_params* params) {
+  int rc = temporal_usable(r, "mrt_renderer_move_scene");
+  if (rc) return rc;
+  if (!scene) return fail(MRT_ERR_INVALID, "mrt_renderer_move_scene: null scene");
+  if (cam) {
+    rc = mrt_camera_check(cam);
+    if (rc) return rc;
+  }
+  PARAMS_OR_DEFAULT(mrt_reproject_params, p, params, mrt_reproject_params_default(&p), mrt_reproject_params_check);
+  if (scene->device != r->scene->device)
+    return fail(MRT_ERR_INVALID, scene->device < 0 ? "mrt_renderer_move_scene: a host-only scene has nothing on a device"
+                                                   : "mrt_renderer_move_scene: the scene is on another device than the renderer");
+  rc = mrt_scene_motion_compatible(r->scene, scene);
+  if (rc) return rc;
+  if (r->frame_index == 0 && !r->history_valid) return swap_scene(r, scene, cam);   // nothing to carry
+  const uint32_t W = r->desc.width, H = r->desc.height;
+  HIP_TRY(hipSetDevice(r->scene->device));
+  rc = size_group({&r->prev_guide_n, &r->prev_guide_p, &r->temporal_prev, &r->history, &r->motion_n, &r->motion_p},
+                  image_bytes(r));   // the first move only
+  if (rc) return rc;
+  const bool moments = (r->desc.flags & MRT_FLAG_MOMENTS) != 0;
+  if (moments) {
+    rc = size_group({&r->moments_prev, &r->moments_history}, image_bytes(r));
+    if (rc) return rc;
+  }
+  // as mrt_renderer_move_camera: what the old camera saw of the old scene
+  rc = ensure_guides(r);
+  if (rc) return rc;
+  rc = resolve_image_into(r, r->temporal_prev);
+  if (rc) return rc;
+  if (moments) {
+    rc = resolve_moments_into(r, r->moments_prev);
+    if (rc) return rc;
+  }
+  // the swap, behind the call's one host wait: failing before it leaves the
+  // renderer as it was; from it on a failure leaves the new scene in force
+  // without a history, as mrt_renderer_set_scene would
+  const mrt_scene* old_scene = r->scene;
+  const mrt_camera old = r->camera;
+  const bool had_extras = r->extras_current;
+  rc = swap_scene(r, scene, cam);
+  if (rc) return rc;
+  if (had_extras) {   // E and EM stay readable, cleared as mrt_renderer_reset clears them
+    HIP_TRY(hipMemsetAsync(r->extra.p, 0, image_bytes(r), r->stream));
+    HIP_TRY(hipMemsetAsync(r->extra_moments.p, 0, image_bytes(r), r->stream));
+    r->extras_current = true;
+  }
+  std::swap(r->guide_n.p, r->prev_guide_n.p);   // equal sizes: the old scene's planes become the previous ones
+  std::swap(r->guide_p.p, r->prev_guide_p.p);
+  // the new scene's guide planes and, for each pixel's surface point, where it was in the old scene
+  if (!r->guide_spill.p) HIP_TRY(alloc_isect_spill(r->guide_spill, r->scene->dev.max_stack));
+  rc = guides_motion_with_spill(r->scene, old_scene, &r->camera, W, H, r->guide_n.as<float>(), r->guide_p.as<float>(),
+                                r->motion_n.as<float>(), r->motion_p.as<float>(), r->desc.flags & MRT_FLAG_PRECISE,
+                                r->guide_spill.as<uint32_t>(), r->stream);
+  if (rc) return rc;
+  r->guides_current = true;
+  rc = mrt_reproject(r->temporal_prev.as<float>(), r->prev_guide_n.as<float>(), r->prev_guide_p.as<float>(), &old,
+                     r->motion_n.as<float>(), r->motion_p.as<float>(), r->history.as<float>(), W, H, &p, r->stream);
+  if (rc) return rc;
+  if (moments) {
+    rc = mrt_reproject(r->moments_prev.as<float>(), r->prev_guide_n.as<float>(), r->prev_guide_p.as<float>(), &old,
+                       r->motion_n.as<float>(), r->motion_p.as<float>(), r->moments_history.as<float>(), W, H, &p,
                        r->stream);
     if (rc) return rc;
   }

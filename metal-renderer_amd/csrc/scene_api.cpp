@@ -588,6 +588,10 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
     return fail(MRT_ERR_IO, err);
   if (desc->procedural_triangles) mrt::append_procedural_mesh(s->host, desc->procedural_triangles, desc->procedural_seed);
   mrt::flatten(s->host);
+  s->motion_digest = 14695981039346656037ull;
+  for (const mrt::RefTriangleReference& t : s->host.references)
+    for (const uint32_t w : {t.materialIndex, t.lightTriangleIndex == 0xFFFFFFFFu ? 0u : 1u})
+      for (int k = 0; k < 4; ++k) s->motion_digest = (s->motion_digest ^ ((w >> (8 * k)) & 0xFFu)) * 1099511628211ull;
   SceneBuild b;
   b.desc = desc;
   b.s = s.get();
@@ -609,6 +613,35 @@ int mrt_scene_create(const mrt_scene_desc* desc, mrt_scene** out) {
 int mrt_scene_info_get(const mrt_scene* scene, mrt_scene_info* info) {
   if (!scene || !info) return fail(MRT_ERR_INVALID, "null argument");
   *info = scene->info;
+  return MRT_OK;
+}
+
+// host only.  O(1) for a compatible pair: equal counts and equal digests of what
+// is compared (mrt_scene::motion_digest; two different sequences of a million
+// words agree in 64 bits with probability 2^-64, and the kernels' reads stay
+// inside both scenes' buffers whatever the words, since the counts are compared
+// exactly).  Only a pair that differs is walked, to name the first difference
+int mrt_scene_motion_compatible(const mrt_scene* a, const mrt_scene* b) {
+  if (!a || !b) return fail(MRT_ERR_INVALID, "mrt_scene_motion_compatible: null argument");
+  const auto& ra = a->host.references;
+  const auto& rb = b->host.references;
+  if (a == b || (ra.size() == rb.size() && a->host.materials.size() == b->host.materials.size() &&
+                 a->motion_digest == b->motion_digest))
+    return MRT_OK;
+  if (ra.size() != rb.size())
+    return fail(MRT_ERR_INVALID, "motion: the scenes have " + std::to_string(ra.size()) + " and " +
+                                     std::to_string(rb.size()) + " triangles");
+  if (a->host.materials.size() != b->host.materials.size())
+    return fail(MRT_ERR_INVALID, "motion: the scenes have " + std::to_string(a->host.materials.size()) + " and " +
+                                     std::to_string(b->host.materials.size()) + " materials");
+  for (size_t k = 0; k < ra.size(); ++k) {
+    if (ra[k].materialIndex != rb[k].materialIndex)
+      return fail(MRT_ERR_INVALID, "motion: primitive " + std::to_string(k) + " has material " +
+                                       std::to_string(ra[k].materialIndex) + " in one scene and " +
+                                       std::to_string(rb[k].materialIndex) + " in the other");
+    if ((ra[k].lightTriangleIndex == 0xFFFFFFFFu) != (rb[k].lightTriangleIndex == 0xFFFFFFFFu))
+      return fail(MRT_ERR_INVALID, "motion: primitive " + std::to_string(k) + " is a light triangle in one scene only");
+  }
   return MRT_OK;
 }
 

@@ -160,12 +160,9 @@ bool camera_is_default(const mrt_camera& c) {
   return std::memcmp(&c, &d, sizeof(mrt_camera)) == 0;
 }
 
-// mrt_guides with the caller's stack spill (a renderer's own, so that its guide
-// pass shares nothing with the stage calls on the scene or another renderer)
-int guides_with_spill(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, float* guide_n,
-                      float* guide_p, uint32_t flags, uint32_t* spill, void* stream) {
-  if (!scene || !guide_n || !guide_p || guide_n == guide_p || W < 2 || H < 2 || W > 32768 || H > 32768)
-    return fail(MRT_ERR_INVALID, "mrt_guides: bad argument");
+// the camera block of a guide pass: `cam` (NULL = the default) checked, its lens
+// removed; *moved: not the reference's camera, so the kernel reads the block
+static int guide_camera(const mrt_camera* cam, mrt::CameraBlock* cb, bool* moved) {
   mrt_camera c;
   if (cam) {
     const int rc = mrt_camera_check(cam);
@@ -179,10 +176,49 @@ int guides_with_spill(const mrt_scene* scene, const mrt_camera* cam, uint32_t W,
   mrt_camera d;
   (void)mrt_camera_default(&d);
   d.focus_distance = 0.0f;
-  const bool moved = std::memcmp(&c, &d, sizeof(mrt_camera)) != 0;
-  const mrt::CameraBlock cb = camera_block(c);
+  *moved = std::memcmp(&c, &d, sizeof(mrt_camera)) != 0;
+  *cb = camera_block(c);
+  return MRT_OK;
+}
+
+// mrt_guides with the caller's stack spill (a renderer's own, so that its guide
+// pass shares nothing with the stage calls on the scene or another renderer)
+int guides_with_spill(const mrt_scene* scene, const mrt_camera* cam, uint32_t W, uint32_t H, float* guide_n,
+                      float* guide_p, uint32_t flags, uint32_t* spill, void* stream) {
+  if (!scene || !guide_n || !guide_p || guide_n == guide_p || W < 2 || H < 2 || W > 32768 || H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_guides: bad argument");
+  mrt::CameraBlock cb;
+  bool moved = false;
+  const int rc = guide_camera(cam, &cb, &moved);
+  if (rc) return rc;
   HIP_TRY(MRT_BUILD_CALL(flags, launch_guides(scene->dev, W, H, moved ? &cb : nullptr, guide_n, guide_p, spill,
                                               (hipStream_t)stream)));
+  return MRT_OK;
+}
+
+// mrt_guides_motion, likewise with the caller's stack spill
+int guides_motion_with_spill(const mrt_scene* scene, const mrt_scene* prev_scene, const mrt_camera* cam, uint32_t W,
+                             uint32_t H, float* guide_n, float* guide_p, float* motion_n, float* motion_p,
+                             uint32_t flags, uint32_t* spill, void* stream) {
+  if (!scene || !prev_scene || !guide_n || !guide_p || !motion_n || !motion_p || W < 2 || H < 2 || W > 32768 ||
+      H > 32768)
+    return fail(MRT_ERR_INVALID, "mrt_guides_motion: bad argument");
+  const size_t bytes = (size_t)W * H * 16;
+  if (written_overlap({{guide_n, bytes, true}, {guide_p, bytes, true}, {motion_n, bytes, true}, {motion_p, bytes, true}}))
+    return fail(MRT_ERR_INVALID, "mrt_guides_motion: the four planes must not overlap");
+  if (scene->device < 0 || prev_scene->device < 0)
+    return fail(MRT_ERR_INVALID, "mrt_guides_motion: a host-only scene has nothing on a device");
+  if (scene->device != prev_scene->device)
+    return fail(MRT_ERR_INVALID, "mrt_guides_motion: the two scenes are on different devices");
+  int rc = mrt_scene_motion_compatible(prev_scene, scene);
+  if (rc) return rc;
+  mrt::CameraBlock cb;
+  bool moved = false;
+  rc = guide_camera(cam, &cb, &moved);
+  if (rc) return rc;
+  HIP_TRY(MRT_BUILD_CALL(flags, launch_guides_motion(scene->dev, prev_scene->dev.prims, W, H, moved ? &cb : nullptr,
+                                                     guide_n, guide_p, motion_n, motion_p, spill,
+                                                     (hipStream_t)stream)));
   return MRT_OK;
 }
 
@@ -437,6 +473,13 @@ int mrt_debug_denoise_path(uint32_t path) {
   if (path > mrt::kAtrousStaged) return fail(MRT_ERR_INVALID, "mrt_debug_denoise_path: 0, 1 or 2");
   g_denoise_path.store(path);
   return MRT_OK;
+}
+
+int mrt_guides_motion(const mrt_scene* scene, const mrt_scene* prev_scene, const mrt_camera* cam, uint32_t W,
+                      uint32_t H, float* guide_n, float* guide_p, float* motion_n, float* motion_p, uint32_t flags,
+                      void* stream) {
+  return guides_motion_with_spill(scene, prev_scene, cam, W, H, guide_n, guide_p, motion_n, motion_p, flags,
+                                  scene ? scene->isect_spill.as<uint32_t>() : nullptr, stream);
 }
 
 int mrt_denoise(const float* image, const float* guide_n, const float* guide_p, float* out, float* scratch,

@@ -415,6 +415,10 @@ _ABI = {
     "mrt_renderer_set_firefly": [_vp, _P(FireflyParams)],
     "mrt_renderer_get_firefly": [_vp, _P(FireflyParams), _P(_u32)],
     "mrt_renderer_read_clamped": [_vp, _vp, _size, _P(_u32)],
+    "mrt_scene_motion_compatible": [_vp, _vp],
+    "mrt_guides_motion": [_vp, _vp, _P(Camera), _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp],
+    "mrt_renderer_set_scene": [_vp, _vp],
+    "mrt_renderer_move_scene": [_vp, _vp, _P(Camera), _P(ReprojectParams)],
 }
 EXPORTED = list(_ABI)
 
@@ -602,11 +606,22 @@ class Renderer(_Handle):
                          stream, image_ptr)
         self._h = _get(_vp, "mrt_renderer_create", ctypes.byref(d))
         self.width, self.height = width, height
+        self._prev_scene = None   # the scene a move_scene left, until the renderer has synchronised
+        self._pinned = []         # scenes of move_scene calls that failed on the device (move_scene)
 
     # -mtkView:drawableSizeWillChange:
     def resize(self, width: int, height: int) -> None:
         _call("mrt_renderer_resize", self._h, width, height)
         self.width, self.height = width, height
+        self._prev_scene = None
+
+    def set_scene(self, scene: Scene) -> None:
+        """resize() to the same size with another scene: waits for the queued
+        work, plans the kernel again, restarts at frame 0; camera, flags and
+        noise schedules persist (mrt_renderer_set_scene)."""
+        _call("mrt_renderer_set_scene", self._h, scene.handle)
+        self.scene = scene
+        self._prev_scene = None
 
     def reset(self) -> None:
         _call("mrt_renderer_reset", self._h)
@@ -639,6 +654,7 @@ class Renderer(_Handle):
 
     def sync(self) -> None:
         _call("mrt_renderer_sync", self._h)
+        self._prev_scene = None
 
     def image_ptr(self) -> int:
         return _get(_vp, "mrt_renderer_image", self._h).value
@@ -653,6 +669,7 @@ class Renderer(_Handle):
         import numpy as np
         a = np.zeros((self.height, self.width, 4) if shape is None else shape, dtype)
         _call(what, self._h, _ptr(a), a.size, *more)
+        self._prev_scene = None   # (every reader synchronises)
         return a
 
     def read_image(self):
@@ -683,6 +700,23 @@ class Renderer(_Handle):
         view, as a counted history beside the image (no host wait); params
         None = ReprojectParams.default()."""
         _call("mrt_renderer_move_camera", self._h, ctypes.byref(camera), _opt(params))
+
+    def move_scene(self, scene: Scene, camera: "Camera | None" = None,
+                   params: "ReprojectParams | None" = None) -> None:
+        """move_camera() across a scene change: `scene` is another pose of the
+        scene in force (scene_motion_compatible); camera None keeps the camera.
+        The scene it replaces is kept alive here until the next sync or read
+        (mrt_renderer_move_scene)."""
+        try:
+            _call("mrt_renderer_move_scene", self._h, scene.handle, _opt(camera), _opt(params))
+        except MrtError as e:
+            # A failed check (INVALID, STATE) changed nothing.  A device error may have struck before or behind
+            # the swap, and the library has no call that tells which scene is in force: both stay alive with the
+            # renderer, and self.scene goes on naming the one it was created or last moved with
+            if e.status not in (-1, -5):   # MRT_ERR_INVALID, MRT_ERR_STATE
+                self._pinned.append(scene)
+            raise
+        self._prev_scene, self.scene = self.scene, scene
 
     def resolve(self) -> None:
         """Merge the image with the history into the renderer's resolved
@@ -986,6 +1020,21 @@ def guides(scene: Scene, width: int, height: int, n_ptr: int, p_ptr: int, camera
     and (position, t), W*H float4 each on the device."""
     _launch("mrt_guides", scene.handle, _opt(camera), width, height, n_ptr, p_ptr, _flags(precise),
             stream=stream, sync=sync)
+
+
+def scene_motion_compatible(a: Scene, b: Scene) -> None:
+    """Raises MrtError (status -1, naming the first difference) unless the two
+    scenes are poses of one mesh (mrt_scene_motion_compatible; host only)."""
+    _call("mrt_scene_motion_compatible", a.handle, b.handle)
+
+
+def guides_motion(scene: Scene, prev_scene: Scene, width: int, height: int, n_ptr: int, p_ptr: int, motion_n_ptr: int,
+                  motion_p_ptr: int, camera: Camera | None = None, precise=True, stream=None, sync=True):
+    """guides() of `scene` and the motion planes: each pixel's surface point as
+    it lies in prev_scene (mrt_guides_motion).  With sync=False both scenes must
+    outlive the stream's work."""
+    _launch("mrt_guides_motion", scene.handle, prev_scene.handle, _opt(camera), width, height, n_ptr, p_ptr,
+            motion_n_ptr, motion_p_ptr, _flags(precise), stream=stream, sync=sync)
 
 
 def denoise(image_ptr: int, n_ptr: int, p_ptr: int, out_ptr: int, scratch_ptr: int, width: int, height: int,
