@@ -79,6 +79,13 @@
 #define MRT_LDS_BLOCKS MRT_BOUNCE_WAVES
 #endif
 
+// Diagnostic: 1 gives the all-in-LDS kernels the per-solid loop of the convex
+// shadow query as well (dev_shadow.h convex_occlusion_loop), so that a lane-
+// statistics variant can count its face passes next to the plan's
+#ifndef MRT_CONVEX_LOOP
+#define MRT_CONVEX_LOOP 0
+#endif
+
 namespace mrt { namespace MRT_NS { namespace {
 
 constexpr int kBlock = 256;   // 4 waves of 64 lanes

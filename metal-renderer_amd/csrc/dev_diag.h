@@ -35,10 +35,15 @@ namespace mrt { namespace MRT_NS { namespace {
 //         (per record), and a back-to-back pair of clock reads (the cost of
 //         the measurement itself, to be subtracted per event)
 //   46-47 unused, read zero (the third sweep key's rounds; DESIGN "Retired A/B switches")
+//   48-51 convex shadow query, split by the wave's class (LS_SPLIT:
+//         0 = camera rays, 1 = a queue level): first-face passes (the plan's one
+//         pass; the per-solid loop's entry-face pass of each solid) and wave
+//         calls of the query, for the camera waves (48, 49) and the levels (50, 51)
 // ---------------------------------------------------------------------------
 #if MRT_LANESTATS
-constexpr int kLaneStats = 48;
+constexpr int kLaneStats = 52;
 __shared__ unsigned long long s_lanes[kBlock / 64][kLaneStats];
+__shared__ uint32_t s_lane_split[kBlock / 64];   // the wave's class for the split slots
 __device__ unsigned long long g_lanes[kLaneStats];
 __device__ __forceinline__ void ls_add(int k, uint32_t v) {
   const uint64_t m = __ballot(1);
@@ -46,7 +51,15 @@ __device__ __forceinline__ void ls_add(int k, uint32_t v) {
 }
 __device__ __forceinline__ uint32_t ls_lanes() { return (uint32_t)__popcll(__ballot(1)); }
 #define LS_ADD(k, v) ls_add((k), (v))
-#define LS_INIT() do { if ((threadIdx.x & 63u) < (uint32_t)kLaneStats) s_lanes[threadIdx.x >> 6][threadIdx.x & 63u] = 0; } while (0)
+// the wave's class from here on (wave-uniform), and a count into slot k + 2 * class
+__device__ __forceinline__ void ls_split(uint32_t cls) {
+  const uint64_t m = __ballot(1);
+  if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)m) - 1)) s_lane_split[threadIdx.x >> 6] = cls;
+}
+#define LS_SPLIT(cls) ls_split((cls))
+#define LS_ADD_SPLIT(k, v) ls_add((k) + 2 * (int)s_lane_split[threadIdx.x >> 6], (v))
+#define LS_INIT() do { if ((threadIdx.x & 63u) < (uint32_t)kLaneStats) s_lanes[threadIdx.x >> 6][threadIdx.x & 63u] = 0; \
+    if ((threadIdx.x & 63u) == 0u) s_lane_split[threadIdx.x >> 6] = 0; } while (0)
 #define LS_FLUSH() do { const uint32_t l_ = threadIdx.x & 63u; \
     if (l_ < (uint32_t)kLaneStats && s_lanes[threadIdx.x >> 6][l_]) atomicAdd(&g_lanes[l_], s_lanes[threadIdx.x >> 6][l_]); } while (0)
 // the shader clock, read and waited for (the wait is for the scalar and LDS
@@ -65,6 +78,8 @@ __device__ __forceinline__ uint64_t ls_clock() {
 #define LS_WAIT_VM(k) do { LS_T0(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); LS_T1(k); } while (0)
 #else
 #define LS_ADD(k, v) do {} while (0)
+#define LS_SPLIT(cls) do {} while (0)
+#define LS_ADD_SPLIT(k, v) do {} while (0)
 #define LS_INIT() do {} while (0)
 #define LS_FLUSH() do {} while (0)
 #define LS_T0() do {} while (0)

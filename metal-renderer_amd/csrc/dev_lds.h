@@ -13,7 +13,7 @@ namespace mrt { namespace MRT_NS { namespace {
 //   kAllLds  — small scenes: every node, leaf triangle, per-primitive shading
 //              record, material and light entry is staged in LDS once per
 //              block, so traversal and shading never leave the CU.
-// LDS image: [nodes][triangles][prims][materials][lights][sweep list] as float4, then the
+// LDS image: [nodes][triangles][prims][materials][lights][sweep list][convex face pairs] as float4, then the
 // uint32 scratch (segment prefix), then the stack laid out [entry][lane]
 // (consecutive lanes hit consecutive banks).  All LDS accesses index the
 // __shared__ symbol directly so they lower to ds_read/ds_write (a pointer
@@ -28,6 +28,7 @@ struct LdsCtx {
   uint32_t mat_base;
   uint32_t light_base;
   uint32_t sweep_base;    // the sweep list's records (kAllLds, sc.sweep_leaves of them)
+  uint32_t conv_base;     // uint32 offset of the convex solids' face pairs (kAllLds, conv_table_float4s)
   uint32_t scratch_base;  // uint32 offset of the per-block scratch
   uint32_t stack_base;    // uint32 offset of the block's stack slot 0 (lane 0's); lanes add threadIdx.x
   uint32_t* spill;        // stack entries >= STACK: the block's rows of a global [lane][word] spill
@@ -55,13 +56,18 @@ __host__ __device__ inline uint32_t lds_scene_float4s(int mode, uint32_t node_f4
   if (mode == kTopLds) return node_f4 * lds_nodes;
   return 0;
 }
+// the convex solids' face pairs as a table a lane indexes by (solid, face)
+// (shadow_plan.h shadow_plan_pair_index: 8 words per solid, faces 6 and 7 hold
+// "no triangles"): DeviceScene::conv_face_tris lives in the kernel arguments,
+// where only wave-uniform indices are cheap
+__host__ __device__ inline uint32_t conv_table_float4s(const DeviceScene& sc) { return 2u * sc.conv_count; }
 // both trees' nodes and leaf-triangle records (mrt_layout.h DeviceScene)
 __host__ __device__ inline uint32_t scene_nodes(const DeviceScene& sc) { return sc.num_nodes + sc.occ_nodes; }
 __host__ __device__ inline uint32_t scene_tri_records(const DeviceScene& sc) { return sc.num_triangles + sc.occ_tris; }
 __host__ __device__ inline uint32_t lds_scene_float4s(int mode, const DeviceScene& sc) {
   return lds_scene_float4s(mode, node_float4s(sc.width), scene_nodes(sc), sc.lds_nodes, scene_tri_records(sc),
                            sc.num_triangles, sc.num_materials, sc.num_lights + 1) +
-         (mode == kAllLds ? 2 * sc.sweep_leaves : 0u);   // the sweep list's records (sweep_nearest)
+         (mode == kAllLds ? 2 * sc.sweep_leaves + conv_table_float4s(sc) : 0u);   // the sweep list's records (sweep_nearest), the face pairs
 }
 
 // 16-B buffer load at a 32-bit byte offset from a wave-uniform descriptor
@@ -184,7 +190,9 @@ __device__ __forceinline__ LdsCtx stage_lds(const DeviceScene& sc, uint32_t scra
   cx.mat_base = cx.prim_base + 6 * T;
   cx.light_base = cx.mat_base + 2 * M;
   cx.sweep_base = cx.light_base + 7 * NL;
-  const uint32_t f4 = cx.sweep_base + 2 * SW;
+  const uint32_t CV = (MODE == kAllLds) ? conv_table_float4s(sc) : 0u;
+  cx.conv_base = 4 * (cx.sweep_base + 2 * SW);
+  const uint32_t f4 = cx.sweep_base + 2 * SW + CV;
   cx.scratch_base = 4 * f4;
   cx.stack_base = cx.scratch_base + ((scratch_u32 + 3) & ~3u);
   cx.spill_lane = sc.max_stack;
@@ -197,6 +205,10 @@ __device__ __forceinline__ LdsCtx stage_lds(const DeviceScene& sc, uint32_t scra
     const uint32_t len[6] = {nf4 * n_nodes, 3 * TR, 6 * T, 2 * M, 7 * NL, 2 * SW};
     for (int r = copies ? 1 : 0; r < 6; ++r)
       for (uint32_t i = threadIdx.x; i < len[r]; i += kBlock) g_lds[base[r] + i] = src[r][i];
+    // the face pairs, a word per (solid, face); a per-lane index into the
+    // kernel arguments is a vector load from their segment, once per block
+    for (uint32_t i = threadIdx.x; i < 4 * CV; i += kBlock)
+      lds_u32()[cx.conv_base + i] = (i & 7u) < 6u ? sc.conv_face_tris[i >> 3][i & 7u] : 0xFFFFFFFFu;
     if (copies) {   // quadrant copies: x, y rows (near, far), z rows (lo, hi), refs
       for (uint32_t i = threadIdx.x; i < node_f4 * n_nodes; i += kBlock) {
         const uint32_t node = i / node_f4, rem = i % node_f4;

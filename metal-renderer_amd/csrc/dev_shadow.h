@@ -1,6 +1,7 @@
 // dev_shadow.h — shadow queries: tree choice, light / convex-solid / own-surface shortcuts, the last bounce's light hit
 #pragma once
 #include "dev_traverse.h"
+#include "shadow_plan.h"
 
 namespace mrt { namespace MRT_NS { namespace {
 
@@ -119,9 +120,12 @@ __device__ __forceinline__ bool face_occludes(const DeviceScene& sc, const LdsCt
 //     solid's other faces — the leaf test over every triangle of the solid,
 //     which is what the walk would have tested.
 // Returns whether a solid occludes; the occluder tree is not walked.
+// This form decides solid by solid, faces and all, inside the loop: the
+// kernels that read the scene from global memory keep it (the path kernel's
+// code is as it was); the all-in-LDS kernels take convex_occlusion below.
 template <int MODE>
-__device__ __forceinline__ bool convex_occlusion(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, uint32_t target,
-                                                 float tT, uint32_t origin) {
+__device__ __forceinline__ bool convex_occlusion_loop(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d,
+                                                      uint32_t target, float tT, uint32_t origin) {
   const uint32_t own = fbits(fetch_prim<MODE>(sc, cx, origin, 2).w);   // c * 8 + face + 1 of the origin's solid
   const V3 own_n = mk(fetch_prim<MODE>(sc, cx, origin, 3).w, fetch_prim<MODE>(sc, cx, origin, 4).w,
                       fetch_prim<MODE>(sc, cx, origin, 5).w);   // its face's outward unit normal (0 off the solids)
@@ -151,6 +155,7 @@ __device__ __forceinline__ bool convex_occlusion(const DeviceScene& sc, const Ld
     }
     const bool leaves_own = own_skip == c;
     if ((t0 <= t1) & !leaves_own & !occluded) {
+      LS_ADD_SPLIT(48, 1);
       uint32_t pin = 0xFFFFFFFFu, pout = 0xFFFFFFFFu;
 #pragma unroll
       for (uint32_t k = 0; k < 6; ++k) {
@@ -173,6 +178,84 @@ __device__ __forceinline__ bool convex_occlusion(const DeviceScene& sc, const Ld
   return occluded;
 }
 
+// Solid c's three padded slabs against the segment [o, o + tT d], the
+// arithmetic of convex_occlusion_loop word for word: whether an interval is
+// left, and the entry / exit face (2a + side; 8 = none).
+__device__ __forceinline__ bool convex_slabs(const DeviceScene& sc, uint32_t c, V3 o, V3 d, float tT, uint32_t& fin,
+                                             uint32_t& fout) {
+  const float* B = sc.conv_obb[c];
+  float t0 = 0.0f, t1 = tT;
+  fin = 8u;
+  fout = 8u;
+#pragma unroll
+  for (uint32_t a = 0; a < 3; ++a) {
+    const float nd = (B[3 * a] * d.x + B[3 * a + 1] * d.y) + B[3 * a + 2] * d.z;
+    const float no = (B[3 * a] * o.x + B[3 * a + 1] * o.y) + B[3 * a + 2] * o.z;
+    const float inv = m_rcp(nd);
+    const float tlo = (B[9 + 2 * a] - no) * inv, thi = (B[10 + 2 * a] - no) * inv;
+    const bool pos = (fbits(nd) >> 31) == 0u;
+    const float tn = pos ? tlo : thi, tf = pos ? thi : tlo;
+    const bool in_ = tn > t0, out_ = tf < t1;
+    t0 = in_ ? tn : t0;
+    fin = in_ ? (pos ? 2u * a : 2u * a + 1u) : fin;
+    t1 = out_ ? tf : t1;
+    fout = out_ ? (pos ? 2u * a + 1u : 2u * a) : fout;
+  }
+  return t0 <= t1;
+}
+
+// The same decisions in another order (shadow_plan.h; kAllLds
+// only: the face pairs are read from the LDS image by a per-lane index).
+// Occlusion is an OR over solids and triangles, so a face test need not wait
+// for its solid's turn: the loop over the solids keeps the slab tests and
+// files what each lane crosses into its plan; then every lane tests the entry
+// face of the FIRST solid it crosses, the whole wave in one pass — where the
+// loop form made a divergent pass per solid, each with the few lanes that
+// cross that one; and only if a lane is left neither occluded nor done (a
+// ballot) does the rest run: per crossed solid the faces not yet tested, in the
+// loop form's order.  Per (ray, solid) the same slabs, the same own-face
+// skip and the leaf test over the same triangles until one hits: the answer
+// is the loop form's.
+template <int MODE>
+__device__ __forceinline__ bool convex_occlusion(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, uint32_t target,
+                                                 float tT, uint32_t origin) {
+  const uint32_t own = fbits(fetch_prim<MODE>(sc, cx, origin, 2).w);   // c * 8 + face + 1 of the origin's solid
+  const V3 own_n = mk(fetch_prim<MODE>(sc, cx, origin, 3).w, fetch_prim<MODE>(sc, cx, origin, 4).w,
+                      fetch_prim<MODE>(sc, cx, origin, 5).w);   // its face's outward unit normal (0 off the solids)
+  const uint32_t own_skip = ((own != 0u) & (dot(d, own_n) >= kConvexLeaveDot)) ? (own - 1u) >> 3 : 0xFFFFFFFFu;
+  uint32_t plan = 0u;
+  for (uint32_t c = 0; c < sc.conv_count; ++c) {   // wave-uniform; the three slabs unrolled (scalar operands)
+    uint32_t fin, fout;
+    const bool crosses = convex_slabs(sc, c, o, d, tT, fin, fout);
+    plan = shadow_plan_add(plan, c, crosses & (own_skip != c), fin, fout);
+  }
+  bool occluded = false;
+  if (shadow_plan_has(plan)) {   // the one face pass
+    LS_ADD_SPLIT(48, 1);
+    const uint32_t at = shadow_plan_pair_index(shadow_plan_solid(plan), shadow_plan_first_face(plan));
+    occluded = face_occludes<MODE>(sc, cx, o, d, lds_u32()[cx.conv_base + at], target, tT);
+  }
+  const bool more = shadow_plan_has(plan) & !occluded;
+  if (__ballot(more)) {   // the rare rest: a near miss within delta, an entry near an edge, a second solid
+    const uint32_t crossed = more ? shadow_plan_crossed(plan) : 0u;
+    for (uint32_t c = 0; c < sc.conv_count; ++c) {
+      if (((crossed >> c) & 1u) & !occluded) {
+        uint32_t fin, fout;
+        convex_slabs(sc, c, o, d, tT, fin, fout);
+        uint32_t todo = shadow_plan_todo(plan, c);
+        bool hit = false;
+        while ((todo != 0u) & !hit) {
+          const uint32_t k = shadow_plan_next_face(fin, fout, todo);
+          todo &= ~(1u << k);
+          hit = face_occludes<MODE>(sc, cx, o, d, lds_u32()[cx.conv_base + shadow_plan_pair_index(c, k)], target, tT);
+        }
+        occluded |= hit;
+      }
+    }
+  }
+  return occluded;
+}
+
 template <int STACK, int MODE>
 __device__ __forceinline__ bool trace_occluded(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, uint32_t target,
                                                uint32_t tl, float t_target, bool graze, uint32_t origin,
@@ -188,7 +271,10 @@ __device__ __forceinline__ bool trace_occluded(const DeviceScene& sc, const LdsC
 #endif
   const bool via_occ = root == sc.occ_root;
   if (sc.conv_count && via_occ) {
-    if (!(dbg & 512u) && convex_occlusion<MODE>(sc, cx, o, d, target, t_target, origin)) return true;
+    LS_ADD_SPLIT(49, 1);
+    if (!(dbg & 512u) && (MODE == kAllLds && !MRT_CONVEX_LOOP ? convex_occlusion<MODE>(sc, cx, o, d, target, t_target, origin)
+                                          : convex_occlusion_loop<MODE>(sc, cx, o, d, target, t_target, origin)))
+      return true;
     root = kDone;   // no walk (the light triangles are still tested below)
   }
   if (sc.occ_lights && via_occ && !(dbg & 1024u) && lights_occlude<MODE>(sc, cx, o, d, target, tl, t_target)) return true;

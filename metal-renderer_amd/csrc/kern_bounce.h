@@ -292,6 +292,7 @@ __device__ __forceinline__ uint32_t bounce_wave(const DeviceScene& sc, const Lds
   if (__ballot(sh.valid)) {
     LS_ADD(16, (uint32_t)__popcll(__ballot(sh.valid)));
     LS_ADD(17, 1);
+    LS_SPLIT(bounce == 0u ? 0u : 1u);
   }
   if (sh.valid && ((a.debug & 1u) || shadow_reaches_target<STACK, MODE>(sc, cx, sh.o, sh.d, sh.target, h.prim, sh.graze, a.debug))) {
     s.R = add(s.R, sh.L);

@@ -32,7 +32,9 @@ NAMES = ["near_lanes", "near_calls", "near_int_iters", "near_int_lanes", "near_l
          "root_wait_cycles", "root_waits", "sweep_rec_wait_cycles", "sweep_rec_waits",
          "clock_pair_cycles", "clock_pairs",
          # slots 46-47 read zero: the sweep's third key is no longer built; the slots keep their numbers
-         "sweep_key3_rounds", "sweep_key3_lanes"]
+         "sweep_key3_rounds", "sweep_key3_lanes",
+         # the convex shadow query: first-face passes and wave calls, camera waves then queue levels
+         "convex_passes_camera", "convex_calls_camera", "convex_passes_levels", "convex_calls_levels"]
 # (cycles slot, events slot, output name) of the timed waits
 WAITS = [("q01_wait_cycles", "q01_waits", "q01"), ("q23_wait_cycles", "q23_waits", "q23"),
          ("list_wait_cycles", "list_waits", "list"), ("root_wait_cycles", "root_waits", "root"),
@@ -94,6 +96,10 @@ def main():
         out["shade_util"] = util(c["shade_lanes"], c["shade_calls"])
         out["shadow_phase_util"] = util(c["shadow_rays"], c["shadow_calls"])
         out["list_util"] = util(c["list_lanes"], c["list_calls"])
+        # against tools/convex_branch_stats.py's "entry-face passes" columns (now / merged)
+        for cls in ("camera", "levels"):
+            if c.get(f"convex_calls_{cls}"):
+                out[f"convex_passes_per_call_{cls}"] = round(c[f"convex_passes_{cls}"] / c[f"convex_calls_{cls}"], 3)
         if c.get("stream_queue_waits"):
             # shader-clock cycles (s_memtime) a wave spends in the queue
             # iteration's wait for its own stores, per level iteration
