@@ -273,6 +273,12 @@ __device__ __forceinline__ void slot_pixel_l(uint32_t s, const BounceArgs& a, ui
   }
 }
 
+// The launch's dynamic work distribution (kernels.h): the length of one of the
+// kGrabRanges ranges of a launch's N indices, a whole number of grabs
+__device__ __forceinline__ uint32_t grab_range_len(uint32_t N) {
+  return ((N + kGrabRanges - 1) / kGrabRanges + kGrab - 1) / kGrab * kGrab;
+}
+
 // noise table of frame (batch frame fj) - back, back in {0, 1, 2}
 __device__ __forceinline__ const float4* noise_table(const BounceArgs& a, uint32_t fj, uint32_t back) {
   return a.noise_window + (a.noise_offset + fj - back) * (kNoiseDim * kNoiseDim);

@@ -27,7 +27,8 @@ __device__ __forceinline__ int32_t shadow_root(const DeviceScene& sc, V3 o, bool
 }
 // The same with the per-lane select of the two kernel arguments: the path
 // kernel's, whose register allocation is left as it is (its queries have no
-// stores in flight before them).
+// stores in flight before them).  (The plane loop stands in both: one function
+// for it changes the kernels' code)
 __device__ __forceinline__ int32_t shadow_root_select(const DeviceScene& sc, V3 o, bool graze) {
   if (sc.occ_planes == 0 || graze) return sc.root;
   bool inside = true;
@@ -38,13 +39,27 @@ __device__ __forceinline__ int32_t shadow_root_select(const DeviceScene& sc, V3 
   return inside ? sc.occ_root : sc.root;
 }
 
+// Light record k as the leaf test's triangle: the record's vertices are its
+// primitive's, in its order (scene flattening, Renderer.mm:394-413) — three
+// independent loads, and v2 - v1, v3 - v1 are the leaf record's e1, e2 bit
+// for bit.  prim = lights[k].index.
+struct LightTri {
+  uint32_t prim;
+  V3 p0, e1, e2;
+};
+template <int MODE>
+__device__ __forceinline__ LightTri light_triangle(const DeviceScene& sc, const LdsCtx& cx, uint32_t k) {
+  const float4 LB = fetch_light<MODE>(sc, cx, k, 1), LD = fetch_light<MODE>(sc, cx, k, 3);
+  const float4 LF = fetch_light<MODE>(sc, cx, k, 5);
+  const V3 p0 = mk(LB);
+  return LightTri{fbits(LD.w), p0, sub(mk(LD), p0), sub(mk(LF), p0)};
+}
+
 // The light triangles of an occluder tree built without them (DeviceScene::
 // occ_lights): every shadow ray enters the light's own leaf box, so instead
 // of a leaf visit per ray the other light triangles are tested here in one
-// wave-uniform loop — the leaf test's arithmetic (a light record's vertices
-// are its primitive's, in its order: v2 - v1, v3 - v1 are the leaf record's
-// e1, e2 bit for bit, as in last_bounce_light_hit) and the occlusion rule
-// (k != target, (t_k, k) < (t_T, target), t_k >= 0), so the query's answer
+// wave-uniform loop — the leaf test's arithmetic (light_triangle) and the
+// occlusion rule (tri_accept.h occlusion_accepts), so the query's answer
 // is unchanged — bit for bit in the precise build; in the fast build the
 // compiler may contract this inlined tri_bary differently from the leaf
 // loop's (as origin_occludes), so a near-tie can flip within the 1e-2 gate.
@@ -58,13 +73,10 @@ __device__ __forceinline__ bool lights_occlude(const DeviceScene& sc, const LdsC
   bool occ = false;
   for (uint32_t j = 0; j + 1 < sc.num_lights; ++j) {   // wave-uniform trip count
     const uint32_t k = j < tl ? j : j + 1u;            // per lane: the j-th light other than the target
-    const float4 LB = fetch_light<MODE>(sc, cx, k, 1), LD = fetch_light<MODE>(sc, cx, k, 3);
-    const float4 LF = fetch_light<MODE>(sc, cx, k, 5);
-    const uint32_t prim = fbits(LD.w);
-    const V3 p0 = mk(LB);
+    const LightTri l = light_triangle<MODE>(sc, cx, k);
     float t, u, v;
-    const bool ok = tri_bary(o, d, p0, sub(mk(LD), p0), sub(mk(LF), p0), t, u, v);
-    occ |= ok & (prim != target) & (t >= 0.0f) & (t <= tT) & ((t < tT) | (prim < target));
+    const bool ok = tri_bary(o, d, l.p0, l.e1, l.e2, t, u, v);
+    occ |= occlusion_accepts(ok, t, tT, l.prim, target);
   }
   return occ;
 }
@@ -83,7 +95,7 @@ __device__ __forceinline__ bool face_occludes(const DeviceScene& sc, const LdsCt
       const V3 p2 = mk(fetch_prim<MODE>(sc, cx, prim, 2));
       float t, u, v;
       const bool ok = tri_bary(o, d, p0, sub(p1, p0), sub(p2, p0), t, u, v);
-      occ |= ok & (prim != target) & (t >= 0.0f) & (t <= tT) & ((t < tT) | (prim < target));
+      occ |= occlusion_accepts(ok, t, tT, prim, target);
     }
   }
   return occ;
@@ -120,16 +132,23 @@ __device__ __forceinline__ bool face_occludes(const DeviceScene& sc, const LdsCt
 //     solid's other faces — the leaf test over every triangle of the solid,
 //     which is what the walk would have tested.
 // Returns whether a solid occludes; the occluder tree is not walked.
+// convex_own_skip: the solid a ray along d from primitive `origin` leaves and
+// so skips (the second rule); 0xFFFFFFFF: none.
+template <int MODE>
+__device__ __forceinline__ uint32_t convex_own_skip(const DeviceScene& sc, const LdsCtx& cx, V3 d, uint32_t origin) {
+  const uint32_t own = fbits(fetch_prim<MODE>(sc, cx, origin, 2).w);   // c * 8 + face + 1 of the origin's solid
+  const V3 own_n = mk(fetch_prim<MODE>(sc, cx, origin, 3).w, fetch_prim<MODE>(sc, cx, origin, 4).w,
+                      fetch_prim<MODE>(sc, cx, origin, 5).w);   // its face's outward unit normal (0 off the solids)
+  return ((own != 0u) & (dot(d, own_n) >= kConvexLeaveDot)) ? (own - 1u) >> 3 : 0xFFFFFFFFu;
+}
+
 // This form decides solid by solid, faces and all, inside the loop: the
 // kernels that read the scene from global memory keep it (the path kernel's
 // code is as it was); the all-in-LDS kernels take convex_occlusion below.
 template <int MODE>
 __device__ __forceinline__ bool convex_occlusion_loop(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d,
                                                       uint32_t target, float tT, uint32_t origin) {
-  const uint32_t own = fbits(fetch_prim<MODE>(sc, cx, origin, 2).w);   // c * 8 + face + 1 of the origin's solid
-  const V3 own_n = mk(fetch_prim<MODE>(sc, cx, origin, 3).w, fetch_prim<MODE>(sc, cx, origin, 4).w,
-                      fetch_prim<MODE>(sc, cx, origin, 5).w);   // its face's outward unit normal (0 off the solids)
-  const uint32_t own_skip = ((own != 0u) & (dot(d, own_n) >= kConvexLeaveDot)) ? (own - 1u) >> 3 : 0xFFFFFFFFu;
+  const uint32_t own_skip = convex_own_skip<MODE>(sc, cx, d, origin);
   bool occluded = false;
   for (uint32_t c = 0; c < sc.conv_count; ++c) {   // wave-uniform; the three slabs unrolled (scalar operands)
     const float* B = sc.conv_obb[c];
@@ -179,8 +198,9 @@ __device__ __forceinline__ bool convex_occlusion_loop(const DeviceScene& sc, con
 }
 
 // Solid c's three padded slabs against the segment [o, o + tT d], the
-// arithmetic of convex_occlusion_loop word for word: whether an interval is
-// left, and the entry / exit face (2a + side; 8 = none).
+// arithmetic of convex_occlusion_loop word for word (which keeps its own text:
+// calling this changes the path and per-bounce kernels' code):
+// whether an interval is left, and the entry / exit face (2a + side; 8 = none).
 __device__ __forceinline__ bool convex_slabs(const DeviceScene& sc, uint32_t c, V3 o, V3 d, float tT, uint32_t& fin,
                                              uint32_t& fout) {
   const float* B = sc.conv_obb[c];
@@ -219,10 +239,7 @@ __device__ __forceinline__ bool convex_slabs(const DeviceScene& sc, uint32_t c, 
 template <int MODE>
 __device__ __forceinline__ bool convex_occlusion(const DeviceScene& sc, const LdsCtx& cx, V3 o, V3 d, uint32_t target,
                                                  float tT, uint32_t origin) {
-  const uint32_t own = fbits(fetch_prim<MODE>(sc, cx, origin, 2).w);   // c * 8 + face + 1 of the origin's solid
-  const V3 own_n = mk(fetch_prim<MODE>(sc, cx, origin, 3).w, fetch_prim<MODE>(sc, cx, origin, 4).w,
-                      fetch_prim<MODE>(sc, cx, origin, 5).w);   // its face's outward unit normal (0 off the solids)
-  const uint32_t own_skip = ((own != 0u) & (dot(d, own_n) >= kConvexLeaveDot)) ? (own - 1u) >> 3 : 0xFFFFFFFFu;
+  const uint32_t own_skip = convex_own_skip<MODE>(sc, cx, d, origin);
   uint32_t plan = 0u;
   for (uint32_t c = 0; c < sc.conv_count; ++c) {   // wave-uniform; the three slabs unrolled (scalar operands)
     uint32_t fin, fout;
@@ -307,7 +324,7 @@ __device__ __forceinline__ bool origin_occludes(const DeviceScene& sc, const Lds
   const V3 p2 = mk(fetch_prim<MODE>(sc, cx, prim, 2));
   float t, u, v;
   const bool ok = tri_bary(o, d, p0, sub(p1, p0), sub(p2, p0), t, u, v);
-  return ok & (prim != target) & (t >= 0.0f) & (t <= tT) & ((t < tT) | (prim < target));
+  return occlusion_accepts(ok, t, tT, prim, target);
 }
 
 // Shadow-ray resolve under MPS nearest-hit semantics + lightSamplingHandler
@@ -358,23 +375,17 @@ __device__ __forceinline__ bool last_bounce_light_hit(const DeviceScene& sc, con
   h.found = false;
   float gd = 0.0f, gn = 1.0f;   // the nearest light's (d . n)^2 and n . n
   for (uint32_t k = 0; k < sc.num_lights; ++k) {   // wave-uniform
-    // the light record's vertices are the primitive's, in its order
-    // (scene flattening, Renderer.mm:394-413): three independent loads, and
-    // v2 - v1, v3 - v1 are the leaf record's e1, e2 bit for bit
-    const float4 LB = fetch_light<MODE>(sc, cx, k, 1), LD = fetch_light<MODE>(sc, cx, k, 3);
-    const float4 LF = fetch_light<MODE>(sc, cx, k, 5);
-    const uint32_t prim = fbits(LD.w);   // lights[k].index
-    const V3 p0 = mk(LB), e1 = sub(mk(LD), p0), e2 = sub(mk(LF), p0);
+    const LightTri l = light_triangle<MODE>(sc, cx, k);
     float t, u, v;
-    const bool ok = tri_bary(o, d, p0, e1, e2, t, u, v);
+    const bool ok = tri_bary(o, d, l.p0, l.e1, l.e2, t, u, v);
     const bool hit = ok & (t >= 0.0f) & (t <= h.t);
-    if (hit & (!h.found | (t < h.t) | (prim < h.prim))) {
+    if (hit & (!h.found | (t < h.t) | (l.prim < h.prim))) {
       h.found = true;
       h.t = t;
       h.u = u;
       h.v = v;
-      h.prim = prim;
-      const V3 n = tcross(e1, e2);
+      h.prim = l.prim;
+      const V3 n = tcross(l.e1, l.e2);
       const float dn = tdot(d, n);
       gd = dn * dn;
       gn = tdot(n, n);

@@ -139,10 +139,13 @@ __device__ __forceinline__ bool tri_pair(const DeviceScene& sc, const LdsCtx& cx
   const uint32_t prim[2] = {fbits(a0.w), fbits(b0.w)};
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
+    // (tri_accept.h occlusion_accepts, with tmin, and nearest_accepts restate the
+    // two rules; the text stands here because either call changes every
+    // kernel's code, in all three units)
     const bool hit = ok[j] & (t[j] >= tmin) & (t[j] <= h.t);
     if (any) {
       if (hit & (prim[j] != target) & ((t[j] < h.t) | (prim[j] < target))) return true;
-    } else if (hit & (!h.found | (t[j] < h.t) | (prim[j] < h.prim))) {   // (tri_accept.h nearest_accepts restates it)
+    } else if (hit & (!h.found | (t[j] < h.t) | (prim[j] < h.prim))) {
       h.found = true;
       h.t = t[j];
       if (uv) {

@@ -342,7 +342,7 @@ __global__ __launch_bounds__(kBlock, MRT_BOUNCE_WAVES) void bounce_kernel(Device
   const bool dynamic = (a.debug & 8u) == 0;
   const uint32_t cap = dynamic ? chunk + kSegSlack : chunk;
   const uint32_t out_base = blockIdx.x * cap;
-  const uint32_t rlen = ((N + kGrabRanges - 1) / kGrabRanges + kGrab - 1) / kGrab * kGrab;
+  const uint32_t rlen = grab_range_len(N);
   uint32_t cur_range = blockIdx.x % kGrabRanges, ranges_left = kGrabRanges;
   uint32_t static_base = blockIdx.x * kBlock + (tid & ~63u);
 
@@ -362,6 +362,8 @@ __global__ __launch_bounds__(kBlock, MRT_BOUNCE_WAVES) void bounce_kernel(Device
           // last exits by ~30 us: C2 +1.6 %, one GPU's 1/8 share +3.5 %;
           // publishing closed ranges in a launch-wide mask word measured
           // slower than the per-block mask alone)
+          // (the grab loop stands in each of the three kernels because one
+          // function for it, called here, changes every kernel's code: DESIGN §2.1w)
           while (ranges_left) {
             const uint32_t r0 = cur_range * rlen;
             if (r0 < N && !(__hip_atomic_load(&s_closed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & (1u << cur_range))) {

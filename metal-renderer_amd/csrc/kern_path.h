@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kBlock, MRT_PATH_WAVES) void path_kernel(DeviceScen
   __syncthreads();
   const uint32_t N = a.num_slots * a.batch;
   const uint32_t L = a.max_path_length;
-  const uint32_t rlen = ((N + kGrabRanges - 1) / kGrabRanges + kGrab - 1) / kGrab * kGrab;
+  const uint32_t rlen = grab_range_len(N);
   uint32_t cur_range = blockIdx.x % kGrabRanges, ranges_left = kGrabRanges;
   const uint32_t lane = tid & 63u;
   uint32_t* const ps = lds_u32() + cx.stack_base + threadIdx.x + (uint32_t)(STACK < 0 ? -STACK : STACK) * kBlock;
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(kBlock, MRT_PATH_WAVES) void path_kernel(DeviceScen
       if (!idle || exhausted) break;
       if (pool_next >= pool_end) {
         uint32_t got = 0xFFFFFFFFu;
-        if (lane == 0) {
+        if (lane == 0) {   // bounce_kernel's grab loop (its text: a shared function changes this kernel's code)
           while (ranges_left) {
             const uint32_t r0 = cur_range * rlen;
             if (r0 < N && !(__hip_atomic_load(&s_closed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) & (1u << cur_range))) {

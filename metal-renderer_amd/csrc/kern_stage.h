@@ -154,6 +154,13 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DeviceScene sc, const
 // and the material index as shade_hit computes them; word = the material
 // index, bit 31 set on a light triangle; a miss writes (0, 0, 0, ~0u) and
 // (0, 0, 0, -1).  A pixel is filterable iff word < kNotFilterable (dev_filter.h).
+// (The ray, the trace, the miss record and this kernel's interpolation stand
+// in both guide kernels: guide_point here, or one function for any of the
+// rest, changes the kernels' code — DESIGN §2.1w.)
+// the word of a hit from its primitive's first two shading records, as a float's bits
+__device__ __forceinline__ float guide_word(float4 r0, float4 r1) {
+  return bitsf(fbits(r0.w) | (fbits(r1.w) != 0xFFFFFFFFu ? kNotFilterable : 0u));
+}
 template <int STACK>
 __global__ __launch_bounds__(kBlock) void guide_kernel(DeviceScene sc, uint32_t W, uint32_t H, CameraBlock cam,
                                                        uint32_t moved, float4* gn, float4* gp, uint32_t* spill) {
@@ -173,8 +180,7 @@ __global__ __launch_bounds__(kBlock) void guide_kernel(DeviceScene sc, uint32_t 
       const float4 N2 = fetch_prim<kGlobal>(sc, cx, h.prim, 5);
       const V3 hv = add(add(mul(mk(P0), wu), mul(mk(P1), wv)), mul(mk(P2), ww));
       const V3 hn = normalize(add(add(mul(mk(N0), wu), mul(mk(N1), wv)), mul(mk(N2), ww)));
-      const uint32_t word = fbits(P0.w) | (fbits(P1.w) != 0xFFFFFFFFu ? kNotFilterable : 0u);
-      n = make_float4(hn.x, hn.y, hn.z, bitsf(word));
+      n = make_float4(hn.x, hn.y, hn.z, guide_word(P0, P1));
       p = make_float4(hv.x, hv.y, hv.z, h.t);
     }
     gn[i] = n;
@@ -219,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void guide_motion_kernel(DeviceScene sc, co
       for (uint32_t k = 0; k < 6; ++k) C[k] = fetch_prim<kGlobal>(sc, cx, h.prim, k);
 #pragma unroll
       for (uint32_t k = 0; k < 6; ++k) Q[k] = prev_prims[6 * (size_t)h.prim + k];
-      const float w = bitsf(fbits(C[0].w) | (fbits(C[1].w) != 0xFFFFFFFFu ? kNotFilterable : 0u));
+      const float w = guide_word(C[0], C[1]);
       V3 hv, hn;
       guide_point(C, wu, wv, ww, hv, hn);
       n = make_float4(hn.x, hn.y, hn.z, w);

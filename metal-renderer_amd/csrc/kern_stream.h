@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(Device
   uint32_t* cnt = s_rows[wave][0];
   uint32_t* alive_cnt = cnt + kStreamMaxL;   // s_rows[wave][1]
   const uint32_t N0 = a.num_slots * a.batch;
-  const uint32_t rlen = ((N0 + kGrabRanges - 1) / kGrabRanges + kGrab - 1) / kGrab * kGrab;
+  const uint32_t rlen = grab_range_len(N0);
   uint32_t cur_range = blockIdx.x % kGrabRanges, ranges_left = kGrabRanges;
   // this wave's queue: level k (1..L-1) at slots qbase + (k - 1) * kStreamCap
   const uint32_t qbase = (blockIdx.x * (kBlock / 64u) + wave) * (L > 1 ? L - 1 : 1u) * kStreamCap;
@@ -59,7 +59,8 @@ __global__ __launch_bounds__(kBlock, MRT_STREAM_WAVES) void stream_kernel(Device
     for (uint32_t k = L - 1; k >= 1; --k)
       if (cnt[k] >= 64u) { lvl = k; break; }
     if (lvl == 0 && input && pend >= pend_end) {
-      // grab kGrab camera rays from the launch's ranges (as bounce_kernel)
+      // grab kGrab camera rays from the launch's ranges (bounce_kernel's grab
+      // loop, its text: a shared function changes this kernel's code)
       uint32_t got = 0xFFFFFFFFu, gend = 0;
       if (lane == 0) {
         while (ranges_left) {

@@ -55,6 +55,23 @@ hipError_t device_cus(uint32_t* cus) {
   return e;
 }
 
+// The stack variant of a stage kernel that walks the tree (intersect, guides)
+// over `count` rays: the whole stack in LDS (STACK = kMaxStack, a block per
+// kBlock rays) while the tree's depth allows, else 32 LDS entries + the global
+// spill buffer on the capped persistent grid (STACK = -32), which needs `spill`.
+struct StageStack {
+  bool whole;      // the kMaxStack form
+  uint32_t grid;
+  size_t lds;      // bytes of dynamic LDS
+};
+hipError_t stage_stack(const DeviceScene& sc, uint32_t count, const uint32_t* spill, StageStack* v) {
+  v->whole = sc.max_stack <= (uint32_t)kMaxStack;
+  if (!v->whole && !spill) return hipErrorInvalidValue;
+  v->grid = v->whole ? blocks_for(count) : std::min<uint32_t>(blocks_for(count), kIntersectSpillGrid);
+  v->lds = (size_t)(v->whole ? kMaxStack : 32) * kBlock * 4;
+  return hipSuccess;
+}
+
 // ---- the persistent kernels' host side: one skeleton for the three kinds of
 // kernel_plan.h.  A unit instantiates a kind's kernels only where it names the
 // kind (the split fast build: the stream kernel in its own unit, below). ----
@@ -275,15 +292,11 @@ hipError_t launch_intersect(const DeviceScene& sc, const void* rays, uint32_t st
   if (count == 0) return hipSuccess;
   if (sc.width != 4) return hipErrorInvalidValue;
   const uint8_t* r = reinterpret_cast<const uint8_t*>(rays);
-  if (sc.max_stack <= (uint32_t)kMaxStack) {   // whole stack in LDS
-    const size_t lds = (size_t)kMaxStack * kBlock * 4;
-    intersect_kernel<kMaxStack><<<dim3(blocks_for(count)), dim3(kBlock), lds, s>>>(sc, r, stride, count, out, nullptr);
-  } else {                                      // 32 LDS entries + global spill, persistent grid
-    if (!spill) return hipErrorInvalidValue;
-    const size_t lds = (size_t)32 * kBlock * 4;
-    const dim3 g(std::min<uint32_t>(blocks_for(count), kIntersectSpillGrid));
-    intersect_kernel<-32><<<g, dim3(kBlock), lds, s>>>(sc, r, stride, count, out, spill);
-  }
+  StageStack v;
+  const hipError_t e = stage_stack(sc, count, spill, &v);
+  if (e != hipSuccess) return e;
+  if (v.whole) intersect_kernel<kMaxStack><<<dim3(v.grid), dim3(kBlock), v.lds, s>>>(sc, r, stride, count, out, nullptr);
+  else intersect_kernel<-32><<<dim3(v.grid), dim3(kBlock), v.lds, s>>>(sc, r, stride, count, out, spill);
   return hipGetLastError();
 }
 
@@ -294,15 +307,11 @@ hipError_t launch_guides(const DeviceScene& sc, uint32_t W, uint32_t H, const Ca
   float4* gp = reinterpret_cast<float4*>(guide_p);
   const CameraBlock cb = cam ? *cam : CameraBlock{};
   const uint32_t moved = cam ? 1u : 0u, count = W * H;
-  if (sc.max_stack <= (uint32_t)kMaxStack) {   // as launch_intersect: whole stack in LDS
-    const size_t lds = (size_t)kMaxStack * kBlock * 4;
-    guide_kernel<kMaxStack><<<dim3(blocks_for(count)), dim3(kBlock), lds, s>>>(sc, W, H, cb, moved, gn, gp, nullptr);
-  } else {                                      // 32 LDS entries + global spill, persistent grid
-    if (!spill) return hipErrorInvalidValue;
-    const size_t lds = (size_t)32 * kBlock * 4;
-    const dim3 g(std::min<uint32_t>(blocks_for(count), kIntersectSpillGrid));
-    guide_kernel<-32><<<g, dim3(kBlock), lds, s>>>(sc, W, H, cb, moved, gn, gp, spill);
-  }
+  StageStack v;
+  const hipError_t e = stage_stack(sc, count, spill, &v);
+  if (e != hipSuccess) return e;
+  if (v.whole) guide_kernel<kMaxStack><<<dim3(v.grid), dim3(kBlock), v.lds, s>>>(sc, W, H, cb, moved, gn, gp, nullptr);
+  else guide_kernel<-32><<<dim3(v.grid), dim3(kBlock), v.lds, s>>>(sc, W, H, cb, moved, gn, gp, spill);
   return hipGetLastError();
 }
 
@@ -408,16 +417,12 @@ hipError_t launch_guides_motion(const DeviceScene& sc, const float* prev_prims, 
   const float4* pp = reinterpret_cast<const float4*>(prev_prims);
   const CameraBlock cb = cam ? *cam : CameraBlock{};
   const uint32_t moved = cam ? 1u : 0u, count = W * H;
-  if (sc.max_stack <= (uint32_t)kMaxStack) {   // the two variants of launch_guides, chosen as it chooses them
-    const size_t lds = (size_t)kMaxStack * kBlock * 4;
-    guide_motion_kernel<kMaxStack><<<dim3(blocks_for(count)), dim3(kBlock), lds, s>>>(sc, pp, W, H, cb, moved, gn, gp,
-                                                                                      mn, mp, nullptr);
-  } else {
-    if (!spill) return hipErrorInvalidValue;
-    const size_t lds = (size_t)32 * kBlock * 4;
-    const dim3 g(std::min<uint32_t>(blocks_for(count), kIntersectSpillGrid));
-    guide_motion_kernel<-32><<<g, dim3(kBlock), lds, s>>>(sc, pp, W, H, cb, moved, gn, gp, mn, mp, spill);
-  }
+  StageStack v;
+  const hipError_t e = stage_stack(sc, count, spill, &v);
+  if (e != hipSuccess) return e;
+  if (v.whole)
+    guide_motion_kernel<kMaxStack><<<dim3(v.grid), dim3(kBlock), v.lds, s>>>(sc, pp, W, H, cb, moved, gn, gp, mn, mp, nullptr);
+  else guide_motion_kernel<-32><<<dim3(v.grid), dim3(kBlock), v.lds, s>>>(sc, pp, W, H, cb, moved, gn, gp, mn, mp, spill);
   return hipGetLastError();
 }
 

@@ -47,4 +47,11 @@ MRT_ACCEPT_FN bool nearest_accepts_short(bool ok, float t, float tmin, float ht,
   return hit & ((t < ht) | (prim < hprim));
 }
 
+// the occlusion rule of a shadow query towards `target` at distance tT:
+// triangle prim (in range, at t) occludes iff it is another triangle with
+// (t, prim) below (tT, target) and t in [tmin, tT]
+MRT_ACCEPT_FN bool occlusion_accepts(bool ok, float t, float tT, uint32_t prim, uint32_t target, float tmin = 0.0f) {
+  return ok & (prim != target) & (t >= tmin) & (t <= tT) & ((t < tT) | (prim < target));
+}
+
 }  // namespace mrt

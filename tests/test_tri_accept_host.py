@@ -6,8 +6,10 @@ tools/tri_accept_model.cpp compiles the header twice — without contraction
 (the precise build) and with std::fmaf where the fast build contracts, b1 + b2
 as one fma with either of its products — and runs the cross product of special
 values (±0, denormals, the neighbours of 0 and 1, ±inf, NaN) through both forms
-of the range test and of the nearest rule, then 1e6 random rays against
-triangles and their copies, many aimed at a vertex or an edge.  Part 7 of
+of the range test and of the nearest rule, and through the occlusion rule
+(occlusion_accepts, the one text of the shadow queries) against its written-out
+form, then 1e6 random rays against triangles and their copies, many aimed at a
+vertex or an edge.  Part 7 of
 tools/walk_model.cpp runs the forms on its adversarial rays (origins inside and
 on the faces of the record boxes, direction components 0, -0, ±1e-20) against
 every triangle of the scene in both arithmetics.  Cap: 0 disagreements.
@@ -53,10 +55,10 @@ def test_special_values_and_random_triangles(models, fma):
     line = r.stdout.strip()
     print(line)
     special, rand = line.split(" ; ")
-    tests, bary, nearest = _numbers(special, "tests", "bary", "nearest")
-    assert tests >= 100000 and bary == 0 and nearest == 0
-    cases, tests, bary, nearest, state = _numbers(rand, "cases", "tests", "bary", "nearest", "state")
-    assert cases == 1000000 and tests >= 8 * cases and bary == 0 and nearest == 0 and state == 0
+    tests, bary, nearest, occlusion = _numbers(special, "tests", "bary", "nearest", "occlusion")
+    assert tests >= 100000 and bary == 0 and nearest == 0 and occlusion == 0
+    cases, tests, bary, nearest, state, occlusion = _numbers(rand, "cases", "tests", "bary", "nearest", "state", "occlusion")
+    assert cases == 1000000 and tests >= 8 * cases and bary == 0 and nearest == 0 and state == 0 and occlusion == 0
 
 
 @pytest.mark.parametrize("name", ["cornellbox", "plain-1", "wedge", "plain-4"])

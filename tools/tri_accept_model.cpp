@@ -7,11 +7,14 @@
 //      0 and 1, ±inf, NaN and a few plain ones — for the range test's
 //      (det, b1, b2) with b1 + b2 as each arithmetic forms it, and for the
 //      nearest rule's (t, tmin, h.t, prim, h.prim) in every state the
-//      invariant allows (nothing found: h.prim = 0xFFFFFFFF);
+//      invariant allows (nothing found: h.prim = 0xFFFFFFFF), and for the
+//      occlusion rule's (t, tmin, t_T, prim, target) against its written-out
+//      form: in [tmin, t_T], another triangle, (t, prim) below (t_T, target);
 //   B. random rays against random triangles and their copies (equal t: the
 //      tie rule), many aimed at a vertex or an edge, where b1, b2 and their sum
 //      stand at 0 and 1: each ray folds a list of triangles into a hit with
-//      both forms, in index order and reversed.
+//      both forms, in index order and reversed, and is an occlusion query
+//      towards each of the triangles at its own t.
 // Prints one line; every count of disagreements must be 0.
 // build: g++ -O2 -std=c++17 -ffp-contract=off -DMODEL_FMA=<0|1> -I../metal-renderer_amd/csrc tri_accept_model.cpp
 // usage: tri_accept_model [random cases = 1000000]
@@ -54,7 +57,14 @@ float rnd() {
   return (float)((g_rng >> 40) & 0xFFFFFF) / 16777216.0f;
 }
 
-struct Counts { double tests = 0, bary = 0, nearest = 0, state = 0; };
+struct Counts { double tests = 0, bary = 0, nearest = 0, state = 0, occlusion = 0; };
+
+// the occlusion rule written out: the range, then the order on (t, prim)
+bool occludes(bool ok, float t, float tmin, float tT, uint32_t prim, uint32_t target) {
+  if (!ok || prim == target) return false;
+  if (!(t >= tmin) || !(t <= tT)) return false;
+  return t < tT || prim < target;
+}
 
 // dev_math.h tri_bary's terms; `alt`: b1 + b2 contracted with b1's product instead of b2's
 void tri_terms(const float* o, const float* d, const float* v0, const float* e1, const float* e2, bool alt, float& det,
@@ -125,6 +135,16 @@ int main(int argc, char** argv) {
               A.nearest += nearest_accepts(ok != 0, t, tmin, ht, found, prim, hprim) !=
                            nearest_accepts_short(ok != 0, t, tmin, ht, prim, hprim);
             }
+  // A3. the occlusion rule
+  for (int ok = 0; ok < 2; ++ok)
+    for (float t : S)
+      for (float tmin : {0.0f, -0.0f, 1e-3f})
+        for (float tT : S)
+          for (uint32_t prim : P)
+            for (uint32_t target : P) {
+              A.tests += 1;
+              A.occlusion += occlusion_accepts(ok != 0, t, tT, prim, target, tmin) != occludes(ok != 0, t, tmin, tT, prim, target);
+            }
   // B. random rays and triangles
   Counts B;
   for (long n = 0; n < cases; ++n) {
@@ -159,17 +179,23 @@ int main(int argc, char** argv) {
     for (int alt = 0; alt < (MODEL_FMA ? 2 : 1); ++alt)
       for (int rev = 0; rev < 2; ++rev) {
         Hit full{inf, 0.0f, 0.0f, kNoPrim, false}, brief = full;
+        bool ok[4];
+        float ts[4];
         for (int i = 0; i < 4; ++i) {
           const int k = rev ? 3 - i : i;
-          float det, b1, b2, sum, t;
-          tri_terms(o, d, tri[k], tri[k] + 3, tri[k] + 6, alt != 0, det, b1, b2, sum, t);
-          fold(bary_inside(det, b1, b2, sum), bary_inside_short(det, b1, b2, sum), t, (1.0f - b1) - b2, b1, prim[k], 0.0f,
-               full, brief, B);
+          float det, b1, b2, sum;
+          tri_terms(o, d, tri[k], tri[k] + 3, tri[k] + 6, alt != 0, det, b1, b2, sum, ts[k]);
+          ok[k] = bary_inside(det, b1, b2, sum);
+          fold(ok[k], bary_inside_short(det, b1, b2, sum), ts[k], (1.0f - b1) - b2, b1, prim[k], 0.0f, full, brief, B);
         }
+        for (int k = 0; k < 4; ++k)       // the occluder
+          for (int T = 0; T < 4; ++T)     // the target, at its own t (its copy: the tie)
+            B.occlusion += occlusion_accepts(ok[k], ts[k], ts[T], prim[k], prim[T]) !=
+                           occludes(ok[k], ts[k], 0.0f, ts[T], prim[k], prim[T]);
       }
   }
-  std::printf("accept forms (fma %d): special tests %.0f bary %.0f nearest %.0f ; random cases %ld tests %.0f bary %.0f "
-              "nearest %.0f state %.0f\n",
-              (int)MODEL_FMA, A.tests, A.bary, A.nearest, cases, B.tests, B.bary, B.nearest, B.state);
+  std::printf("accept forms (fma %d): special tests %.0f bary %.0f nearest %.0f occlusion %.0f ; random cases %ld tests %.0f "
+              "bary %.0f nearest %.0f state %.0f occlusion %.0f\n",
+              (int)MODEL_FMA, A.tests, A.bary, A.nearest, A.occlusion, cases, B.tests, B.bary, B.nearest, B.state, B.occlusion);
   return 0;
 }
